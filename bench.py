@@ -124,6 +124,35 @@ def cpu_baseline(batch=4, steps=3):
             "sample": f"{steps} timed full steps (fwd+bwd+SGD) of VideoMAE-base at batch {batch}, fp32 torch CPU oracle, after 1 warm-up"}
 
 
+DUMP_SAMPLE = 1 << 22            # elements per sampled array: 16 MB of float32 each, under 64 MB for the whole dump
+
+
+def _sample(flat, seed):
+    """A fixed, seeded, sorted sample of a flat tensor's elements (all of it when it is small); the same for every build."""
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat.float().cpu()
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+    return flat[idx.to(flat.device)].float().cpu()
+
+
+def dump_outputs(out_dir, model, loss, scaler):
+    """What a caller of the timed step holds after the last one: its loss (float64), the GradScaler's scale (float64), and seeded
+    samples of the updated parameters and of the gradients (float32), every parameter flattened in named_parameters() order."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.named_parameters())
+    flat_p = torch.cat([p.detach().reshape(-1).float() for _, p in params])
+    flat_g = torch.cat([(p.grad.detach() if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for _, p in params])
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64),
+              "loss_scale": np.array([float(scaler.get_scale())], dtype=np.float64),
+              "parameters_sample": _sample(flat_p, 1).numpy(),
+              "gradients_sample": _sample(flat_g, 2).numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -146,7 +175,12 @@ def main():
     ap.add_argument("--stream-input", action="store_true",
                     help="feed every step a fresh uint8 batch from pinned host memory through the upload ring (copy stream + events) "
                          "instead of re-using clips resident in HBM; reported beside the resident-input number, never as `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0): the loss, the "
+                         "loss scale, and a fixed seeded sample of the updated parameters and of the gradients (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # BVC_FORCE_LAUNCH=1: take the launcher path for one rank too (rehearses parent -> child -> RCCL on a one-GPU box)
     if (args.gpus > 1 or os.environ.get("BVC_FORCE_LAUNCH")) and "RANK" not in os.environ:
@@ -269,6 +303,8 @@ def main():
     if use_ddp:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t)
+    # before anything below steps the model again: the outputs of the last timed step
+    dumped = dump_outputs(args.dump_outputs, model, loss, scaler) if args.dump_outputs and rank == 0 else None
     # The same loop at the reference's per-GPU batch (16 clips, slurm_dev_def.bash:52) and at round 1's default (64), in the same
     # run and the same line, so that rounds stay comparable whatever the headline batch is: 3 untimed + 10 timed steps each.
     by_batch = {}
@@ -374,6 +410,8 @@ def main():
             line["comm"] = comm
         if stream_info is not None:
             line["input_stream"] = stream_info
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)

@@ -1,5 +1,6 @@
-// Multi-head self-attention forward / backward for head_dim 64 on gfx950 (no mask, no dropout),
-// flash-style: the N x N score matrix never leaves registers.
+// Multi-head self-attention forward / backward for head_dim 32, 64, 96 and 128 on gfx950 (no mask, no dropout),
+// flash-style: the N x N score matrix never leaves registers.  96 and 128 (ViT-H / ViT-g encoders padded from 80 / 88, the ViT-Ti
+// predictor) use a panel image of 64 + 32 / 64 + 64 columns (pan_w) and the two-kernel backward at every N.
 //
 // Reference semantics: softmax(Q K^T / sqrt(d)) V per (batch, head)   (HF:181-206 / SDPA, HF:239-252).
 // Layout in HBM: qkv bf16 [B*N][3*D] with q | k | v column blocks (each head a 64-wide slice),
@@ -55,11 +56,41 @@ __device__ __forceinline__ int swz_dual(int r) {
     else return (r >> 2) & 3;
 }
 
+// HD = 96 / 128: the image is made of column PANELS of 64 and 32 (96 = 64 + 32, 128 = 64 + 64), each with the row pitch and the
+// swizzle of its own width, interleaved per 16-row group: group g (rows 16 g .. 16 g + 15) at g * 16 * HD * 2 bytes, panel p at
+// p * 2048 inside it, row r of the group at r * PW * 2.  A 16-row k-step (KS) and a 32-row sub-tile (SUB) are then the same byte
+// offsets as for HD <= 64, and the swizzles only see r & 15 - the conflict-free 64- and 32-wide images are reused, not redesigned.
+template <int HD>
+constexpr int pan_w(int p) { return HD - 64 * p >= 64 ? 64 : HD - 64 * p; }
+__device__ __forceinline__ int swz_pw(int pw, int r) { return pw == 64 ? swz_dual<64>(r) : swz_dual<32>(r); }
+
+// one PW-wide panel of a 64-row tile: 1 KiB pieces of RPP rows (8 or 16: a piece never straddles a 16-row group of GB bytes)
+template <int PW, int NW>
+__device__ __forceinline__ void stage_panel(__amdgpu_buffer_rsrc_t rs, int row0, int ld, int col0, char* lds, int GB, int wave, int lane) {
+    constexpr int CPR = PW / 8;
+    constexpr int RPP = 64 / CPR;
+#pragma unroll
+    for (int jj = 0; jj < (PW / 8 + NW - 1) / NW; ++jj) {
+        const int j = wave + NW * jj;
+        if (NW > PW / 8 && j >= PW / 8) break;
+        const int r = RPP * j + lane / CPR;
+        const int c = (lane % CPR) ^ swz_dual<PW>(r);
+        const uint32_t off = (uint32_t)(((size_t)(row0 + r) * ld + col0 + c * 8) * 2);
+        const uint32_t dst = (uint32_t)((RPP * j >> 4) * GB + ((RPP * j) & 15) * PW * 2);
+        glds16(rs, off, __builtin_amdgcn_readfirstlane((uint32_t)(size_t)((AS3 char*)lds) + dst));
+    }
+}
+
 // stage rows [row0, row0+64) x HD bf16 starting at element column `col0` of a [rows][ld] bf16 array
 // into a 64 x HD LDS image (8 KiB / 4 KiB); pieces of 1 KiB, two / one per wave
 template <int HD, int NW = 4>
 __device__ __forceinline__ void stage64(__amdgpu_buffer_rsrc_t rs, int row0, int ld, int col0, char* lds,
                                         int wave, int lane) {
+    if constexpr (HD > 64) {    // panel image (see pan_w)
+        stage_panel<64, NW>(rs, row0, ld, col0, lds, 16 * HD * 2, wave, lane);
+        stage_panel<pan_w<HD>(1), NW>(rs, row0, ld, col0 + 64, lds + 2048, 16 * HD * 2, wave, lane);
+        return;
+    }
     constexpr int CPR = HD / 8;                 // 16-B chunks per row
     constexpr int RPP = 64 / CPR;               // rows per 1 KiB piece
 #pragma unroll
@@ -89,6 +120,28 @@ struct FragAddr {
 template <int HD>
 __device__ __forceinline__ FragAddr<HD> make_frag_addr(int lane) {
     FragAddr<HD> a;
+    if constexpr (HD > 64) {     // panel image (see pan_w): k-step st reads panel st / 4, transposed block t panel t / 2
+        constexpr int GB = 16 * HD * 2;
+        const int r = lane & 31, h = lane >> 5, rg = r & 15;
+#pragma unroll
+        for (int st = 0; st < HD / 16; ++st) {
+            const int pw = pan_w<HD>(st >> 2);
+            a.rows[st] = (r >> 4) * GB + (st >> 2) * 2048 + rg * pw * 2 + (((2 * (st & 3) + h) ^ swz_pw(pw, rg)) << 4);
+        }
+        const int q = (lane >> 2) & 3, p = lane & 3;
+#pragma unroll
+        for (int t = 0; t < HD / 32; ++t) {
+            const int pw = pan_w<HD>(t >> 1);
+            const int col = 32 * (t & 1) + 16 * ((lane >> 4) & 1) + 4 * p;
+            const int chunk = col >> 3, within = (col & 7) * 2;
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const int r0 = 4 * h + q + 8 * half;
+                a.tr[t][half] = (t >> 1) * 2048 + r0 * pw * 2 + ((chunk ^ swz_pw(pw, r0)) << 4) + within;
+            }
+        }
+        return a;
+    }
     constexpr int RB = HD * 2;   // bytes per tile row
     const int r = lane & 31, h = lane >> 5;
 #pragma unroll
@@ -589,8 +642,10 @@ __device__ __forceinline__ void dkdv_subtile(const AS3 char* lds, const FragAddr
 }
 
 // grid (ceil(N/128), B*H); wave w owns 32 keys; loops over query tiles (Q, dO, lse, delta staged)
+// HD = 128 (ViT-Ti predictor only): K, V fragments and the dK^T / dV^T accumulators do not fit 256 registers (it spilled 128 B per
+// lane), so that instantiation runs one workgroup per CU with the whole register file
 template <int HD>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+__global__ __launch_bounds__(256, HD > 96 ? 1 : 2) void attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                bf16_t* __restrict__ dqkv, int N, int H, int D,
                                                                uint32_t qkv_bytes, uint32_t dctx_bytes, uint32_t stat_bytes,
@@ -993,27 +1048,48 @@ static int bwd_hd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, cons
     hipLaunchKernelGGL(attn_bwd_dq_kernel<HD>, grid, dim3(256), 4 * 64 * HD * 2, stream, qkv, dctx, ctx, lse, delta, dqkv, N, H, D,
                        (uint32_t)bytes, scale, scale_log2, remap);
     }
-    if (parts & 2)
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<HD>, grid, dim3(256), 2 * (2 * 64 * HD * 2 + 512), stream, qkv, dctx, lse, delta, dqkv, N, H, D,
+    if (parts & 2) {
+    constexpr int lds_dkdv = 2 * (2 * 64 * HD * 2 + 512);
+    if constexpr (lds_dkdv > 65536) {      // HD = 128: 65 KiB, above the default dynamic LDS limit
+        static bool attr_set = false;
+        if (!attr_set) {
+            BVC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkdv_kernel<HD>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkdv));
+            attr_set = true;
+        }
+    }
+    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<HD>, grid, dim3(256), lds_dkdv, stream, qkv, dctx, lse, delta, dqkv, N, H, D,
                        (uint32_t)bytes, (uint32_t)((size_t)B * N * D * 2), (uint32_t)((size_t)B * H * N * 4), scale, scale_log2, remap);
+    }
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }
 
+static bool attn_hd_ok(int hd) { return hd == 32 || hd == 64 || hd == 96 || hd == 128; }
+
 int launch_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, int H, int head_dim, hipStream_t stream, float sm_scale) {
     BVC_REQUIRE(B > 0 && N > 0 && H > 0, "attn_fwd: empty shape");
-    BVC_REQUIRE(head_dim == 64 || head_dim == 32, "attn_fwd: head_dim %d unsupported (32 or 64)", head_dim);
+    BVC_REQUIRE(attn_hd_ok(head_dim), "attn_fwd: head_dim %d unsupported (32, 64, 96 or 128)", head_dim);
     BVC_REQUIRE((size_t)B * N * 3 * H * head_dim * 2 < 0xffffffffull, "attn_fwd: qkv larger than 4 GiB");
-    return head_dim == 64 ? fwd_hd<64>(qkv, ctx, lse, B, N, H, stream, sm_scale) : fwd_hd<32>(qkv, ctx, lse, B, N, H, stream, sm_scale);
+    switch (head_dim) {
+        case 32: return fwd_hd<32>(qkv, ctx, lse, B, N, H, stream, sm_scale);
+        case 96: return fwd_hd<96>(qkv, ctx, lse, B, N, H, stream, sm_scale);
+        case 128: return fwd_hd<128>(qkv, ctx, lse, B, N, H, stream, sm_scale);
+        default: return fwd_hd<64>(qkv, ctx, lse, B, N, H, stream, sm_scale);
+    }
 }
 
 int launch_attn_bwd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, const float* lse, float* delta,
                     bf16_t* dqkv, int B, int N, int H, int head_dim, hipStream_t stream, float sm_scale, int parts) {
     BVC_REQUIRE(B > 0 && N > 0 && H > 0, "attn_bwd: empty shape");
-    BVC_REQUIRE(head_dim == 64 || head_dim == 32, "attn_bwd: head_dim %d unsupported (32 or 64)", head_dim);
+    BVC_REQUIRE(attn_hd_ok(head_dim), "attn_bwd: head_dim %d unsupported (32, 64, 96 or 128)", head_dim);
     BVC_REQUIRE((size_t)B * N * 3 * H * head_dim * 2 < 0xffffffffull, "attn_bwd: qkv larger than 4 GiB");
-    return head_dim == 64 ? bwd_hd<64>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts)
-                          : bwd_hd<32>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
+    switch (head_dim) {
+        case 32: return bwd_hd<32>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
+        case 96: return bwd_hd<96>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
+        case 128: return bwd_hd<128>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
+        default: return bwd_hd<64>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
+    }
 }
 
 }  // namespace bvc

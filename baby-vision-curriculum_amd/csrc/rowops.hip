@@ -7,7 +7,8 @@
 
 namespace bvc {
 
-constexpr int kMaxChunks = 4;   // float4 chunks per lane: D <= 1024
+constexpr int kMaxChunks = 4;   // float4 chunks per lane: D <= 1024 (the instantiations every width up to ViT-L runs)
+constexpr int kWideChunks = 6;  // D <= 1536: ViT-H (1280), ViT-g (1408); launched only when D > 1024
 
 __device__ __forceinline__ int map_row(int m, RowMap rm) {
     return rm.rin > 0 ? (m / rm.rin) * rm.rout + rm.roff + (m % rm.rin) : m;
@@ -25,7 +26,7 @@ __device__ __forceinline__ float row_sum(float v) {
 // LPR lanes per row: 64 (one wave per row) or 32 (two rows per wave: widths up to 512 that are multiples of 128 - the decoder's and
 // the predictor's 384 - would leave half of the wave idle in the second of their 1.5 float4 chunks per lane); y = (x - mean) * rstd * gamma + beta in bf16; saves mean / rstd (biased variance,
 // torch.nn.LayerNorm semantics, HF:336-337)
-template <int LPR>
+template <int LPR, int NC>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, RowMap rm, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, bf16_t* __restrict__ y, float* __restrict__ y32,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int M, int D, float eps) {
@@ -39,17 +40,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     const int m = m0 + rsel;
     const bool live = m < M;                             // (a half-wave past the last row idles; its shuffles stay in its own half)
     const f32x4* xr = reinterpret_cast<const f32x4*>(x + (size_t)map_row(live ? m : M - 1, rm) * D);
-    f32x4 v[kMaxChunks];
+    f32x4 v[NC];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = sub + LPR * i;
         if (c < nch) { v[i] = xr[c]; s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]); }
     }
     const float mu = row_sum<LPR>(s) / D;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = sub + LPR * i;
         if (c < nch) {
 #pragma unroll
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     uint2* yr = y ? reinterpret_cast<uint2*>(y + (size_t)m * D) : nullptr;
     f32x4* yf = y32 ? reinterpret_cast<f32x4*>(y32 + (size_t)m * D) : nullptr;
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = sub + LPR * i;
         if (c < nch) {
             f32x4 o = (v[i] - mu) * rs;
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // per-workgroup partials of dgamma = sum_rows dy * xhat and dbeta = sum_rows dy go to part[block][2][D]
 // (every workgroup hammering the same D addresses with atomics serialises: measured 2x on the kernel);
 // ln_param_reduce_kernel folds them into the gradients
-template <int RPB, int LPR>
+template <int RPB, int LPR, int NC>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x, RowMap rm,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, float* __restrict__ dres,
@@ -92,9 +93,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane % LPR, rsel = lane / LPR;
     const int nch = D >> 2;
-    f32x4 gam[kMaxChunks], dg[kMaxChunks], db[kMaxChunks];
+    f32x4 gam[NC], dg[NC], db[NC];
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = sub + LPR * i;
         gam[i] = c < nch ? reinterpret_cast<const f32x4*>(gamma)[c] : f32x4{0, 0, 0, 0};
         dg[i] = f32x4{0, 0, 0, 0};
@@ -116,10 +117,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
         const f32x4* xr = reinterpret_cast<const f32x4*>(x + xrow);
         const uint2* dyr = reinterpret_cast<const uint2*>(dy + (size_t)mc * D);
         const float mu = mean[mc], rs = rstd[mc];
-        f32x4 xh[kMaxChunks], g[kMaxChunks];
+        f32x4 xh[NC], g[NC];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-        for (int i = 0; i < kMaxChunks; ++i) {
+        for (int i = 0; i < NC; ++i) {
             const int c = sub + LPR * i;
             if (c < nch) {
                 const uint2 d = dyr[c];
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
         f32x4* dr = reinterpret_cast<f32x4*>(dres + xrow);
         uint2* db16 = dres_bf ? reinterpret_cast<uint2*>(dres_bf + xrow) : nullptr;
 #pragma unroll
-        for (int i = 0; i < kMaxChunks; ++i) {
+        for (int i = 0; i < NC; ++i) {
             const int c = sub + LPR * i;
             if (c < nch) {
                 f32x4 dx = (g[i] - s1 - xh[i] * s2) * rs;
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     // cross-wave reduction of the column partials (4 RPW of them), then one partial row per workgroup
     const int slot = wave * RPW + rsel;
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = sub + LPR * i;
         if (c < nch) {
             *reinterpret_cast<f32x4*>(red + (slot * 2 + 0) * D + c * 4) = dg[i];
@@ -575,6 +576,7 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
 // used as RowGather in the target selection below
 // targets (pretrain_jepa.py:384-392): h = layer_norm(target_encoder(imgs)) without affine, rows picked by the 4 prediction
 // masks, set-major then sample:  out[(i*B + b)*Np + j] = LN(h[b*L + idx[(i*B + b)*Np + j]]).  One wave per row.
+template <int NC>
 __global__ __launch_bounds__(256) void target_select_kernel(const float* __restrict__ h, const int* __restrict__ idx,
                                                             float* __restrict__ out, int rows, int B, int Np, int L, int D, float eps) {
     const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -582,17 +584,17 @@ __global__ __launch_bounds__(256) void target_select_kernel(const float* __restr
     const int b = (m / Np) % B;
     const f32x4* xr = reinterpret_cast<const f32x4*>(h + ((size_t)b * L + idx[m]) * D);
     const int nch = D >> 2;
-    f32x4 v[kMaxChunks];
+    f32x4 v[NC];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = lane + 64 * i;
         if (c < nch) { v[i] = xr[c]; s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]); }
     }
     const float mu = wave_sum(s) / D;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = lane + 64 * i;
         if (c < nch) {
 #pragma unroll
@@ -602,7 +604,7 @@ __global__ __launch_bounds__(256) void target_select_kernel(const float* __restr
     const float rs = rsqrtf(wave_sum(q) / D + eps);
     f32x4* o = reinterpret_cast<f32x4*>(out + (size_t)m * D);
 #pragma unroll
-    for (int i = 0; i < kMaxChunks; ++i) {
+    for (int i = 0; i < NC; ++i) {
         const int c = lane + 64 * i;
         if (c < nch) o[c] = (v[i] - mu) * rs;
     }
@@ -1106,11 +1108,13 @@ constexpr int kLnFwdMaxBlocks = 4096;      // 16 per CU (the kernel holds its ro
 
 int launch_ln_fwd(const float* x, RowMap rm, const float* gamma, const float* beta, bf16_t* y, float* mean, float* rstd,
                   int M, int D, float eps, hipStream_t s, float* y32) {
-    BVC_REQUIRE(D % 4 == 0 && D <= kMaxChunks * 256, "ln_fwd: D=%d unsupported", D);
-    if (ln_half_wave_rows(D))
-        hipLaunchKernelGGL(ln_fwd_kernel<32>, dim3(balanced_grid((M + 7) / 8, kLnFwdMaxBlocks)), dim3(256), 0, s, x, rm, gamma, beta, y, y32, mean, rstd, M, D, eps);
+    BVC_REQUIRE(D % 4 == 0 && D <= kWideChunks * 256, "ln_fwd: D=%d unsupported", D);
+    if (D > kMaxChunks * 256)
+        hipLaunchKernelGGL((ln_fwd_kernel<64, kWideChunks>), dim3(balanced_grid((M + 3) / 4, kLnFwdMaxBlocks)), dim3(256), 0, s, x, rm, gamma, beta, y, y32, mean, rstd, M, D, eps);
+    else if (ln_half_wave_rows(D))
+        hipLaunchKernelGGL((ln_fwd_kernel<32, kMaxChunks>), dim3(balanced_grid((M + 7) / 8, kLnFwdMaxBlocks)), dim3(256), 0, s, x, rm, gamma, beta, y, y32, mean, rstd, M, D, eps);
     else
-        hipLaunchKernelGGL(ln_fwd_kernel<64>, dim3(balanced_grid((M + 3) / 4, kLnFwdMaxBlocks)), dim3(256), 0, s, x, rm, gamma, beta, y, y32, mean, rstd, M, D, eps);
+        hipLaunchKernelGGL((ln_fwd_kernel<64, kMaxChunks>), dim3(balanced_grid((M + 3) / 4, kLnFwdMaxBlocks)), dim3(256), 0, s, x, rm, gamma, beta, y, y32, mean, rstd, M, D, eps);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }
@@ -1137,7 +1141,7 @@ size_t ln_bwd_workspace_floats_upto(int Mmax, int D) {
 
 int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean, const float* rstd, const float* gamma,
                   float* dres, int accumulate, bf16_t* dres_bf, float* dgamma, float* dbeta, float* part, int M, int D, hipStream_t s) {
-    BVC_REQUIRE(D % 4 == 0 && D <= kMaxChunks * 256, "ln_bwd: D=%d unsupported", D);
+    BVC_REQUIRE(D % 4 == 0 && D <= kWideChunks * 256, "ln_bwd: D=%d unsupported", D);
     BVC_REQUIRE(part != nullptr, "ln_bwd: workspace missing");
     // rows per workgroup: enough workgroups to keep >= 16 waves per CU streaming (the kernel is HBM-bound and
     // each wave walks its rows serially), few enough that the per-column atomics stay negligible
@@ -1146,9 +1150,10 @@ int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean
     const int nblk = balanced_grid((M + rpg - 1) / rpg, kLnBwdMaxBlocks);
     const bool half = ln_half_wave_rows(D);
     const size_t lds = (size_t)(half ? 16 : 8) * D * sizeof(float);
-#define BVC_LN_BWD(RPB_, LPR_) hipLaunchKernelGGL((ln_bwd_kernel<RPB_, LPR_>), dim3(nblk), dim3(256), lds, s, dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D)
-    if (rpb == 16) { if (half) BVC_LN_BWD(16, 32); else BVC_LN_BWD(16, 64); }
-    else { if (half) BVC_LN_BWD(8, 32); else BVC_LN_BWD(4, 64); }
+#define BVC_LN_BWD(RPB_, LPR_, NC_) hipLaunchKernelGGL((ln_bwd_kernel<RPB_, LPR_, NC_>), dim3(nblk), dim3(256), lds, s, dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D)
+    if (D > kMaxChunks * 256) { if (rpb == 16) BVC_LN_BWD(16, 64, kWideChunks); else BVC_LN_BWD(4, 64, kWideChunks); }
+    else if (rpb == 16) { if (half) BVC_LN_BWD(16, 32, kMaxChunks); else BVC_LN_BWD(16, 64, kMaxChunks); }
+    else { if (half) BVC_LN_BWD(8, 32, kMaxChunks); else BVC_LN_BWD(4, 64, kMaxChunks); }
 #undef BVC_LN_BWD
     BVC_CHECK_HIP(hipGetLastError());
     return launch_ln_param_reduce(part, nblk, D, dgamma, dbeta, s);
@@ -1258,9 +1263,12 @@ int launch_fill_masked(float* xfull, const float* mask_token, const float* pos, 
 }
 
 int launch_target_select(const float* h, const int* idx, float* out, int nsets, int B, int Np, int L, int D, float eps, hipStream_t s) {
-    BVC_REQUIRE(D % 4 == 0 && D <= kMaxChunks * 256, "target_select: D=%d unsupported", D);
+    BVC_REQUIRE(D % 4 == 0 && D <= kWideChunks * 256, "target_select: D=%d unsupported", D);
     const int rows = nsets * B * Np;
-    hipLaunchKernelGGL(target_select_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, h, idx, out, rows, B, Np, L, D, eps);
+    if (D > kMaxChunks * 256)
+        hipLaunchKernelGGL(target_select_kernel<kWideChunks>, dim3((rows + 3) / 4), dim3(256), 0, s, h, idx, out, rows, B, Np, L, D, eps);
+    else
+        hipLaunchKernelGGL(target_select_kernel<kMaxChunks>, dim3((rows + 3) / 4), dim3(256), 0, s, h, idx, out, rows, B, Np, L, D, eps);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

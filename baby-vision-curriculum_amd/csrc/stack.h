@@ -54,7 +54,8 @@ struct Stack {
     float eps;
     std::vector<LayerAct> act;
     float* x_out;     // f32 [M][D] output of the last layer
-    // attention width: heads of hd = D / H dims run at hdp dims (hdp == hd unless hd is not 32 / 64, e.g. 24 -> 32, zero padded);
+    // attention width: heads of hd = D / H dims run at hdp dims (hdp == hd unless hd is not 32 / 64 / 96 / 128, e.g. 24 -> 32,
+    // 80 / 88 -> 96, zero padded);
     // Da = H * hdp is the row width of qkv thirds and of ctx.  Scratch below exists only when hdp != hd.
     int hd, hdp, Da;
     // set by a layer whose fc2 epilogue already produced the NEXT layer's first LayerNorm (ln1o / mean1 / rstd1), cleared by the consumer

@@ -342,6 +342,10 @@ def vit_predictor(**kwargs):
     return VisionTransformerPredictor(mlp_ratio=4, qkv_bias=True, norm_eps=1e-6, **kwargs)
 
 
+def vit_tiny(patch_size=16, **kwargs):
+    return VisionTransformer(patch_size=patch_size, embed_dim=192, depth=12, num_heads=3, mlp_ratio=4, qkv_bias=True, norm_eps=1e-6, **kwargs)
+
+
 def vit_small(patch_size=16, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=384, depth=12, num_heads=6, mlp_ratio=4, qkv_bias=True, norm_eps=1e-6, **kwargs)
 
@@ -354,8 +358,20 @@ def vit_large(patch_size=16, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4, qkv_bias=True, norm_eps=1e-6, **kwargs)
 
 
-VIT_EMBED_DIMS = {'vit_small': 384, 'vit_base': 768, 'vit_large': 1024}
-_FACTORIES = {'vit_small': vit_small, 'vit_base': vit_base, 'vit_large': vit_large, 'vit_predictor': vit_predictor}
+# head dims 80 (huge) and 88 (giant) run zero-padded to 96; the ViT-Ti predictor (384 wide, 3 heads) runs 128-wide heads
+def vit_huge(patch_size=16, **kwargs):
+    return VisionTransformer(patch_size=patch_size, embed_dim=1280, depth=32, num_heads=16, mlp_ratio=4, qkv_bias=True, norm_eps=1e-6, **kwargs)
+
+
+def vit_giant(patch_size=16, **kwargs):
+    # int(1408 * 48 / 11) = 6144, as the reference's Block computes its MLP width
+    return VisionTransformer(patch_size=patch_size, embed_dim=1408, depth=40, num_heads=16, mlp_ratio=48 / 11, qkv_bias=True, norm_eps=1e-6,
+                             **kwargs)
+
+
+VIT_EMBED_DIMS = {'vit_tiny': 192, 'vit_small': 384, 'vit_base': 768, 'vit_large': 1024, 'vit_huge': 1280, 'vit_giant': 1408}
+_FACTORIES = {'vit_tiny': vit_tiny, 'vit_small': vit_small, 'vit_base': vit_base, 'vit_large': vit_large, 'vit_huge': vit_huge,
+              'vit_giant': vit_giant, 'vit_predictor': vit_predictor}
 
 
 def get_model(device, patch_size=16, tubelet_size=1, num_frames=1, model_name='vit_base', image_size=224, pred_depth=6,

@@ -275,8 +275,9 @@ int bvc_op_gemm_kernel(const bvc_gemm_desc* problems, int count, int layout, int
 int bvc_op_row_ln_selected(int tokens, int width, int mlp_width, int heads);
 int bvc_op_gemm_plan_dw(bvc_gemm_desc* problems, int count);
 
-/* softmax(QK^T/sqrt(d))V for head_dim d = 64 or 32; qkv bf16 [B*N][3*d*H]; replaces HF:181-206 / SDPA (HF:239-252) and
- * Attention.forward of pretraining/predictive/vision_transformer.py:198-210 (the ViT-B predictor has d = 32) */
+/* softmax(QK^T/sqrt(d))V for head_dim d = 32, 64, 96 or 128; qkv bf16 [B*N][3*d*H]; replaces HF:181-206 / SDPA (HF:239-252) and
+ * Attention.forward of pretraining/predictive/vision_transformer.py:198-210 (the ViT-B predictor has d = 32, the ViT-Ti predictor
+ * d = 128; ViT-H / ViT-g encoders run their 80 / 88-wide heads zero-padded to 96) */
 int bvc_op_attention_fwd(const void* qkv, void* ctx_out, float* lse, int B, int N, int H, int head_dim, void* stream);
 int bvc_op_attention_bwd(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta_scratch,
                          void* dqkv, int B, int N, int H, int head_dim, void* stream);

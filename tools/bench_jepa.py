@@ -54,6 +54,7 @@ for _ in range(args.steps):
     loss = step()
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
-gf = {"vit_base": 160.6, "vit_large": 473.2}.get(args.model, 0.0)   # GFLOP / sample at N_ctx=100, N_pred=25
+gf = {"vit_base": 160.6, "vit_large": 473.2, "vit_tiny": 43.3, "vit_huge": 939.0, "vit_giant": 1476.8}.get(args.model, 0.0)   # GFLOP / sample at N_ctx=100, N_pred=25 (bench_legs.jepa_gflop)
 print(json.dumps({"workload": f"JEPA {args.model} 2x224^2, B={B}, N_ctx={args.nctx}, N_pred={args.npred}", "samples_per_s": round(B * args.steps / dt, 1),
-                  "ms_per_step": round(1e3 * dt / args.steps, 3), "tflops": round(gf * B * args.steps / dt / 1e3, 1), "loss": round(float(loss.detach()), 5)}))
+                  "ms_per_step": round(1e3 * dt / args.steps, 3), "tflops": round(gf * B * args.steps / dt / 1e3, 1), "loss": round(float(loss.detach()), 5),
+                  "frac_of_mfma_peak": round(gf * B * args.steps / dt / 1e3 / 2500.0, 4)}))

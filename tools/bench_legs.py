@@ -11,7 +11,22 @@ import time
 import torch
 
 JEPA_GFLOP = {"vit_base": 160.6, "vit_large": 473.2}     # per sample at N_ctx = 100, N_pred = 25
+JEPA_GFLOP.update({"vit_tiny": 43.3, "vit_huge": 939.0, "vit_giant": 1476.8})   # jepa_gflop() of the three other factories
 SIMCLR_GFLOP = 104.8                                      # per image, ViT-B/16 at 224^2
+
+
+def jepa_gflop(embed_dim, depth, mlp_hidden, nctx=100, npred=25, nsets=4, tokens=392, patch_dim=768, pred_dim=384, pred_depth=6):
+    """Algorithmic GFLOP of one JEPA training sample, SURVEY.md section 8d's counting: 2 FLOP per MAC, a transformer layer of N
+    tokens is 8 N D^2 (qkv, proj) + 4 N D I (MLP) + 4 N^2 D (scores, context); train = target fwd + 3 x (context fwd + predictor fwd),
+    with the patch embedding over all `tokens` in both encoder calls and the predictor's embed / proj over all `nsets` mask sets."""
+    def layers(n, d, i, count):
+        return count * (8 * n * d * d + 4 * n * d * i + 4 * n * n * d)
+    embed = 2 * tokens * patch_dim * embed_dim
+    target = embed + layers(tokens, embed_dim, mlp_hidden, depth)
+    context = embed + layers(nctx, embed_dim, mlp_hidden, depth)
+    predictor = nsets * (layers(nctx + npred, pred_dim, 4 * pred_dim, pred_depth) + 2 * nctx * embed_dim * pred_dim
+                         + 2 * npred * pred_dim * embed_dim)
+    return (target + 3 * (context + predictor)) / 1e9
 
 
 def _timed(step, warmup, steps):

@@ -4,6 +4,7 @@ There is no CPU fallback: if the shared library is missing or a call fails, an e
 """
 import ctypes
 import os
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BVC_LIB_PATH: another build of the same library (tools/: A/B of two builds on one box); the default is the in-tree build
@@ -94,6 +95,8 @@ SYMBOLS = {
     "bvc_version": (c_char_p, []),
     "bvc_set_option": (c_int, [c_char_p, c_int]),
     "bvc_get_option": (c_int, [c_char_p]),
+    "bvc_deterministic_workspace_bytes": (c_int64, []),
+    "bvc_deterministic_workspace_release": (c_int, []),
     "bvc_videomae_param_count": (c_int, [ctypes.POINTER(VideoMAEConfigC)]),
     "bvc_videomae_param_numel": (c_int64, [ctypes.POINTER(VideoMAEConfigC)]),
     "bvc_videomae_param_info": (c_int, [ctypes.POINTER(VideoMAEConfigC), c_int, ctypes.c_char_p, c_int,
@@ -150,6 +153,7 @@ SYMBOLS = {
                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "bvc_op_layernorm_bwd_workspace": (c_int64, [c_int, c_int]),
     "bvc_op_colsum_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_colsum_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bvc_op_cast_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "bvc_op_row_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "bvc_op_row_normalize_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -187,20 +191,54 @@ SYMBOLS = {
 
 _lib = None
 
+# Deterministic mode (include/bvc.h, option "deterministic").  The effective mode is bvc.use_deterministic_algorithms(...) OR
+# torch.are_deterministic_algorithms_enabled(), read at every library call (lib() below) and pushed to the library when it changes.
+_det_flag = False
+_det_pushed = False      # what this module last pushed (the library's own default is 0)
+
+
+def use_deterministic_algorithms(mode):
+    """Turn the library's deterministic mode on or off for this process (torch.use_deterministic_algorithms' counterpart).  While it,
+    or torch's own flag, is on, every forward and backward of the library gives the same bits on every run for the same inputs,
+    parameters, batch, device and build."""
+    global _det_flag
+    _det_flag = bool(mode)
+    lib()
+
+
+def are_deterministic_algorithms_enabled():
+    """The flag use_deterministic_algorithms set (torch's flag is ORed in at each library call, not reported here)."""
+    return _det_flag
+
+
+def _sync_deterministic(L):
+    global _det_pushed
+    torch = sys.modules.get("torch")
+    want = _det_flag or (torch is not None and torch.are_deterministic_algorithms_enabled())
+    if want != _det_pushed:
+        rc = L.bvc_set_option(b"deterministic", 1 if want else 0)
+        if rc != 0:
+            raise BvcError(f"bvc_set_option(deterministic) failed with status {rc}")
+        _det_pushed = want
+
 
 def lib():
-    """Load libbvc_hip.so once; raise loudly if it has not been built (no fallback path exists)."""
+    """Load libbvc_hip.so once; raise loudly if it has not been built (no fallback path exists).  Every call into the library goes
+    through here, which is where the effective deterministic mode is brought up to date."""
     global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise BvcError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)   # AttributeError if the library does not export a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+    if _lib is not None:
+        _sync_deterministic(_lib)
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise BvcError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                       "(hipcc --offload-arch=gfx950); there is no CPU fallback")
+    L = ctypes.CDLL(LIB_PATH)
+    for name, (res, args) in SYMBOLS.items():
+        fn = getattr(L, name)   # AttributeError if the library does not export a declared symbol
+        fn.restype = res
+        fn.argtypes = args
+    _lib = L
+    _sync_deterministic(_lib)
     return _lib
 
 
@@ -211,7 +249,9 @@ def check(rc, what=""):
 
 
 def set_option(name, value):
-    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1.  Returns the previous value."""
+    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1, "deterministic" 0 / 1 (what
+    bvc.use_deterministic_algorithms and torch.use_deterministic_algorithms switch; the library's raw flag - the next library call
+    after either of those changes resets it to their OR).  Returns the previous value."""
     old = lib().bvc_get_option(name.encode())
     check(lib().bvc_set_option(name.encode(), int(value)), "bvc_set_option")
     return old

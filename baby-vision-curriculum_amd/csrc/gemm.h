@@ -43,8 +43,20 @@ constexpr int kMaxGroup = 4;
 //               the shapes allow, -1 = never (the separate ln_fwd / ln_bwd passes)
 //   row_stagger: 1 (default) = the workgroups of a row-epilogue launch (gemm8.hip EC 4 / 5) start spread over one unit time, so that their
 //               HBM-heavy epilogues do not all fall together; 0 = all start together (A/B)
-struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; };
+//   deterministic: 1 = every reduction whose order the default kernels leave to the scheduler (f32 atomics: split-K / accumulating
+//               GEMM outputs, fused bias gradients, LayerNorm parameter partials, column sums) runs in a fixed order instead: partials
+//               go to a workspace slab with plain stores, a separate pass adds them in index order (launch_gemm, rowops.hip)
+struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; int deterministic = 0; };
 Options& options();
+
+// Workspace of the deterministic mode: library-owned, grow-only, one buffer per (device, stream) - kernels on one stream use it in
+// stream order, kernels on different streams never share it.  Returns nullptr (error set) when the allocation fails.  Grown on the
+// first deterministic launch that needs more (synchronises that stream once, then reused); never shrinks.
+float* det_scratch(size_t floats, hipStream_t stream);
+// bytes the deterministic workspace holds on the current device (all streams)
+size_t det_scratch_bytes();
+// synchronise the current device and free its deterministic workspaces (all streams)
+int det_scratch_release();
 
 // bvc_op_gemm_kernel: while `on`, the launchers write the name of the kernel instantiation they would launch (as rocprofv3
 // prints it) and launch nothing - what bench.py uses to attribute its per-product timings to the rows of a kernel-stats table.

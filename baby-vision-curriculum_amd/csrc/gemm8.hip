@@ -151,14 +151,18 @@ __device__ __forceinline__ void decode_unit(const GemmGroup& g, int uid, Unit& u
 
 // EC (epilogue class): 0 = bf16 outputs without side inputs (BF16, GELU, RELU); 3 = bf16 outputs gated by a bf16 side input (DGELU,
 // DRELU); 1 = f32 side inputs / outputs (F32, RESID, POS, E2D, LOSS, F32_BF16); 2 = weight gradients (TN): f32 store or split-K
-// atomics, fused bias gradient.  Classes are separate instantiations because the side inputs of a whole unit sit in registers.
+// atomics, fused bias gradient; 6 = class 2 of the deterministic mode: where class 2 adds by f32 atomics (split-K / accumulating outputs,
+// the bias gradient) it stores the unit's partials into workspace slabs instead - p.partial = [split][M][N], p.ln_part = [split][M] -
+// which launch_gemm's fixed-order reduce adds onto C / rowsum (no balanced walk: its tail units would need slabs of their own).
+// Classes are separate instantiations because the side inputs of a whole unit sit in registers.
 template <int BM, int BN, bool AT, bool BT, int EC>
 __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const int total_units) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(BM == 256 || (BM == 128 && BN == 384), "128-row tiles: the 128 x 384 geometry only");
     static_assert(BN == 256 || BN == 128 || (BN == 384 && BM == 128), "column tiles of 256 / 128, or 384 with 128 rows");
-    static_assert((EC >= 4) == (BM == 128 && !AT), "row epilogues (EC 4 / 5) are the k-contiguous-A instantiations of the 128 x 384 tile, and only they");
-    static_assert(BM == 256 || EC >= 4 || (AT && BT && EC == 2), "128 x 384 with transposed A: weight gradients");
+    static_assert((EC == 4 || EC == 5) == (BM == 128 && !AT), "row epilogues (EC 4 / 5) are the k-contiguous-A instantiations of the 128 x 384 tile, and only they");
+    static_assert(BM == 256 || EC == 4 || EC == 5 || (AT && BT && (EC == 2 || EC == 6)), "128 x 384 with transposed A: weight gradients");
+    static_assert(EC != 6 || (AT && BT), "EC 6 (deterministic weight gradients) is a TN product");
     static_assert(EC != 4 || !BT, "EC 4 (residual + LayerNorm forward) is an NT product");
     constexpr int A_BYTES = BM * 64 * 2, B_BYTES = BN * 64 * 2, TILE = A_BYTES + B_BYTES;
     constexpr int WMR = BM / 2;                          // rows of a wave row
@@ -219,7 +223,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
         }
         return;
     }
-    if constexpr (EC >= 4) {
+    if constexpr (EC == 4 || EC == 5) {
         // Row epilogues move 490 - 690 KB per unit through HBM while a unit's K loop needs only its A rows: with every workgroup
         // starting together the epilogues of a round fall together - all CUs queue on HBM, then all CUs compute and leave it idle
         // (measured: unit time = K loop + epilogue at the fair share of 5.5 TB/s, profiles/r05_d_*).  The workgroups of an XCD that
@@ -412,7 +416,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
 #pragma unroll
             for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         float rsum[2] = {0.f, 0.f};
-        const bool do_rowsum = EC == 2 && p.rowsum != nullptr && cu.n0 == 0;   // bias gradient: wave wn takes row tiles wn and 4 + wn
+        const bool do_rowsum = (EC == 2 || EC == 6) && p.rowsum != nullptr && cu.n0 == 0;   // bias gradient: wave wn takes row tiles wn and 4 + wn
 
         // one K tile out of LDS slot `cur`; `oth` is the other slot
         auto ktile = [&](auto rs_, char* cur, char* oth) {
@@ -545,8 +549,8 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
         };
 
         for (int kt = 0; kt < cu.nkt; kt += 2) {
-            ktile(std::bool_constant<EC == 2>{}, buf0, buf1);
-            ktile(std::bool_constant<EC == 2>{}, buf1, buf0);
+            ktile(std::bool_constant<EC == 2 || EC == 6>{}, buf0, buf1);
+            ktile(std::bool_constant<EC == 2 || EC == 6>{}, buf1, buf0);
         }
 
         // ------------------------------------------------------------------ epilogue of this unit
@@ -817,6 +821,8 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
             // aligned pieces of one or two output rows per wave-instruction; f32 atomics when K is split (the memory-side atomic units
             // take a wave-instruction as four 64-byte requests whatever the rows), plain stores otherwise.  Once per ~900 K tiles.
             const __amdgpu_buffer_rsrc_t rca = make_rsrc(p.C, kDrop);
+            // (EC 6: the partials of a split / accumulating unit go to its slab, rows of N floats)
+            const __amdgpu_buffer_rsrc_t rsl = make_rsrc(EC == 6 && atomic ? p.partial + (size_t)cu.split * Mrows * Ncols : p.C, kDrop);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -832,15 +838,20 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
                         const int m = m0 + wm * WMR + 16 * i + row, n = n0 + wn * WN + 48 * ps + col;
                         const float v = *reinterpret_cast<const AS3 float*>(wl + row * 192 + col * 4) * alpha;
                         const uint32_t o = (m < Mrows && n < Ncols) ? (uint32_t)(((size_t)m * ldc + n) * 4) : kDrop;
-                        if (atomic) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v, rca, o, 0, 0);
-                        else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rca, o, 0, 0);
+                        if constexpr (EC == 6) {
+                            if (atomic) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsl, (m < Mrows && n < Ncols) ? (uint32_t)(((size_t)m * Ncols + n) * 4) : kDrop, 0, 0);
+                            else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rca, o, 0, 0);
+                        } else {
+                            if (atomic) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v, rca, o, 0, 0);
+                            else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rca, o, 0, 0);
+                        }
                     }
                 }
             }
-        } else if (EC == 2 && atomic) {
+        } else if ((EC == 2 || EC == 6) && atomic) {
             // split-K: f32 atomics, one dword per lane, whole contiguous rows per wave-instruction (256 B / two 128-B rows: the shape
             // the memory-side atomic units take at full rate), through a buffer descriptor (32-bit offsets, dropped when out of range)
-            const __amdgpu_buffer_rsrc_t rca = make_rsrc(p.C, kDrop);
+            const __amdgpu_buffer_rsrc_t rca = make_rsrc(EC == 6 ? p.partial + (size_t)cu.split * Mrows * Ncols : p.C, kDrop);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 park(i);
@@ -851,8 +862,9 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
                     const int m = m0 + wm * WMR + 16 * i + row, n = n0 + wn * WN + col;
                     const int unit = (col >> 2) ^ (row & (UNITS - 1));
                     const float v = *reinterpret_cast<const AS3 float*>(wl + row * (WN * 4) + unit * 16 + (col & 3) * 4) * alpha;
-                    const uint32_t o = (m < Mrows && n < Ncols) ? (uint32_t)(((size_t)m * ldc + n) * 4) : kDrop;
-                    __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v, rca, o, 0, 0);
+                    const uint32_t o = (m < Mrows && n < Ncols) ? (uint32_t)(((size_t)m * (EC == 6 ? Ncols : ldc) + n) * 4) : kDrop;
+                    if constexpr (EC == 6) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rca, o, 0, 0);
+                    else __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v, rca, o, 0, 0);
                 }
             }
         } else {
@@ -867,7 +879,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
                 return (m < Mrows && ncol_ok) ? (uint32_t)(((size_t)m * ld + n) * esz) : kDrop;
             };
             f32x4 bias0 = {0.f, 0.f, 0.f, 0.f}, bias1 = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (EC != 2) {
+            if constexpr (EC != 2 && EC != 6) {
                 const __amdgpu_buffer_rsrc_t rbias = make_rsrc(p.bias, p.bias ? kDrop : 0u);
                 const uint32_t ob = ncol_ok ? (uint32_t)n * 4u : kDrop;
                 bias0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rbias, ob, 0, 0));
@@ -1020,7 +1032,11 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
                 v += __shfl_xor(v, 16, 64);
                 v += __shfl_xor(v, 32, 64);
                 const int m = m0 + wm * WMR + 16 * (TMH * mh + wn) + lane;
-                if (wn < TMH && (lane >> 4) == 0 && m < p.M) atomicAdd(p.rowsum + m, v * alpha);
+                if constexpr (EC == 6) {
+                    if (wn < TMH && (lane >> 4) == 0 && m < p.M) p.ln_part[(size_t)cu.split * p.M + m] = v * alpha;
+                } else {
+                    if (wn < TMH && (lane >> 4) == 0 && m < p.M) atomicAdd(p.rowsum + m, v * alpha);
+                }
             }
         }
         uid += u_step;
@@ -1028,7 +1044,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
         decode_unit<BM, BN>(g, uid, cu);
         // (atomics and the 384-wide tile's dword stores queue behind the prefetch like any store: the plain counted wait of the next
         //  K tile then waits for them as well - once per unit, conservative and exact)
-        after_epi = EC >= 4 ? -1 : ((EC == 2 && atomic) || BN == 384) ? 0 : EC == 0 ? nstores : -1;
+        after_epi = (EC == 4 || EC == 5) ? -1 : (((EC == 2 || EC == 6) && atomic) || BN == 384) ? 0 : EC == 0 ? nstores : -1;
     }
     // drain the out-of-range tail of the stream, then pay back the stagger barrier
     wait_vmcnt<0>();
@@ -1112,7 +1128,7 @@ static int launch_gemm8_one(const GemmGroup& g_in, int total, hipStream_t stream
     if constexpr (EC == 2) {
         if (plan_balance(g, BM, BN, total, ncu)) grid = ncu;    // the full-length units partition over the XCDs as before; every CU gets a workgroup
     }
-    if constexpr (EC >= 4) {
+    if constexpr (EC == 4 || EC == 5) {
         // one unit's time in 64-cycle quanta at ~2.1 GHz: 1.45 us per 128 x 384 x 64 K tile + the epilogue's bytes at a CU's fair share of HBM
         const double us = 1.45 * ((g.prob[0].K + 63) / 64) + (EC == 4 ? 23.0 : 32.0);
         g.stagger = options().row_stagger && total > ncu ? (int)(us * 33.0) : 0;
@@ -1139,7 +1155,7 @@ static int epi_class(int epi, GemmLayout layout) {
 
 // Launcher hook used by launch_gemm (gemm.hip): bn = 256 / 128 (256-row tiles) or 384 (128-row tiles, weight gradients only).
 // Returns BVC_OK after launching, 1 when the group is not eligible.
-int launch_gemm8(const GemmGroup& g, GemmLayout layout, int bn, hipStream_t stream) {
+int launch_gemm8(const GemmGroup& g, GemmLayout layout, int bn, hipStream_t stream, bool det) {
     const int total = g.tile_start[g.nprob];
     int ec = -2;
     for (int i = 0; i < g.nprob; ++i) {
@@ -1158,7 +1174,8 @@ int launch_gemm8(const GemmGroup& g, GemmLayout layout, int bn, hipStream_t stre
     if (total <= 0) return 1;
 #define BVC_G8(BN_, AT_, BT_, EC_) return launch_gemm8_one<256, BN_, AT_, BT_, EC_>(g, total, stream)
     if (bn == 384) {
-        if (layout == GEMM_TN) return ec == 2 ? launch_gemm8_one<128, 384, true, true, 2>(g, total, stream) : 1;
+        if (layout == GEMM_TN) return ec != 2 ? 1 : det ? launch_gemm8_one<128, 384, true, true, 6>(g, total, stream)
+                                                        : launch_gemm8_one<128, 384, true, true, 2>(g, total, stream);
         // row epilogues: one problem whose rows are exactly one tile wide, offsets of whole rows inside 32 bits
         const GemmProblem& p = g.prob[0];
         if (g.nprob != 1 || p.N != 384 || p.ldc != 384 || (double)p.M * 1536.0 >= 4294000000.0) return 1;
@@ -1175,6 +1192,8 @@ int launch_gemm8(const GemmGroup& g, GemmLayout layout, int bn, hipStream_t stre
         if (ec == 0) { if (bn == 256) BVC_G8(256, false, true, 0); else BVC_G8(128, false, true, 0); }
         if (ec == 3) { if (bn == 256) BVC_G8(256, false, true, 3); else BVC_G8(128, false, true, 3); }
         if (ec == 1) { if (bn == 256) BVC_G8(256, false, true, 1); else BVC_G8(128, false, true, 1); }
+    } else if (det) {
+        if (bn == 256) BVC_G8(256, true, true, 6); else BVC_G8(128, true, true, 6);
     } else {
         if (bn == 256) BVC_G8(256, true, true, 2); else BVC_G8(128, true, true, 2);
     }

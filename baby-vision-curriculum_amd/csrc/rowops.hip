@@ -2,6 +2,7 @@
 // bias gradients, parameter cast, mask -> index lists, tube-patch gather, pixel targets, decoder
 // input fill, loss finalize.  All are one-pass streaming kernels with 8-16 B per lane accesses.
 #include "rowops.h"
+#include "gemm.h"
 
 #include <algorithm>
 
@@ -187,10 +188,78 @@ __global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __res
     atomicAdd(c < D ? dgamma + c : dbeta + (c - D), s);
 }
 
+// Deterministic mode (options().deterministic): column c of nrows partial rows of W floats, added in row order onto its output -
+// out0[c] for c < split, out1[c - split] otherwise: v = out + part[0][c] + part[1][c] + ...  Replaces the atomics of
+// ln_param_reduce_kernel (part = the [2][D] rows, split = D) and of the column sums (their per-row-block partials, split = W).
+// grid ceil(W / 256); 8 loads in flight per thread.
+__global__ __launch_bounds__(256) void det_rows_reduce_kernel(const float* __restrict__ part, int nrows, int W, int split,
+                                                              float* __restrict__ out0, float* __restrict__ out1) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= W) return;
+    float* o = c < split ? out0 + c : out1 + (c - split);
+    float s = *o;
+    int b = 0;
+    for (; b + 8 <= nrows; b += 8) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = part[(size_t)(b + i) * W + c];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += v[i];
+    }
+    for (; b < nrows; ++b) s += part[(size_t)b * W + c];
+    *o = s;
+}
+// first pass of the two-pass form: mid[y][c] = part[y per][c] + ... + part[y per + per - 1][c] (row order; grid (ceil(W / 256), chunks))
+__global__ __launch_bounds__(256) void det_rows_chunk_kernel(const float* __restrict__ part, int nrows, int W, int per,
+                                                             float* __restrict__ mid) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= W) return;
+    const int b0 = blockIdx.y * per, b1 = min(nrows, b0 + per);
+    float s = 0.f;
+    int b = b0;
+    for (; b + 8 <= b1; b += 8) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = part[(size_t)(b + i) * W + c];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += v[i];
+    }
+    for (; b < b1; ++b) s += part[(size_t)b * W + c];
+    mid[(size_t)blockIdx.y * W + c] = s;
+}
+
+// Fixed-order column reduce of nrows partial rows (deterministic mode).  One thread per column alone leaves the chip idle (W = 2 D = 768
+// columns = 3 workgroups walking ~10^4 rows: 2.6 ms per step at 256 clips); rows are therefore summed in chunks of ~sqrt(nrows), in
+// order, then the chunk sums in order - the same association on every run.  `mid` = det_rows_chunks(nrows) x W floats of scratch.
+static int det_rows_chunk_rows(int nrows) {
+    int per = 16;
+    while ((long long)per * per < nrows) per *= 2;
+    return per;
+}
+static size_t det_rows_mid_floats(int nrows, int W) {
+    const int per = det_rows_chunk_rows(nrows);
+    return nrows > per ? (size_t)((nrows + per - 1) / per) * W : 0;
+}
+static int launch_det_rows_reduce(const float* part, int nrows, int W, int split, float* out0, float* out1, float* mid, hipStream_t s) {
+    const int per = det_rows_chunk_rows(nrows);
+    if (nrows > per) {
+        const int chunks = (nrows + per - 1) / per;
+        hipLaunchKernelGGL(det_rows_chunk_kernel, dim3((W + 255) / 256, chunks), dim3(256), 0, s, part, nrows, W, per, mid);
+        BVC_CHECK_HIP(hipGetLastError());
+        part = mid;
+        nrows = chunks;
+    }
+    hipLaunchKernelGGL(det_rows_reduce_kernel, dim3((W + 255) / 256), dim3(256), 0, s, part, nrows, W, split, out0, out1);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
 // ============================================================================ column sums
 // out[n] += alpha * sum_m X[m][n]   (bias gradients), X bf16 [M][ld]; grid (ceil(N/512), ceil(M/RB))
-__global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ X, int M, int N, int ld, float alpha,
-                                                          const float* __restrict__ alpha_dev, float* __restrict__ out, int RB) {
+// DET: no atomics - row block y writes its partial row to out[y][N] (det_rows_reduce_kernel adds them in order)
+template <bool DET>
+__device__ __forceinline__ void colsum_bf16_body(const bf16_t* __restrict__ X, int M, int N, int ld, float alpha,
+                                                 const float* __restrict__ alpha_dev, float* __restrict__ out, int RB) {
     __shared__ float red[4][512];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = (blockIdx.x * 64 + lane) * 8;
@@ -208,13 +277,25 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restri
     __syncthreads();
     for (int c = threadIdx.x; c < 512; c += 256) {
         const int n = blockIdx.x * 512 + c;
-        if (n < N) atomicAdd(out + n, (alpha_dev ? alpha * alpha_dev[0] : alpha) * ((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])));
+        if (n < N) {
+            const float v = (alpha_dev ? alpha * alpha_dev[0] : alpha) * ((red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
+            if constexpr (DET) out[(size_t)blockIdx.y * N + n] = v;
+            else atomicAdd(out + n, v);
+        }
     }
+}
+__global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ X, int M, int N, int ld, float alpha,
+                                                          const float* __restrict__ alpha_dev, float* __restrict__ out, int RB) {
+    colsum_bf16_body<false>(X, M, N, ld, alpha, alpha_dev, out, RB);
+}
+__global__ __launch_bounds__(256) void colsum_bf16_det_kernel(const bf16_t* __restrict__ X, int M, int N, int ld, float alpha,
+                                                              const float* __restrict__ alpha_dev, float* __restrict__ part, int RB) {
+    colsum_bf16_body<true>(X, M, N, ld, alpha, alpha_dev, part, RB);
 }
 
 // out[n] += sum over mapped rows of X f32 [..][D]   (mask-token gradient); grid (ceil(D/256), ceil(M/RB))
-__global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict__ X, RowMap rm, int M, int D,
-                                                         float* __restrict__ out, int RB) {
+template <bool DET>
+__device__ __forceinline__ void colsum_f32_body(const float* __restrict__ X, RowMap rm, int M, int D, float* __restrict__ out, int RB) {
     __shared__ float red[4][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = (blockIdx.x * 64 + lane) * 4;
@@ -228,7 +309,19 @@ __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict
     __syncthreads();
     const int c = threadIdx.x;
     const int n = blockIdx.x * 256 + c;
-    if (n < D) atomicAdd(out + n, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
+    if constexpr (DET) {
+        if (n < D) out[(size_t)blockIdx.y * D + n] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+    } else {
+        if (n < D) atomicAdd(out + n, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
+    }
+}
+__global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict__ X, RowMap rm, int M, int D,
+                                                         float* __restrict__ out, int RB) {
+    colsum_f32_body<false>(X, rm, M, D, out, RB);
+}
+__global__ __launch_bounds__(256) void colsum_f32_det_kernel(const float* __restrict__ X, RowMap rm, int M, int D,
+                                                             float* __restrict__ part, int RB) {
+    colsum_f32_body<true>(X, rm, M, D, part, RB);
 }
 
 // out[b][d] = mean over the N tokens of clip b (sequence_output.mean(1), HF VideoMAEForVideoClassification.forward);
@@ -1161,6 +1254,14 @@ int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean
 
 int launch_ln_param_reduce(const float* part, int nblk, int D, float* dgamma, float* dbeta, hipStream_t s) {
     BVC_REQUIRE(part && dgamma && dbeta && nblk > 0 && D > 0, "ln_param_reduce: bad argument");
+    if (options().deterministic) {     // all partial rows in index order, no atomics
+        float* mid = nullptr;
+        if (const size_t f = det_rows_mid_floats(nblk, 2 * D)) {
+            mid = det_scratch(f, s);
+            if (!mid) return BVC_ERR_HIP;
+        }
+        return launch_det_rows_reduce(part, nblk, 2 * D, D, dgamma, dbeta, mid, s);
+    }
     hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * D + 255) / 256, (nblk + 15) / 16), dim3(256), 0, s, part, nblk, D, dgamma, dbeta);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
@@ -1169,6 +1270,15 @@ int launch_ln_param_reduce(const float* part, int nblk, int D, float* dgamma, fl
 int launch_colsum_bf16_scaled(const bf16_t* X, int M, int N, int ld, float alpha, const float* alpha_dev, float* out, hipStream_t s) {
     BVC_REQUIRE(N % 8 == 0 && ld % 8 == 0, "colsum_bf16: N and ld must be multiples of 8");
     const int RB = M >= 16384 ? 256 : 64;
+    if (options().deterministic) {     // partial rows into the workspace, then a fixed-order column reduce
+        const int nrb = (M + RB - 1) / RB;
+        if (nrb <= 0) return BVC_OK;
+        float* part = det_scratch((size_t)nrb * N + det_rows_mid_floats(nrb, N), s);
+        if (!part) return BVC_ERR_HIP;
+        hipLaunchKernelGGL(colsum_bf16_det_kernel, dim3((N + 511) / 512, nrb), dim3(256), 0, s, X, M, N, ld, alpha, alpha_dev, part, RB);
+        BVC_CHECK_HIP(hipGetLastError());
+        return launch_det_rows_reduce(part, nrb, N, N, out, out, part + (size_t)nrb * N, s);
+    }
     hipLaunchKernelGGL(colsum_bf16_kernel, dim3((N + 511) / 512, (M + RB - 1) / RB), dim3(256), 0, s, X, M, N, ld, alpha, alpha_dev, out, RB);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
@@ -1181,6 +1291,15 @@ int launch_colsum_bf16(const bf16_t* X, int M, int N, int ld, float alpha, float
 int launch_colsum_f32(const float* X, RowMap rm, int M, int D, float* out, hipStream_t s) {
     BVC_REQUIRE(D % 4 == 0, "colsum_f32: D must be a multiple of 4");
     const int RB = 256;
+    if (options().deterministic) {
+        const int nrb = (M + RB - 1) / RB;
+        if (nrb <= 0) return BVC_OK;
+        float* part = det_scratch((size_t)nrb * D + det_rows_mid_floats(nrb, D), s);
+        if (!part) return BVC_ERR_HIP;
+        hipLaunchKernelGGL(colsum_f32_det_kernel, dim3((D + 255) / 256, nrb), dim3(256), 0, s, X, rm, M, D, part, RB);
+        BVC_CHECK_HIP(hipGetLastError());
+        return launch_det_rows_reduce(part, nrb, D, D, out, out, part + (size_t)nrb * D, s);
+    }
     hipLaunchKernelGGL(colsum_f32_kernel, dim3((D + 255) / 256, (M + RB - 1) / RB), dim3(256), 0, s, X, rm, M, D, out, RB);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;

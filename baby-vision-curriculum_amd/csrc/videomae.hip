@@ -151,6 +151,7 @@ int bvc_set_option(const char* name, int value) {
     else if (!strcmp(name, "dw_overlap")) options().dw_overlap = value != 0;
     else if (!strcmp(name, "row_stagger")) options().row_stagger = value != 0;
     else if (!strcmp(name, "row_ln")) { BVC_REQUIRE(value >= -1 && value <= 1, "set_option: row_ln takes -1 / 0 / 1"); options().row_ln = value; }
+    else if (!strcmp(name, "deterministic")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: deterministic takes 0 / 1"); options().deterministic = value; }
     else BVC_REQUIRE(false, "set_option: unknown option '%s'", name);
     return BVC_OK;
 }
@@ -159,6 +160,7 @@ int bvc_get_option(const char* name) {
     if (name && !strcmp(name, "dw_overlap")) return options().dw_overlap;
     if (name && !strcmp(name, "row_ln")) return options().row_ln;
     if (name && !strcmp(name, "row_stagger")) return options().row_stagger;
+    if (name && !strcmp(name, "deterministic")) return options().deterministic;
     bvc::set_error("get_option: unknown option '%s'", name ? name : "(null)");
     return BVC_ERR_INVALID;
 }
@@ -545,6 +547,8 @@ int bvc_op_gemm_kernel(const bvc_gemm_desc* problems, int count, int layout, int
     if (rc == BVC_OK) snprintf(name, name_cap, "%s", d.name);
     return rc;
 }
+int64_t bvc_deterministic_workspace_bytes(void) { return (int64_t)det_scratch_bytes(); }
+int bvc_deterministic_workspace_release(void) { return det_scratch_release(); }
 int bvc_op_gemm_plan_dw(bvc_gemm_desc* problems, int count) {
     BVC_REQUIRE(problems && count >= 1 && count <= 4, "op_gemm_plan_dw: bad argument");
     return plan_dw(problems, count);
@@ -583,6 +587,10 @@ int bvc_op_layernorm_bwd(const void* dy, const float* x, int rin, int rout, int 
                          dgamma, dbeta, workspace, M, D, (hipStream_t)stream);
 }
 int64_t bvc_op_layernorm_bwd_workspace(int M, int D) { return (int64_t)ln_bwd_workspace_floats(M, D); }
+int bvc_op_colsum_f32(const float* X, int rin, int rout, int roff, int M, int D, float* out, void* stream) {
+    BVC_REQUIRE(X && out && M > 0 && D > 0, "op_colsum_f32: bad argument");
+    return launch_colsum_f32(X, RowMap{rin, rout, roff}, M, D, out, (hipStream_t)stream);
+}
 int bvc_op_colsum_bf16(const void* X, int M, int N, int ld, float alpha, const float* alpha_dev, float* out, void* stream) {
     BVC_REQUIRE(X && out, "op_colsum_bf16: null argument");
     return launch_colsum_bf16_scaled((const bf16_t*)X, M, N, ld, alpha, alpha_dev, out, (hipStream_t)stream);

@@ -44,9 +44,28 @@ const char* bvc_version(void);
  *   "row_ln"      the LayerNorms of 384-wide stacks (VideoMAE decoder, JEPA predictor) inside the epilogues of the products next to
  *                 them (BVC_EPI_RESID_LN / BVC_EPI_DLN): 0 (default) = the measured selection, 1 = whenever the shapes allow,
  *                 -1 = never (separate LayerNorm passes)
- * bvc_get_option returns the value, or BVC_ERR_INVALID for an unknown name. */
+ *   "deterministic" 0 (default) / 1: while 1, every forward and backward entry point (bvc_videomae_*, bvc_vit_*, bvc_predictor_*,
+ *                 bvc_op_*) gives the same bits on every run for the same inputs, parameters, batch, device and build.  The f32 atomics
+ *                 whose arrival order the scheduler decides - split-K / accumulating GEMM outputs (tile config 13 included), fused bias
+ *                 gradients (rowsum), LayerNorm parameter partials, column sums - are replaced by plain stores of the partials into a
+ *                 workspace and a separate pass that adds them in a fixed order.  Results differ from mode 0 in the last bits only.
+ *                 Workspace: library-owned, grow-only, one buffer per (device, stream) - so that work on two streams never shares
+ *                 one - allocated by the first deterministic launch on that stream that needs more (a growth synchronises that
+ *                 stream once) and reused afterwards; model contexts and bvc_op_* callers share it.  It lives until
+ *                 bvc_deterministic_workspace_release() or the end of the process: a process that creates and destroys streams should
+ *                 release it after destroying them (each stream ever used keeps its buffer, and a new stream that reuses a destroyed
+ *                 stream's handle would take over that buffer).  Tile configs that have no deterministic form (the experiment
+ *                 kernels 3-5, 8, 14 of a -DBVC_EXPERIMENTS build) return BVC_ERR_INVALID for split / accumulating / bias-gradient
+ *                 outputs; tile configs 6 / 7 / 9 run them on the 128 x 128 / 128 x 64 deterministic kernel.
+ *                 Read at every launch, so it may change between calls (not while a call is being enqueued elsewhere).
+ * bvc_get_option returns the value, or BVC_ERR_INVALID for an unknown name; bvc_set_option rejects values outside the list. */
 int bvc_set_option(const char* name, int value);
 int bvc_get_option(const char* name);
+/* bytes the deterministic mode's workspace holds on the current HIP device (all streams; 0 before its first use) */
+int64_t bvc_deterministic_workspace_bytes(void);
+/* synchronises the current HIP device, then frees its deterministic workspaces (all streams); the next deterministic launch
+ * allocates again */
+int bvc_deterministic_workspace_release(void);
 
 /* ------------------------------------------------------------------------------------------------
  * VideoMAE pre-training step.
@@ -293,6 +312,9 @@ int bvc_op_layernorm_bwd(const void* dy_bf16, const float* x, int rin, int rout,
                          float* dgamma, float* dbeta, float* workspace, int M, int D, void* stream);
 int64_t bvc_op_layernorm_bwd_workspace(int M, int D);
 int bvc_op_colsum_bf16(const void* X, int M, int N, int ld, float alpha, const float* alpha_dev, float* out, void* stream);
+/* out[n] += sum over rows m of X f32 [M][D] (rows strided by (rin, rout, roff) as for LayerNorm, rin <= 0 = dense): the mask-token
+ * gradient of the VideoMAE decoder / JEPA predictor; D % 4 == 0 */
+int bvc_op_colsum_f32(const float* X, int rin, int rout, int roff, int M, int D, float* out, void* stream);
 int bvc_op_cast_bf16(const float* in, void* out, int64_t n, void* stream);
 /* SimCLR loss pieces (info_nce_loss, pretraining/contrastive/pretrain_simclr.py:114-128, with its masks :284-292):
  * row_normalize = the two norms of F.cosine_similarity; the (2B x 2B) similarity is a GEMM of the normalised rows with

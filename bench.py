@@ -1,6 +1,6 @@
 """Headline benchmark: VideoMAE-base 16x224^2 pre-training clips/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -8,6 +8,11 @@ One step = the reference's loop body (pretraining/generative/pretrain_videomae.p
 masks -> device, zero_grad, forward, loss all-reduce, GradScaler-scaled backward (with the bucketed RCCL
 gradient all-reduce overlapped when N > 1), scaler.step(SGD-Nesterov), scaler.update - on synthetic clips
 that are already resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the line's headline figures need: set-up, warm-up, the timed steps, --dump-outputs,
+the line.  --full adds everything else the benchmark measures, after the timed steps and outside them:
+the 64- / 16-clip legs (`by_batch`), the per-kernel probes (`roofline.kernel(s)`), BASELINE configs 4 / 5
+(`extra`), the data-parallel communication report (`comm`) and the fp32 CPU oracle step (`cpu_baseline`).
 """
 import argparse
 import json
@@ -162,13 +167,17 @@ def main():
                     help="clips per GPU.  Throughput grows with the per-GPU batch (profiles/r02_f_batch_sweep.txt: 16 / 64 / 128 / 256 "
                          "clips -> 0.15 / 0.20 / 0.21 / 0.22 of the MFMA roof) and 288 GB of HBM holds far more than the reference's "
                          "16 clips (slurm_dev_def.bash:52), so the default is 256 (~40 GB); BASELINE.md lists 16 and 64 as well")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-by-batch", action="store_true", help="skip the 64- and 16-clip legs reported as `by_batch`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: `by_batch`, the per-kernel probes, "
+                         "`extra`, `comm` (data-parallel runs) and `cpu_baseline`; the --no-* switches below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-by-batch", action="store_true", help="with --full: skip the 64- and 16-clip legs reported as `by_batch`")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the `extra` block: BASELINE configs 4 and 5 on this GPU (I-JEPA ViT-L/16 at 16 and 256 samples, SimCLR "
-                         "ViT-B at 512 images), a few seconds each, after the headline loop")
+                    help="with --full: skip the `extra` block: BASELINE configs 4 and 5 on this GPU (I-JEPA ViT-L/16 at 16 and 256 "
+                         "samples, SimCLR ViT-B at 512 images), a few seconds each, after the headline loop")
     ap.add_argument("--no-probe", action="store_true",
-                    help="skip the per-kernel probes behind `roofline.kernel` / `roofline.kernels` (profiling runs: only the timed steps' kernels)")
+                    help="with --full: skip the per-kernel probes behind `roofline.kernel` / `roofline.kernels` (profiling runs: only the "
+                         "timed steps' kernels)")
     ap.add_argument("--torch-sgd", action="store_true", help="use torch.optim.SGD instead of the fused HIP update")
     ap.add_argument("--per-step", action="store_true", help="diagnostic: per-step HIP-event and host-enqueue times to stderr")
     ap.add_argument("--bucket-mb", type=float, default=25.0, help="gradient all-reduce bucket size of the data-parallel wrapper")
@@ -308,7 +317,7 @@ def main():
     # The same loop at the reference's per-GPU batch (16 clips, slurm_dev_def.bash:52) and at round 1's default (64), in the same
     # run and the same line, so that rounds stay comparable whatever the headline batch is: 3 untimed + 10 timed steps each.
     by_batch = {}
-    if world == 1 and not args.stream_input and not args.no_by_batch:
+    if args.full and world == 1 and not args.stream_input and not args.no_by_batch:
         full = clips
         for b in (64, 16):
             if b >= B:
@@ -332,7 +341,7 @@ def main():
                                 "roofline": {"bound": "mfma", "achieved": round(tf, 2), "frac": round(tf / PEAK_BF16_TFLOPS, 4), "traffic": tr}}
         clips, B = full, args.batch
     comm = None
-    if use_ddp:
+    if args.full and use_ddp:
         # two more steps OUTSIDE the timed region with per-bucket events on the communication stream: bytes, time, ring bus bandwidth
         xmodel.profile_buckets = True
         for _ in range(2):
@@ -359,7 +368,7 @@ def main():
     # metrics, units and FLOP counts; never part of `value`
     # (after the data-parallel report above: this block frees the headline model)
     extra = None
-    if world == 1 and not args.stream_input and not args.no_extra:
+    if args.full and world == 1 and not args.stream_input and not args.no_extra:
         from tools import bench_legs
         del clips
         model = xmodel = opt = None
@@ -400,7 +409,7 @@ def main():
         if world == 1:
             # the dominant kernel of the step = the kernel instantiation with the largest time share, from per-product launches
             # timed alone in this run and named as rocprofv3 names them (compare: profiles/r03_*_roofline_table_b256.txt row 1)
-            if not args.no_probe:
+            if args.full and not args.no_probe:
                 line["roofline"].update(kernel_roofline(bvc, B, dev))
             if by_batch:
                 line["by_batch"] = by_batch
@@ -412,7 +421,7 @@ def main():
             line["input_stream"] = stream_info
         if dumped is not None:
             line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if use_ddp:

@@ -31,7 +31,7 @@ for step in "$@"; do
     # forced data-parallel path on ONE GPU (world size 1 over RCCL: every fence, stream hop and collective launch of the N-GPU job,
     # no bytes on xGMI): overhead of the wrapper per bucket size, next to the plain run
     ddpsweep) run ddp_plain 200 python bench.py --no-cpu-baseline --steps 20
-              for mb in 5 25 50 100 400; do BVC_FORCE_DDP=1 run ddp_mb$mb 200 python bench.py --no-cpu-baseline --steps 20 --bucket-mb $mb; done
+              for mb in 5 25 50 100 400; do BVC_FORCE_DDP=1 run ddp_mb$mb 200 python bench.py --full --no-cpu-baseline --steps 20 --bucket-mb $mb; done
               python3 - <<'PY'
 import json, glob, re
 rows = []
@@ -53,7 +53,7 @@ PY
     model) run model 420 python -m pytest tests/test_gpu_videomae.py -m gpu -q -p no:cacheprovider ;;
     all)   run alltests 900 python -m pytest tests -m gpu -q -x -p no:cacheprovider ;;
     smoke) run smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 400 python bench.py ;;
+    bench) run bench 400 python bench.py --full ;;
     bench32) run bench32 400 python bench.py --batch 32 --no-cpu-baseline ;;
     diag32) run diag32 300 python bench.py --batch 32 --no-cpu-baseline --per-step
             OMP_NUM_THREADS=4 run diag32omp 300 python bench.py --batch 32 --no-cpu-baseline --per-step
@@ -62,7 +62,7 @@ PY
     sweepb) for b in 16 32 48 64 96 128; do run bench_b$b 300 python bench.py --batch $b --no-cpu-baseline --steps 20; done ;;
     bench64) run bench64 400 python bench.py --batch 64 --no-cpu-baseline --steps 15 ;;
     benchq) run benchq 300 python bench.py --no-cpu-baseline ;;
-    benchddp) BVC_FORCE_DDP=1 run benchddp 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline ;;
+    benchddp) BVC_FORCE_DDP=1 run benchddp 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 3 --full --no-cpu-baseline ;;
     micro) run micro 400 python tools/ab/microbench.py ;;
     racescreen) run racescreen 500 python tools/persist_race_screen.py ;;
     g8race) run g8race 600 python tools/g8_race_screen.py ;;
@@ -105,7 +105,7 @@ PY
            cd $R; find $OUT/profd -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats_default.csv
            find $OUT/profd -name "*kernel_trace.csv" -delete ;;
     profnobb) rm -rf $OUT/profn; cd /tmp      # the default command without the 64- / 16-clip legs: every launch of a kernel is at the headline batch
-           run profnobb 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profn -- python3 $R/bench.py --no-by-batch --no-extra
+           run profnobb 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profn -- python3 $R/bench.py --full --no-by-batch --no-extra
            cd $R; find $OUT/profn -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats_no_by_batch.csv
            find $OUT/profn -name "*kernel_trace.csv" -delete ;;
     prof_jepa) rm -rf $OUT/prof_jepa; cd /tmp

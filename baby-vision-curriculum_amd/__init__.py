@@ -12,7 +12,7 @@ memory, streams, the optimiser object and torch.distributed only.
 from . import _lib, _ops  # noqa: F401
 from ._lib import use_deterministic_algorithms, are_deterministic_algorithms_enabled  # noqa: F401
 from .videomae import (VideoMAEConfig, VideoMAEForPreTraining, VideoMAEForPreTrainingOutput, VideoMAEForVideoClassification,  # noqa: F401
-                       get_config, get_model)
+                       get_config, get_model, VIDEOMAE_ARCHS, videomae_config)
 from .mask import TubeMaskingGenerator, RandomMaskingGenerator  # noqa: F401
 from .ddp import DistributedDataParallel  # noqa: F401
 from .ddputils import AllReduce  # noqa: F401

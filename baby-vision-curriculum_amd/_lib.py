@@ -147,6 +147,10 @@ SYMBOLS = {
     "bvc_op_attention_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_op_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_op_attention_bwd_part": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "bvc_op_attention_width": (c_int, [c_int]),
+    "bvc_op_attention_fwd_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p]),
+    "bvc_op_attention_bwd_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                            ctypes.c_float, c_void_p]),
     "bvc_op_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int, c_int, c_float, c_void_p]),
     "bvc_op_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -249,7 +253,7 @@ def check(rc, what=""):
 
 
 def set_option(name, value):
-    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1, "deterministic" 0 / 1 (what
+    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1, "head_pad" 0 / 1, "deterministic" 0 / 1 (what
     bvc.use_deterministic_algorithms and torch.use_deterministic_algorithms switch; the library's raw flag - the next library call
     after either of those changes resets it to their OR).  Returns the previous value."""
     old = lib().bvc_get_option(name.encode())

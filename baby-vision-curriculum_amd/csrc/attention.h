@@ -1,7 +1,7 @@
-// Attention launchers (internal to libbvc_hip.so); head_dim 32, 64, 96 or 128 (D = head_dim * H).
+// Attention launchers (internal to libbvc_hip.so); head_dim 32, 64, 80, 88, 96 or 128 (D = head_dim * H; 80 / 88 in place).
 // softmax_scale = 0 means head_dim^-1/2; a caller that zero-pads a narrower head (JEPA ViT-L predictor: 24 -> 32) passes
-// the scale of the TRUE head width - the padded lanes contribute nothing to q.k, the context or any gradient (ViT-H / ViT-g:
-// 80 / 88 -> 96).
+// the scale of the TRUE head width - the padded lanes contribute nothing to q.k, the context or any gradient (ViT-H / ViT-g
+// under bvc_set_option("head_pad", 1): 80 / 88 -> 96).
 #pragma once
 #include "common.h"
 

@@ -1,6 +1,8 @@
-// Multi-head self-attention forward / backward for head_dim 32, 64, 96 and 128 on gfx950 (no mask, no dropout),
-// flash-style: the N x N score matrix never leaves registers.  96 and 128 (ViT-H / ViT-g encoders padded from 80 / 88, the ViT-Ti
-// predictor) use a panel image of 64 + 32 / 64 + 64 columns (pan_w) and the two-kernel backward at every N.
+// Multi-head self-attention forward / backward for head_dim 32, 64, 80, 88, 96 and 128 on gfx950 (no mask, no dropout),
+// flash-style: the N x N score matrix never leaves registers.  96 and 128 (the ViT-Ti predictor) use a panel image of 64 + 32 /
+// 64 + 64 columns (pan_w) and the two-kernel backward at every N.  80 and 88 (ViT-H / ViT-g, VideoMAE-H) run IN PLACE on the
+// 96-wide image (img_hd): heads sit at column h * head_dim of the unpadded qkv / ctx, the chunks of the 32-wide panel past the head
+// are zero in LDS and in the register fragments, and only the head's own columns are stored.
 //
 // Reference semantics: softmax(Q K^T / sqrt(d)) V per (batch, head)   (HF:181-206 / SDPA, HF:239-252).
 // Layout in HBM: qkv bf16 [B*N][3*D] with q | k | v column blocks (each head a 64-wide slice),
@@ -62,10 +64,18 @@ __device__ __forceinline__ int swz_dual(int r) {
 // offsets as for HD <= 64, and the swizzles only see r & 15 - the conflict-free 64- and 32-wide images are reused, not redesigned.
 template <int HD>
 constexpr int pan_w(int p) { return HD - 64 * p >= 64 ? 64 : HD - 64 * p; }
+// the LDS image a head width runs on: 80 / 88 on the 96-wide one (their 32-wide panel holds 2 / 3 valid 16-B chunks of 4); the
+// result is bitwise that of zero-padding the head to 96 in HBM: the extra columns are exact zeros in every product and every sum
+constexpr int img_hd(int hd) { return hd == 80 || hd == 88 ? 96 : hd; }
+// a per-lane LDS-DMA offset past the end of any buffer descriptor: the piece loads zeros.  The launchers refuse an 80 / 88 qkv of
+// kDmaZero bytes or more, so the offset is out of range of every descriptor these kernels build
+constexpr uint32_t kDmaZero = 0xfffffff0u;
 __device__ __forceinline__ int swz_pw(int pw, int r) { return pw == 64 ? swz_dual<64>(r) : swz_dual<32>(r); }
 
-// one PW-wide panel of a 64-row tile: 1 KiB pieces of RPP rows (8 or 16: a piece never straddles a 16-row group of GB bytes)
-template <int PW, int NW>
+// one PW-wide panel of a 64-row tile: 1 KiB pieces of RPP rows (8 or 16: a piece never straddles a 16-row group of GB bytes);
+// source chunks c >= VC (past a head narrower than the image) are loaded out of range of the descriptor, i.e. as zeros - every
+// slot of the image is rewritten by every stage, so no stale data can sit in them
+template <int PW, int NW, int VC = PW / 8>
 __device__ __forceinline__ void stage_panel(__amdgpu_buffer_rsrc_t rs, int row0, int ld, int col0, char* lds, int GB, int wave, int lane) {
     constexpr int CPR = PW / 8;
     constexpr int RPP = 64 / CPR;
@@ -75,20 +85,23 @@ __device__ __forceinline__ void stage_panel(__amdgpu_buffer_rsrc_t rs, int row0,
         if (NW > PW / 8 && j >= PW / 8) break;
         const int r = RPP * j + lane / CPR;
         const int c = (lane % CPR) ^ swz_dual<PW>(r);
-        const uint32_t off = (uint32_t)(((size_t)(row0 + r) * ld + col0 + c * 8) * 2);
+        uint32_t off = (uint32_t)(((size_t)(row0 + r) * ld + col0 + c * 8) * 2);
+        if constexpr (VC < CPR) off = c < VC ? off : kDmaZero;
         const uint32_t dst = (uint32_t)((RPP * j >> 4) * GB + ((RPP * j) & 15) * PW * 2);
         glds16(rs, off, __builtin_amdgcn_readfirstlane((uint32_t)(size_t)((AS3 char*)lds) + dst));
     }
 }
 
 // stage rows [row0, row0+64) x HD bf16 starting at element column `col0` of a [rows][ld] bf16 array
-// into a 64 x HD LDS image (8 KiB / 4 KiB); pieces of 1 KiB, two / one per wave
-template <int HD, int NW = 4>
+// into a 64 x HD LDS image (8 KiB / 4 KiB); pieces of 1 KiB, two / one per wave.  HV < HD: only the first HV columns are the
+// head's, the rest of the image is zero (80 / 88 on the 96 image)
+template <int HD, int NW = 4, int HV = HD>
 __device__ __forceinline__ void stage64(__amdgpu_buffer_rsrc_t rs, int row0, int ld, int col0, char* lds,
                                         int wave, int lane) {
+    static_assert(HV == HD || (HD == 96 && HV > 64 && HV % 8 == 0), "stage64: a narrower head only on the 96 image");
     if constexpr (HD > 64) {    // panel image (see pan_w)
         stage_panel<64, NW>(rs, row0, ld, col0, lds, 16 * HD * 2, wave, lane);
-        stage_panel<pan_w<HD>(1), NW>(rs, row0, ld, col0 + 64, lds + 2048, 16 * HD * 2, wave, lane);
+        stage_panel<pan_w<HD>(1), NW, (HV - 64) / 8>(rs, row0, ld, col0 + 64, lds + 2048, 16 * HD * 2, wave, lane);
         return;
     }
     constexpr int CPR = HD / 8;                 // 16-B chunks per row
@@ -185,6 +198,15 @@ __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * 
 
 // 8 consecutive bf16 of one row straight from HBM (row clamped by the caller)
 __device__ __forceinline__ bf16x8 load8(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
+// the same at head column `col` of a head of HV columns on an image of HI: zeros past the head (nothing is read there)
+template <int HV, int HI>
+__device__ __forceinline__ bf16x8 load8_head(const bf16_t* p, int col) {
+    if constexpr (HV == HI) return load8(p);
+    else {
+        const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+        return col < HV ? load8(p) : z;
+    }
+}
 
 // hipcc keeps its own count of the vector-memory loads it knows; the LDS-DMA of these kernels is inline asm it does not see.
 // Passing a plain load's result through an empty asm makes hipcc wait for that load HERE, before the first LDS-DMA is
@@ -329,7 +351,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const bf16_t* __re
                                                           float* __restrict__ lse, int N, int H, int D,
                                                           uint32_t qkv_bytes, float scale_log2, int remap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages x (K image + V image)
-    constexpr int IMG = 64 * HD * 2, STG = 2 * IMG, SUB = 32 * HD * 2;
+    constexpr int HI = img_hd(HD);   // the image width (96 for 80 / 88)
+    constexpr int IMG = 64 * HI * 2, STG = 2 * IMG, SUB = 32 * HI * 2;
     const AS3 char* lds = (const AS3 char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -341,51 +364,51 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const bf16_t* __re
     const int qi = tile_ * (32 * NW) + ts.own * 32 + (lane & 31);   // this lane's query
     const int h = lane >> 5;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(qkv, qkv_bytes);
-    const FragAddr<HD> fa = make_frag_addr<HD>(lane);
+    const FragAddr<HI> fa = make_frag_addr<HI>(lane);
     const int gm = ts.gs - 1;
     auto mine = [&](int sub) { return (sub & gm) == ts.part; };      // does this wave take 32-key sub-tile `sub`?
 
-    bf16x8 qf[HD / 16];   // Q^T fragments (B operand of S^T = K Q^T): Q[qi][16 step + 8 h + 0..7]
+    bf16x8 qf[HI / 16];   // Q^T fragments (B operand of S^T = K Q^T): Q[qi][16 step + 8 h + 0..7]
     {
         const bf16_t* qrow = qkv + (size_t)(b * N + min(qi, N - 1)) * ld + head * HD + 8 * h;
 #pragma unroll
-        for (int st = 0; st < HD / 16; ++st) qf[st] = load8(qrow + 16 * st);
+        for (int st = 0; st < HI / 16; ++st) qf[st] = load8_head<HD, HI>(qrow + 16 * st, 16 * st + 8 * h);
     }
-    FwdState<HD> st;
+    FwdState<HI> st;
 #pragma unroll
-    for (int t = 0; t < HD / 32; ++t) st.o[t] = zero16();
+    for (int t = 0; t < HI / 32; ++t) st.o[t] = zero16();
     st.m_run = -INFINITY; st.l_run = 0.f;
 
     const int nkt = (N + 63) >> 6;
     const int krow0 = b * N;
     auto issue = [&](int kt, int stage) {
-        stage64<HD, NW>(rs, krow0 + kt * 64, ld, D + head * HD, smem + stage * STG, wave, lane);
-        stage64<HD, NW>(rs, krow0 + kt * 64, ld, 2 * D + head * HD, smem + stage * STG + IMG, wave, lane);
+        stage64<HI, NW, HD>(rs, krow0 + kt * 64, ld, D + head * HD, smem + stage * STG, wave, lane);
+        stage64<HI, NW, HD>(rs, krow0 + kt * 64, ld, 2 * D + head * HD, smem + stage * STG + IMG, wave, lane);
     };
 #pragma unroll
-    for (int stq = 0; stq < HD / 16; ++stq) settle(qf[stq]);
+    for (int stq = 0; stq < HI / 16; ++stq) settle(qf[stq]);
     issue(0, 0);
     for (int kt = 0; kt < nkt; kt += 2) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (kt + 1 < nkt) issue(kt + 1, 1);
-        if (mine(2 * kt)) fwd_subtile<HD, 0, IMG>(lds, fa, qf, st, kt * 64, N, h, scale_log2);
-        if (kt * 64 + 32 < N && mine(2 * kt + 1)) fwd_subtile<HD, SUB, IMG + SUB>(lds, fa, qf, st, kt * 64 + 32, N, h, scale_log2);
+        if (mine(2 * kt)) fwd_subtile<HI, 0, IMG>(lds, fa, qf, st, kt * 64, N, h, scale_log2);
+        if (kt * 64 + 32 < N && mine(2 * kt + 1)) fwd_subtile<HI, SUB, IMG + SUB>(lds, fa, qf, st, kt * 64 + 32, N, h, scale_log2);
         if (kt + 1 >= nkt) break;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (kt + 2 < nkt) issue(kt + 2, 0);
-        if (mine(2 * kt + 2)) fwd_subtile<HD, STG, STG + IMG>(lds, fa, qf, st, kt * 64 + 64, N, h, scale_log2);
-        if (kt * 64 + 96 < N && mine(2 * kt + 3)) fwd_subtile<HD, STG + SUB, STG + IMG + SUB>(lds, fa, qf, st, kt * 64 + 96, N, h, scale_log2);
+        if (mine(2 * kt + 2)) fwd_subtile<HI, STG, STG + IMG>(lds, fa, qf, st, kt * 64 + 64, N, h, scale_log2);
+        if (kt * 64 + 96 < N && mine(2 * kt + 3)) fwd_subtile<HI, STG + SUB, STG + IMG + SUB>(lds, fa, qf, st, kt * 64 + 96, N, h, scale_log2);
     }
     if (ts.gs > 1) {      // workgroup-uniform: merge the parts of a query tile (flash-decoding style: common maximum, rescaled sums)
         AS3 float* cl = (AS3 float*)smem;
-        constexpr int NO = HD / 32 * 16, SLOT = (NO + 2) * 64;
+        constexpr int NO = HI / 32 * 16, SLOT = (NO + 2) * 64;
         __syncthreads();
         if (ts.part > 0) {
             AS3 float* w = cl + ((ts.part - 1) * ts.valid + ts.own) * SLOT + lane;
 #pragma unroll
-            for (int t = 0; t < HD / 32; ++t)
+            for (int t = 0; t < HI / 32; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) w[(t * 16 + r) * 64] = st.o[t][r];
             w[NO * 64] = st.m_run;
@@ -402,7 +425,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const bf16_t* __re
                 st.m_run = m_new;
                 st.l_run = st.l_run * a + l_p * c;
 #pragma unroll
-                for (int t = 0; t < HD / 32; ++t)
+                for (int t = 0; t < HI / 32; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) st.o[t][r] = st.o[t][r] * a + w[(t * 16 + r) * 64] * c;
             }
@@ -413,10 +436,11 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const bf16_t* __re
     if (qi < N && ts.part == 0) {
         bf16_t* orow = ctx + (size_t)(b * N + qi) * D + head * HD;
 #pragma unroll
-        for (int t = 0; t < HD / 32; ++t)
+        for (int t = 0; t < HI / 32; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d = 32 * t + 8 * g + 4 * h;
+                if (HD != HI && d >= HD) continue;     // past a narrower head
                 uint2 a = {pack2bf(st.o[t][4 * g] * inv, st.o[t][4 * g + 1] * inv), pack2bf(st.o[t][4 * g + 2] * inv, st.o[t][4 * g + 3] * inv)};
                 *reinterpret_cast<uint2*>(orow + d) = a;
             }
@@ -460,7 +484,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
                                                              float* __restrict__ delta, bf16_t* __restrict__ dqkv, int N, int H, int D,
                                                              uint32_t qkv_bytes, float scale, float scale_log2, int remap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int IMG = 64 * HD * 2, STG = 2 * IMG, SUB = 32 * HD * 2;
+    constexpr int HI = img_hd(HD);
+    constexpr int IMG = 64 * HI * 2, STG = 2 * IMG, SUB = 32 * HI * 2;
     const AS3 char* lds = (const AS3 char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -473,23 +498,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
     const int qc = min(qi, N - 1);
     const int h = lane >> 5;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(qkv, qkv_bytes);
-    const FragAddr<HD> fa = make_frag_addr<HD>(lane);
+    const FragAddr<HI> fa = make_frag_addr<HI>(lane);
     const int gm = ts.gs - 1;
     auto mine = [&](int sub) { return (sub & gm) == ts.part; };
 
-    bf16x8 qf[HD / 16], dof[HD / 16];
+    bf16x8 qf[HI / 16], dof[HI / 16];
     float del_q = 0.f;
     {
         const bf16_t* qrow = qkv + (size_t)(b * N + qc) * ld + head * HD + 8 * h;
         const bf16_t* drow = dctx + (size_t)(b * N + qc) * D + head * HD + 8 * h;
         const bf16_t* orow_in = ctx + (size_t)(b * N + qc) * D + head * HD + 8 * h;
 #pragma unroll
-        for (int st = 0; st < HD / 16; ++st) {
-            qf[st] = load8(qrow + 16 * st);
-            dof[st] = load8(drow + 16 * st);
+        for (int st = 0; st < HI / 16; ++st) {
+            qf[st] = load8_head<HD, HI>(qrow + 16 * st, 16 * st + 8 * h);
+            dof[st] = load8_head<HD, HI>(drow + 16 * st, 16 * st + 8 * h);
             // delta = rowsum(dO * O) of this query (the softmax-gradient correction): the two half-waves hold disjoint halves
             // of the row, so it costs one more 16-B load per step here instead of a pass of its own over dO and O
-            const bf16x8 of = load8(orow_in + 16 * st);
+            const bf16x8 of = load8_head<HD, HI>(orow_in + 16 * st, 16 * st + 8 * h);     // (past the head: 0 * 0 terms)
 #pragma unroll
             for (int j = 0; j < 8; ++j) del_q += bf2f((bf16_t)dof[st][j]) * bf2f((bf16_t)of[j]);
         }
@@ -498,44 +523,45 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
     if (h == 0 && qi < N && ts.part == 0) delta[(size_t)bh * N + qi] = -del_q;     // NEGATED: the dK/dV kernel, launched after this one, starts its dP chain from it
     float nlse = -lse[(size_t)bh * N + qc];
 #pragma unroll
-    for (int stq = 0; stq < HD / 16; ++stq) { settle(qf[stq]); settle(dof[stq]); }
+    for (int stq = 0; stq < HI / 16; ++stq) { settle(qf[stq]); settle(dof[stq]); }
     settle(nlse); settle(del_q);
     f32x16 ndel;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ndel[r] = -del_q;
-    f32x16 dq[HD / 32];
+    f32x16 dq[HI / 32];
 #pragma unroll
-    for (int t = 0; t < HD / 32; ++t) dq[t] = zero16();
+    for (int t = 0; t < HI / 32; ++t) dq[t] = zero16();
 
     const int nkt = (N + 63) >> 6;
     const int krow0 = b * N;
     auto issue = [&](int kt, int stage) {
-        stage64<HD>(rs, krow0 + kt * 64, ld, D + head * HD, smem + stage * STG, wave, lane);
-        stage64<HD>(rs, krow0 + kt * 64, ld, 2 * D + head * HD, smem + stage * STG + IMG, wave, lane);
+        stage64<HI, 4, HD>(rs, krow0 + kt * 64, ld, D + head * HD, smem + stage * STG, wave, lane);
+        stage64<HI, 4, HD>(rs, krow0 + kt * 64, ld, 2 * D + head * HD, smem + stage * STG + IMG, wave, lane);
     };
     issue(0, 0);
     for (int kt = 0; kt < nkt; kt += 2) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (kt + 1 < nkt) issue(kt + 1, 1);
-        if (mine(2 * kt)) dq_subtile<HD, 0, IMG>(lds, fa, qf, dof, dq, kt * 64, N, h, scale_log2, nlse, ndel);
-        if (kt * 64 + 32 < N && mine(2 * kt + 1)) dq_subtile<HD, SUB, IMG + SUB>(lds, fa, qf, dof, dq, kt * 64 + 32, N, h, scale_log2, nlse, ndel);
+        if (mine(2 * kt)) dq_subtile<HI, 0, IMG>(lds, fa, qf, dof, dq, kt * 64, N, h, scale_log2, nlse, ndel);
+        if (kt * 64 + 32 < N && mine(2 * kt + 1)) dq_subtile<HI, SUB, IMG + SUB>(lds, fa, qf, dof, dq, kt * 64 + 32, N, h, scale_log2, nlse, ndel);
         if (kt + 1 >= nkt) break;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (kt + 2 < nkt) issue(kt + 2, 0);
-        if (mine(2 * kt + 2)) dq_subtile<HD, STG, STG + IMG>(lds, fa, qf, dof, dq, kt * 64 + 64, N, h, scale_log2, nlse, ndel);
+        if (mine(2 * kt + 2)) dq_subtile<HI, STG, STG + IMG>(lds, fa, qf, dof, dq, kt * 64 + 64, N, h, scale_log2, nlse, ndel);
         if (kt * 64 + 96 < N && mine(2 * kt + 3))
-            dq_subtile<HD, STG + SUB, STG + IMG + SUB>(lds, fa, qf, dof, dq, kt * 64 + 96, N, h, scale_log2, nlse, ndel);
+            dq_subtile<HI, STG + SUB, STG + IMG + SUB>(lds, fa, qf, dof, dq, kt * 64 + 96, N, h, scale_log2, nlse, ndel);
     }
-    if (ts.gs > 1) tail_reduce<HD / 32>(smem, ts, lane, dq);
+    if (ts.gs > 1) tail_reduce<HI / 32>(smem, ts, lane, dq);
     if (qi < N && ts.part == 0) {
         bf16_t* orow = dqkv + (size_t)(b * N + qi) * ld + head * HD;
 #pragma unroll
-        for (int t = 0; t < HD / 32; ++t)
+        for (int t = 0; t < HI / 32; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d = 32 * t + 8 * g + 4 * h;
+                if (HD != HI && d >= HD) continue;
                 uint2 a = {pack2bf(dq[t][4 * g] * scale, dq[t][4 * g + 1] * scale), pack2bf(dq[t][4 * g + 2] * scale, dq[t][4 * g + 3] * scale)};
                 *reinterpret_cast<uint2*>(orow + d) = a;
             }
@@ -645,13 +671,14 @@ __device__ __forceinline__ void dkdv_subtile(const AS3 char* lds, const FragAddr
 // HD = 128 (ViT-Ti predictor only): K, V fragments and the dK^T / dV^T accumulators do not fit 256 registers (it spilled 128 B per
 // lane), so that instantiation runs one workgroup per CU with the whole register file
 template <int HD>
-__global__ __launch_bounds__(256, HD > 96 ? 1 : 2) void attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+__global__ __launch_bounds__(256, img_hd(HD) > 96 ? 1 : 2) void attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                bf16_t* __restrict__ dqkv, int N, int H, int D,
                                                                uint32_t qkv_bytes, uint32_t dctx_bytes, uint32_t stat_bytes,
                                                                float scale, float scale_log2, int remap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int IMG = 64 * HD * 2, SUB = 32 * HD * 2, STG = 2 * IMG + 512;
+    constexpr int HI = img_hd(HD);
+    constexpr int IMG = 64 * HI * 2, SUB = 32 * HI * 2, STG = 2 * IMG + 512;
     const AS3 char* lds = (const AS3 char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -669,26 +696,29 @@ __global__ __launch_bounds__(256, HD > 96 ? 1 : 2) void attn_bwd_dkdv_kernel(con
     const __amdgpu_buffer_rsrc_t rd = make_rsrc(dctx, dctx_bytes);
     const __amdgpu_buffer_rsrc_t rl = make_rsrc(lse, stat_bytes);
     const __amdgpu_buffer_rsrc_t re = make_rsrc(delta, stat_bytes);
-    const FragAddr<HD> fa = make_frag_addr<HD>(lane);
+    const FragAddr<HI> fa = make_frag_addr<HI>(lane);
 
-    bf16x8 kf[HD / 16], vf[HD / 16];   // B operands of S = Q K^T and dP = dO V^T
+    bf16x8 kf[HI / 16], vf[HI / 16];   // B operands of S = Q K^T and dP = dO V^T
     {
         const bf16_t* krow = qkv + (size_t)(b * N + kc) * ld + D + head * HD + 8 * h;
 #pragma unroll
-        for (int st = 0; st < HD / 16; ++st) { kf[st] = load8(krow + 16 * st); vf[st] = load8(krow + D + 16 * st); }
+        for (int st = 0; st < HI / 16; ++st) {
+            kf[st] = load8_head<HD, HI>(krow + 16 * st, 16 * st + 8 * h);
+            vf[st] = load8_head<HD, HI>(krow + D + 16 * st, 16 * st + 8 * h);
+        }
     }
 #pragma unroll
-    for (int stq = 0; stq < HD / 16; ++stq) { settle(kf[stq]); settle(vf[stq]); }
-    f32x16 dk[HD / 32], dv[HD / 32];
+    for (int stq = 0; stq < HI / 16; ++stq) { settle(kf[stq]); settle(vf[stq]); }
+    f32x16 dk[HI / 32], dv[HI / 32];
 #pragma unroll
-    for (int t = 0; t < HD / 32; ++t) { dk[t] = zero16(); dv[t] = zero16(); }
+    for (int t = 0; t < HI / 32; ++t) { dk[t] = zero16(); dv[t] = zero16(); }
 
     const int nqt = (N + 63) >> 6;
     const int qrow0 = b * N;
     auto issue = [&](int qt, int stage) {
         char* dst = smem + stage * STG;
-        stage64<HD>(rq, qrow0 + qt * 64, ld, head * HD, dst, wave, lane);
-        stage64<HD>(rd, qrow0 + qt * 64, D, head * HD, dst + IMG, wave, lane);
+        stage64<HI, 4, HD>(rq, qrow0 + qt * 64, ld, head * HD, dst, wave, lane);
+        stage64<HI, 4, HD>(rd, qrow0 + qt * 64, D, head * HD, dst + IMG, wave, lane);
         if (wave == 0)
             glds4(rl, (uint32_t)(((size_t)bh * N + qt * 64 + lane) * 4), (uint32_t)(size_t)((AS3 char*)dst) + 2 * IMG);
         if (wave == 1)
@@ -699,27 +729,28 @@ __global__ __launch_bounds__(256, HD > 96 ? 1 : 2) void attn_bwd_dkdv_kernel(con
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (qt + 1 < nqt) issue(qt + 1, 1);
-        if (mine(2 * qt)) dkdv_subtile<HD, 0, 2 * IMG>(lds, fa, kf, vf, dk, dv, qt * 64, N, h, scale_log2);
-        if (qt * 64 + 32 < N && mine(2 * qt + 1)) dkdv_subtile<HD, SUB, 2 * IMG + 128>(lds, fa, kf, vf, dk, dv, qt * 64 + 32, N, h, scale_log2);
+        if (mine(2 * qt)) dkdv_subtile<HI, 0, 2 * IMG>(lds, fa, kf, vf, dk, dv, qt * 64, N, h, scale_log2);
+        if (qt * 64 + 32 < N && mine(2 * qt + 1)) dkdv_subtile<HI, SUB, 2 * IMG + 128>(lds, fa, kf, vf, dk, dv, qt * 64 + 32, N, h, scale_log2);
         if (qt + 1 >= nqt) break;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (qt + 2 < nqt) issue(qt + 2, 0);
-        if (mine(2 * qt + 2)) dkdv_subtile<HD, STG, STG + 2 * IMG>(lds, fa, kf, vf, dk, dv, qt * 64 + 64, N, h, scale_log2);
-        if (qt * 64 + 96 < N && mine(2 * qt + 3)) dkdv_subtile<HD, STG + SUB, STG + 2 * IMG + 128>(lds, fa, kf, vf, dk, dv, qt * 64 + 96, N, h, scale_log2);
+        if (mine(2 * qt + 2)) dkdv_subtile<HI, STG, STG + 2 * IMG>(lds, fa, kf, vf, dk, dv, qt * 64 + 64, N, h, scale_log2);
+        if (qt * 64 + 96 < N && mine(2 * qt + 3)) dkdv_subtile<HI, STG + SUB, STG + 2 * IMG + 128>(lds, fa, kf, vf, dk, dv, qt * 64 + 96, N, h, scale_log2);
     }
     if (ts.gs > 1) {      // (one accumulator set at a time: three partial sets of 8 KiB fit the 33 KiB ring, six do not)
-        tail_reduce<HD / 32>(smem, ts, lane, dk);
-        tail_reduce<HD / 32>(smem, ts, lane, dv);
+        tail_reduce<HI / 32>(smem, ts, lane, dk);
+        tail_reduce<HI / 32>(smem, ts, lane, dv);
     }
     if (ki < N && ts.part == 0) {
         bf16_t* krow = dqkv + (size_t)(b * N + ki) * ld + D + head * HD;
         bf16_t* vrow = krow + D;
 #pragma unroll
-        for (int t = 0; t < HD / 32; ++t)
+        for (int t = 0; t < HI / 32; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d = 32 * t + 8 * g + 4 * h;
+                if (HD != HI && d >= HD) continue;
                 uint2 a = {pack2bf(dk[t][4 * g] * scale, dk[t][4 * g + 1] * scale), pack2bf(dk[t][4 * g + 2] * scale, dk[t][4 * g + 3] * scale)};
                 *reinterpret_cast<uint2*>(krow + d) = a;
                 uint2 e = {pack2bf(dv[t][4 * g], dv[t][4 * g + 1]), pack2bf(dv[t][4 * g + 2], dv[t][4 * g + 3])};
@@ -976,20 +1007,21 @@ static bool head_kernel_enabled() {
 
 template <int HD>
 static int fwd_hd(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, int H, hipStream_t stream, float sm_scale) {
+    constexpr int HI = img_hd(HD);
     const int D = H * HD;
     const size_t bytes = (size_t)B * N * 3 * D * 2;
     const float scale_log2 = (sm_scale > 0.f ? sm_scale : 1.0f / sqrtf((float)HD)) * 1.4426950408889634f;
 #ifdef BVC_EXPERIMENTS
     if (getenv("BVC_ATTN_NW8") != nullptr) {      // 256-query blocks (eight waves): half the K / V staging per query - same-process A/B only
         const dim3 grid8((unsigned)(((N + 255) / 256) * B * H));
-        hipLaunchKernelGGL((attn_fwd_kernel<HD, 8>), grid8, dim3(512), 4 * 64 * HD * 2, stream, qkv, ctx, lse, N, H, D, (uint32_t)bytes, scale_log2,
+        hipLaunchKernelGGL((attn_fwd_kernel<HD, 8>), grid8, dim3(512), 4 * 64 * HI * 2, stream, qkv, ctx, lse, N, H, D, (uint32_t)bytes, scale_log2,
                            xcd_remap());
         BVC_CHECK_HIP(hipGetLastError());
         return BVC_OK;
     }
 #endif
     const dim3 grid((unsigned)(((N + 127) / 128) * B * H));
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, 4>), grid, dim3(256), 4 * 64 * HD * 2, stream, qkv, ctx, lse, N, H, D, (uint32_t)bytes, scale_log2,
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, 4>), grid, dim3(256), 4 * 64 * HI * 2, stream, qkv, ctx, lse, N, H, D, (uint32_t)bytes, scale_log2,
                        xcd_remap());
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
@@ -998,6 +1030,7 @@ static int fwd_hd(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, int 
 template <int HD>
 static int bwd_hd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, const float* lse, float* delta, bf16_t* dqkv, int B,
                   int N, int H, hipStream_t stream, float sm_scale, int parts) {
+    constexpr int HI = img_hd(HD);
     const int D = H * HD;
     const size_t bytes = (size_t)B * N * 3 * D * 2;
     const float scale = sm_scale > 0.f ? sm_scale : 1.0f / sqrtf((float)HD), scale_log2 = scale * 1.4426950408889634f;
@@ -1038,18 +1071,18 @@ static int bwd_hd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, cons
     // dQ first: it also produces delta = rowsum(dO * O), which the dK/dV kernel consumes
     if (parts & 1) {
 #ifdef BVC_EXPERIMENTS
-    if (getenv("BVC_ATTN_DQ_W") != nullptr) {      // the single-wave 96-query dQ kernel (see above): same-process A/B only
+    if (HI == HD && getenv("BVC_ATTN_DQ_W") != nullptr) {      // the single-wave 96-query dQ kernel (see above): same-process A/B only
         constexpr int NB = 3;
         const dim3 gridw((unsigned)(((N + 32 * NB - 1) / (32 * NB)) * B * H));
-        hipLaunchKernelGGL((attn_bwd_dq_w_kernel<HD, NB>), gridw, dim3(64), kRing * 2 * 32 * HD * 2, stream, qkv, dctx, ctx, lse, delta, dqkv, N, H, D,
+        hipLaunchKernelGGL((attn_bwd_dq_w_kernel<HI, NB>), gridw, dim3(64), kRing * 2 * 32 * HI * 2, stream, qkv, dctx, ctx, lse, delta, dqkv, N, H, D,
                            (uint32_t)bytes, scale, scale_log2, remap);
     } else
 #endif
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<HD>, grid, dim3(256), 4 * 64 * HD * 2, stream, qkv, dctx, ctx, lse, delta, dqkv, N, H, D,
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<HD>, grid, dim3(256), 4 * 64 * HI * 2, stream, qkv, dctx, ctx, lse, delta, dqkv, N, H, D,
                        (uint32_t)bytes, scale, scale_log2, remap);
     }
     if (parts & 2) {
-    constexpr int lds_dkdv = 2 * (2 * 64 * HD * 2 + 512);
+    constexpr int lds_dkdv = 2 * (2 * 64 * HI * 2 + 512);
     if constexpr (lds_dkdv > 65536) {      // HD = 128: 65 KiB, above the default dynamic LDS limit
         static bool attr_set = false;
         if (!attr_set) {
@@ -1065,14 +1098,18 @@ static int bwd_hd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, cons
     return BVC_OK;
 }
 
-static bool attn_hd_ok(int hd) { return hd == 32 || hd == 64 || hd == 96 || hd == 128; }
+static bool attn_hd_ok(int hd) { return hd == 32 || hd == 64 || hd == 80 || hd == 88 || hd == 96 || hd == 128; }
 
 int launch_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, int H, int head_dim, hipStream_t stream, float sm_scale) {
     BVC_REQUIRE(B > 0 && N > 0 && H > 0, "attn_fwd: empty shape");
-    BVC_REQUIRE(attn_hd_ok(head_dim), "attn_fwd: head_dim %d unsupported (32, 64, 96 or 128)", head_dim);
+    BVC_REQUIRE(attn_hd_ok(head_dim), "attn_fwd: head_dim %d unsupported (32, 64, 80, 88, 96 or 128)", head_dim);
     BVC_REQUIRE((size_t)B * N * 3 * H * head_dim * 2 < 0xffffffffull, "attn_fwd: qkv larger than 4 GiB");
+    BVC_REQUIRE(img_hd(head_dim) == head_dim || (size_t)B * N * 3 * H * head_dim * 2 < kDmaZero,
+                "attn_fwd: qkv of head_dim %d must stay below 4 GiB - 16 bytes", head_dim);
     switch (head_dim) {
         case 32: return fwd_hd<32>(qkv, ctx, lse, B, N, H, stream, sm_scale);
+        case 80: return fwd_hd<80>(qkv, ctx, lse, B, N, H, stream, sm_scale);
+        case 88: return fwd_hd<88>(qkv, ctx, lse, B, N, H, stream, sm_scale);
         case 96: return fwd_hd<96>(qkv, ctx, lse, B, N, H, stream, sm_scale);
         case 128: return fwd_hd<128>(qkv, ctx, lse, B, N, H, stream, sm_scale);
         default: return fwd_hd<64>(qkv, ctx, lse, B, N, H, stream, sm_scale);
@@ -1082,10 +1119,14 @@ int launch_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, in
 int launch_attn_bwd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, const float* lse, float* delta,
                     bf16_t* dqkv, int B, int N, int H, int head_dim, hipStream_t stream, float sm_scale, int parts) {
     BVC_REQUIRE(B > 0 && N > 0 && H > 0, "attn_bwd: empty shape");
-    BVC_REQUIRE(attn_hd_ok(head_dim), "attn_bwd: head_dim %d unsupported (32, 64, 96 or 128)", head_dim);
+    BVC_REQUIRE(attn_hd_ok(head_dim), "attn_bwd: head_dim %d unsupported (32, 64, 80, 88, 96 or 128)", head_dim);
     BVC_REQUIRE((size_t)B * N * 3 * H * head_dim * 2 < 0xffffffffull, "attn_bwd: qkv larger than 4 GiB");
+    BVC_REQUIRE(img_hd(head_dim) == head_dim || (size_t)B * N * 3 * H * head_dim * 2 < kDmaZero,
+                "attn_bwd: qkv of head_dim %d must stay below 4 GiB - 16 bytes", head_dim);
     switch (head_dim) {
         case 32: return bwd_hd<32>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
+        case 80: return bwd_hd<80>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
+        case 88: return bwd_hd<88>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
         case 96: return bwd_hd<96>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
         case 128: return bwd_hd<128>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
         default: return bwd_hd<64>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);

@@ -46,7 +46,9 @@ constexpr int kMaxGroup = 4;
 //   deterministic: 1 = every reduction whose order the default kernels leave to the scheduler (f32 atomics: split-K / accumulating
 //               GEMM outputs, fused bias gradients, LayerNorm parameter partials, column sums) runs in a fixed order instead: partials
 //               go to a workspace slab with plain stores, a separate pass adds them in index order (launch_gemm, rowops.hip)
-struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; int deterministic = 0; };
+//   head_pad:   1 = heads of 80 / 88 dims run zero-padded to 96 in HBM (padded weight copies, pad / unpad launches per layer call), as
+//               before the in-place attention instantiations; 0 (default) = in place.  Read when a stack is allocated (A/B only)
+struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; int deterministic = 0; int head_pad = 0; };
 Options& options();
 
 // Workspace of the deterministic mode: library-owned, grow-only, one buffer per (device, stream) - kernels on one stream use it in

@@ -31,7 +31,7 @@ int check_vit(const bvc_vit_config& c) {
     BVC_REQUIRE(c.patch_size % 8 == 0, "vit config: patch_size must be a multiple of 8");
     BVC_REQUIRE(c.num_heads > 0 && c.embed_dim % c.num_heads == 0, "vit config: embed_dim %% num_heads != 0");
     const int hd = c.embed_dim / c.num_heads;
-    BVC_REQUIRE(hd % 8 == 0 && hd <= 128, "vit config: head_dim %d unsupported (multiples of 8 up to 128; 80 / 88 run zero-padded to 96)", hd);
+    BVC_REQUIRE(hd % 8 == 0 && hd <= 128, "vit config: head_dim %d unsupported (multiples of 8 up to 128)", hd);
     BVC_REQUIRE(c.embed_dim % 64 == 0 && c.embed_dim <= 1536, "vit config: embed_dim must be a multiple of 64, at most 1536");
     BVC_REQUIRE(c.mlp_hidden % 64 == 0 && c.depth >= 1, "vit config: mlp_hidden must be a multiple of 64");
     BVC_REQUIRE((c.num_channels * c.tubelet_size * c.patch_size * c.patch_size) % 64 == 0, "vit config: patch dim must be a multiple of 64");

@@ -54,9 +54,8 @@ struct Stack {
     float eps;
     std::vector<LayerAct> act;
     float* x_out;     // f32 [M][D] output of the last layer
-    // attention width: heads of hd = D / H dims run at hdp dims (hdp == hd unless hd is not 32 / 64 / 96 / 128, e.g. 24 -> 32,
-    // 80 / 88 -> 96, zero padded);
-    // Da = H * hdp is the row width of qkv thirds and of ctx.  Scratch below exists only when hdp != hd.
+    // attention width: heads of hd = D / H dims run at hdp = attn_width(hd) dims (hdp == hd unless hd is not 32 / 64 / 80 / 88 / 96 /
+    // 128, e.g. 24 -> 32, zero padded); Da = H * hdp is the row width of qkv thirds and of ctx.  Scratch below exists only when hdp != hd.
     int hd, hdp, Da;
     // set by a layer whose fc2 epilogue already produced the NEXT layer's first LayerNorm (ln1o / mean1 / rstd1), cleared by the consumer
     bool ln1_ready = false;
@@ -98,6 +97,13 @@ struct Work {
     bool join_pending[2] = {false, false};
     int64_t pend_lo[2], pend_hi[2];
 };
+
+// the head width a stack runs attention at (attention.hip): 80 / 88 in place unless bvc_set_option("head_pad", 1) asks for the
+// zero-padded 96 of earlier builds; other widths round up to 32 / 64 / 96 / 128 (zero-padded copies of the qkv / proj weights)
+inline int attn_width(int hd) {
+    if ((hd == 80 || hd == 88) && !options().head_pad) return hd;
+    return hd <= 32 ? 32 : hd <= 64 ? 64 : hd <= 96 ? 96 : 128;
+}
 
 LayerOff add_layer_params(ParamTable& t, const std::string& prefix, int64_t d, int64_t inter, bool hf_names);
 int alloc_stack(Arena& a, Stack& s, int D, int I, int H, int nlayers, float eps, size_t M, size_t BHN);

@@ -65,7 +65,7 @@ LayerOff add_layer_params(ParamTable& t, const std::string& p, int64_t d, int64_
 int alloc_stack(Arena& a, Stack& s, int D, int I, int H, int nlayers, float eps, size_t M, size_t BHN) {
     s.D = D; s.I = I; s.H = H; s.nlayers = nlayers; s.eps = eps;
     s.hd = D / H;
-    s.hdp = s.hd <= 32 ? 32 : s.hd <= 64 ? 64 : s.hd <= 96 ? 96 : 128;      // the attention widths (attention.hip)
+    s.hdp = attn_width(s.hd);
     BVC_REQUIRE(D % H == 0 && s.hd <= 128 && s.hd % 8 == 0, "stack: head_dim %d unsupported (multiples of 8 up to 128)", s.hd);
     s.Da = H * s.hdp;
     const size_t Da = s.Da;

@@ -49,10 +49,19 @@ int check_config(const bvc_videomae_config& c) {
     BVC_REQUIRE(c.image_size > 0 && c.patch_size > 0 && c.image_size % c.patch_size == 0, "config: image_size %% patch_size != 0");
     BVC_REQUIRE(c.num_frames > 0 && c.tubelet_size > 0 && c.num_frames % c.tubelet_size == 0, "config: num_frames %% tubelet_size != 0");
     BVC_REQUIRE(c.patch_size % 8 == 0, "config: patch_size must be a multiple of 8");
-    BVC_REQUIRE(c.hidden_size == 64 * c.num_attention_heads, "config: encoder head_dim must be 64 (hidden %d, heads %d)", c.hidden_size, c.num_attention_heads);
-    BVC_REQUIRE(c.decoder_hidden_size == 64 * c.decoder_num_attention_heads, "config: decoder head_dim must be 64");
+    // the widths check_vit (jepa.hip) accepts: heads of any multiple of 8 up to 128 dims (attention.hip runs 32 / 64 / 80 / 88 / 96 /
+    // 128 as they are, other widths zero-padded: stack.h attn_width), rows up to 1536 wide (rowops.hip: the 6-chunk LayerNorm)
+    BVC_REQUIRE(c.num_attention_heads > 0 && c.hidden_size % c.num_attention_heads == 0, "config: encoder head_dim undefined (hidden_size %d %% num_attention_heads %d != 0)",
+                c.hidden_size, c.num_attention_heads);
+    BVC_REQUIRE(c.decoder_num_attention_heads > 0 && c.decoder_hidden_size % c.decoder_num_attention_heads == 0,
+                "config: decoder head_dim undefined (decoder_hidden_size %d %% decoder_num_attention_heads %d != 0)", c.decoder_hidden_size, c.decoder_num_attention_heads);
+    const int hd = c.hidden_size / c.num_attention_heads, hdd = c.decoder_hidden_size / c.decoder_num_attention_heads;
+    BVC_REQUIRE(hd % 8 == 0 && hd <= 128, "config: encoder head_dim %d unsupported (multiples of 8 up to 128)", hd);
+    BVC_REQUIRE(hdd % 8 == 0 && hdd <= 128, "config: decoder head_dim %d unsupported (multiples of 8 up to 128)", hdd);
+    BVC_REQUIRE(c.hidden_size % 64 == 0 && c.decoder_hidden_size % 64 == 0, "config: hidden sizes must be multiples of 64");
+    BVC_REQUIRE(c.hidden_size <= 1536 && c.decoder_hidden_size <= 1536, "config: hidden sizes above 1536 unsupported (hidden %d, decoder %d)",
+                c.hidden_size, c.decoder_hidden_size);
     BVC_REQUIRE(c.intermediate_size % 64 == 0 && c.decoder_intermediate_size % 64 == 0, "config: intermediate sizes must be multiples of 64");
-    BVC_REQUIRE(c.hidden_size <= 1024 && c.decoder_hidden_size <= 1024, "config: hidden sizes above 1024 unsupported");
     BVC_REQUIRE((c.num_channels * c.tubelet_size * c.patch_size * c.patch_size) % 64 == 0, "config: patch dim must be a multiple of 64");
     BVC_REQUIRE(c.num_hidden_layers >= 1 && c.decoder_num_hidden_layers >= 1, "config: need at least one layer each");
     return BVC_OK;
@@ -152,6 +161,7 @@ int bvc_set_option(const char* name, int value) {
     else if (!strcmp(name, "row_stagger")) options().row_stagger = value != 0;
     else if (!strcmp(name, "row_ln")) { BVC_REQUIRE(value >= -1 && value <= 1, "set_option: row_ln takes -1 / 0 / 1"); options().row_ln = value; }
     else if (!strcmp(name, "deterministic")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: deterministic takes 0 / 1"); options().deterministic = value; }
+    else if (!strcmp(name, "head_pad")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: head_pad takes 0 / 1"); options().head_pad = value; }
     else BVC_REQUIRE(false, "set_option: unknown option '%s'", name);
     return BVC_OK;
 }
@@ -161,6 +171,7 @@ int bvc_get_option(const char* name) {
     if (name && !strcmp(name, "row_ln")) return options().row_ln;
     if (name && !strcmp(name, "row_stagger")) return options().row_stagger;
     if (name && !strcmp(name, "deterministic")) return options().deterministic;
+    if (name && !strcmp(name, "head_pad")) return options().head_pad;
     bvc::set_error("get_option: unknown option '%s'", name ? name : "(null)");
     return BVC_ERR_INVALID;
 }
@@ -219,6 +230,20 @@ int bvc_videomae_create(const bvc_videomae_config* cfg, int max_batch, int num_m
     const int H = cfg->num_attention_heads, Hd = cfg->decoder_num_attention_heads;
     int rc = BVC_OK;
     auto fail = [&](int r) { bvc_videomae_destroy(c); return r; };
+    {   // every bf16 operand travels with a 32-bit byte extent: refuse before allocating anything (alloc_stack checks it again).  The
+        // widest is the decoder's fc1 output (VideoMAE-H: 1568 x 2560 per clip, 4 GiB at 534 clips; from 2 GiB, 267 clips, the
+        // 256-row persistent GEMM hands those products to the 128 x 128 kernels)
+        const size_t we = std::max<size_t>(3 * (size_t)H * attn_width(D / H), (size_t)I), wd = std::max<size_t>(3 * (size_t)Hd * attn_width(Dd / Hd), (size_t)Id);
+        const size_t ee = Mv * we * 2, ed = Md * wd * 2;
+        if (ee >= 0xFFFFFFF0ull || ed >= 0xFFFFFFF0ull) {
+            const bool dec = ed >= ee;
+            set_error("create: max_batch %d exceeds the 4 GiB operand extent: the %s's %zu tokens x %zu bf16 columns are %.2f GiB; at most %zu clips",
+                      max_batch, dec ? "decoder" : "encoder", dec ? Md : Mv, dec ? wd : we, (dec ? ed : ee) / 1073741824.0,
+                      (size_t)(0xFFFFFFEFull / std::max((dec ? ed : ee) / B, (size_t)1)));
+            delete c;
+            return BVC_ERR_INVALID;
+        }
+    }
 #define A(expr) if ((rc = (expr)) != BVC_OK) return fail(rc)
     A(c->arena.alloc(&c->pos_enc, (size_t)c->L * D));
     A(c->arena.alloc(&c->pos_dec, (size_t)c->L * Dd));
@@ -574,6 +599,21 @@ int bvc_op_attention_bwd_part(const void* qkv, const void* ctx_in, const void* d
     return launch_attn_bwd((const bf16_t*)qkv, (const bf16_t*)ctx_in, (const bf16_t*)dctx, lse, delta, (bf16_t*)dqkv, B, N, H, head_dim,
                            (hipStream_t)stream, 0.f, part);
 }
+int bvc_op_attention_width(int head_dim) {
+    BVC_REQUIRE(head_dim > 0 && head_dim <= 128 && head_dim % 8 == 0, "op_attention_width: head_dim %d unsupported", head_dim);
+    return attn_width(head_dim);
+}
+int bvc_op_attention_fwd_scaled(const void* qkv, void* ctx_out, float* lse, int B, int N, int H, int head_dim, float softmax_scale,
+                                void* stream) {
+    BVC_REQUIRE(qkv && ctx_out && lse && softmax_scale >= 0.f, "op_attention_fwd_scaled: bad argument");
+    return launch_attn_fwd((const bf16_t*)qkv, (bf16_t*)ctx_out, lse, B, N, H, head_dim, (hipStream_t)stream, softmax_scale);
+}
+int bvc_op_attention_bwd_scaled(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta, void* dqkv,
+                                int B, int N, int H, int head_dim, float softmax_scale, void* stream) {
+    BVC_REQUIRE(qkv && ctx_in && dctx && lse && delta && dqkv && softmax_scale >= 0.f, "op_attention_bwd_scaled: bad argument");
+    return launch_attn_bwd((const bf16_t*)qkv, (const bf16_t*)ctx_in, (const bf16_t*)dctx, lse, delta, (bf16_t*)dqkv, B, N, H, head_dim,
+                           (hipStream_t)stream, softmax_scale);
+}
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y,
                          float* mean, float* rstd, int M, int D, float eps, void* stream) {
     BVC_REQUIRE(x && gamma && beta && y && mean && rstd, "op_layernorm_fwd: null argument");
@@ -617,7 +657,7 @@ int bvc_op_row_ln_selected(int tokens, int width, int mlp_width, int heads) {
     if (tokens <= 0 || width <= 0 || heads <= 0 || width % heads != 0) return 0;
     Stack s;
     s.D = width; s.I = mlp_width; s.H = heads; s.nlayers = 0; s.eps = 0.f; s.x_out = nullptr;
-    s.hd = width / heads; s.hdp = s.hd <= 32 ? 32 : 64; s.Da = heads * s.hdp;
+    s.hd = width / heads; s.hdp = attn_width(s.hd); s.Da = heads * s.hdp;
     return fuse_row_ln(s, tokens) ? 1 : 0;
 }
 int bvc_op_sgd_step_segments(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,

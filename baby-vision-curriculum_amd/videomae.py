@@ -343,8 +343,34 @@ class VideoMAEForVideoClassification(FlatParamModule):
         return ImageClassifierOutput(logits=logits, last_hidden_state=tokens)
 
 
+# The VideoMAE (v1) pre-training shapes: (hidden, layers, heads, decoder hidden, decoder heads).  All use patch 16, tubelet 2,
+# decoder depth 4, MLP ratio 4 and norm_pix_loss=True; 'base' is exactly get_config's.  Heads are 64 wide except huge's 80 (1280 / 16
+# in the encoder, 640 / 8 in the decoder), which the attention kernels run in place.
+VIDEOMAE_ARCHS = {
+    "small": (384, 12, 6, 192, 3),
+    "base": (768, 12, 12, 384, 6),
+    "large": (1024, 24, 16, 512, 8),
+    "huge": (1280, 32, 16, 640, 8),
+}
+
+
+def videomae_config(architecture="base", **overrides):
+    """VideoMAEConfig of one VIDEOMAE_ARCHS entry at 16 frames of 224^2; keyword overrides (num_frames, image_size, a reduced
+    num_hidden_layers, ...) replace single fields.  The MLP widths follow the hidden sizes unless overridden too."""
+    if architecture not in VIDEOMAE_ARCHS:
+        raise ValueError(f"architecture {architecture!r} not in {sorted(VIDEOMAE_ARCHS)}")
+    D, depth, heads, Dd, Hd = VIDEOMAE_ARCHS[architecture]
+    kw = dict(image_size=224, patch_size=16, num_channels=3, num_frames=16, tubelet_size=2, hidden_size=D, num_hidden_layers=depth,
+              num_attention_heads=heads, initializer_range=0.02, use_mean_pooling=True, decoder_num_attention_heads=Hd,
+              decoder_hidden_size=Dd, decoder_num_hidden_layers=4, norm_pix_loss=True)
+    kw.update(overrides)
+    kw.setdefault("intermediate_size", 4 * kw["hidden_size"])
+    kw.setdefault("decoder_intermediate_size", 4 * kw["decoder_hidden_size"])
+    return VideoMAEConfig(**kw)
+
+
 def get_config(image_size, args):
-    """pretrain_videomae.py:43-58 (only architecture='base' exists in the reference)."""
+    """pretrain_videomae.py:43-58 (only architecture='base' exists in the reference; videomae_config builds the other sizes)."""
     if getattr(args, "architecture", "base") != "base":
         raise ValueError("only architecture='base' is defined by the reference")
     return VideoMAEConfig(image_size=image_size, patch_size=16, num_channels=3, num_frames=args.num_frames,

@@ -58,6 +58,8 @@ const char* bvc_version(void);
  *                 kernels 3-5, 8, 14 of a -DBVC_EXPERIMENTS build) return BVC_ERR_INVALID for split / accumulating / bias-gradient
  *                 outputs; tile configs 6 / 7 / 9 run them on the 128 x 128 / 128 x 64 deterministic kernel.
  *                 Read at every launch, so it may change between calls (not while a call is being enqueued elsewhere).
+ *   "head_pad"    0 (default) / 1: 1 = heads of 80 / 88 dims run zero-padded to 96 (padded weight copies, pad / unpad launches), the
+ *                 layout of earlier builds; 0 = in place.  Read when a model context allocates its stacks (same-process A/Bs only).
  * bvc_get_option returns the value, or BVC_ERR_INVALID for an unknown name; bvc_set_option rejects values outside the list. */
 int bvc_set_option(const char* name, int value);
 int bvc_get_option(const char* name);
@@ -294,15 +296,24 @@ int bvc_op_gemm_kernel(const bvc_gemm_desc* problems, int count, int layout, int
 int bvc_op_row_ln_selected(int tokens, int width, int mlp_width, int heads);
 int bvc_op_gemm_plan_dw(bvc_gemm_desc* problems, int count);
 
-/* softmax(QK^T/sqrt(d))V for head_dim d = 32, 64, 96 or 128; qkv bf16 [B*N][3*d*H]; replaces HF:181-206 / SDPA (HF:239-252) and
+/* softmax(QK^T/sqrt(d))V for head_dim d = 32, 64, 80, 88, 96 or 128; qkv bf16 [B*N][3*d*H]; replaces HF:181-206 / SDPA (HF:239-252) and
  * Attention.forward of pretraining/predictive/vision_transformer.py:198-210 (the ViT-B predictor has d = 32, the ViT-Ti predictor
- * d = 128; ViT-H / ViT-g encoders run their 80 / 88-wide heads zero-padded to 96) */
+ * d = 128; ViT-H / ViT-g encoders and VideoMAE-H have 80 / 88-wide heads, which run in place: head h at column h*d) */
 int bvc_op_attention_fwd(const void* qkv, void* ctx_out, float* lse, int B, int N, int H, int head_dim, void* stream);
 int bvc_op_attention_bwd(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta_scratch,
                          void* dqkv, int B, int N, int H, int head_dim, void* stream);
 /* one of the backward's two kernels alone (timing probes): part 1 = dQ (+ delta_scratch), part 2 = dK / dV (reads delta_scratch) */
 int bvc_op_attention_bwd_part(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta_scratch,
                               void* dqkv, int B, int N, int H, int head_dim, int part, void* stream);
+/* the head width a model context allocated now runs attention at for heads of head_dim dims (stack.h attn_width): head_dim itself
+ * for 32 / 64 / 80 / 88 / 96 / 128 (80 / 88: 96 while "head_pad" is 1), the next of 32 / 64 / 96 / 128 (zero-padded) otherwise */
+int bvc_op_attention_width(int head_dim);
+/* the forward / backward with an explicit softmax scale (0 = 1/sqrt(head_dim)): what a caller that zero-pads narrower heads to a
+ * wider head_dim passes (1/sqrt of the true width; bvc_set_option("head_pad", 1) runs 80 / 88 that way) */
+int bvc_op_attention_fwd_scaled(const void* qkv, void* ctx_out, float* lse, int B, int N, int H, int head_dim, float softmax_scale,
+                                void* stream);
+int bvc_op_attention_bwd_scaled(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta_scratch,
+                                void* dqkv, int B, int N, int H, int head_dim, float softmax_scale, void* stream);
 /* nn.LayerNorm forward/backward (HF:336-337,484); rows may be strided by (rin, rout, roff), rin<=0 = dense */
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y_bf16,
                          float* mean, float* rstd, int M, int D, float eps, void* stream);

@@ -13,9 +13,11 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--nctx", type=int, default=100)
 ap.add_argument("--npred", type=int, default=25)
+ap.add_argument("--head-pad", type=int, default=0, help="bvc_set_option('head_pad'): 1 = heads of 80 / 88 zero-padded to 96 (A/B)")
 args = ap.parse_args()
 ge.build()
 bvc = ge.load_package()
+bvc._lib.set_option("head_pad", args.head_pad)
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
 enc, pred = bvc.jepa.get_model(dev, patch_size=16, tubelet_size=1, num_frames=2, model_name=args.model, image_size=224)

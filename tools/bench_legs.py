@@ -8,6 +8,7 @@ Each returns a dict with throughput, ms per step and TFLOP/s against the algorit
 import copy
 import time
 
+import numpy as np
 import torch
 
 JEPA_GFLOP = {"vit_base": 160.6, "vit_large": 473.2}     # per sample at N_ctx = 100, N_pred = 25
@@ -27,6 +28,27 @@ def jepa_gflop(embed_dim, depth, mlp_hidden, nctx=100, npred=25, nsets=4, tokens
     predictor = nsets * (layers(nctx + npred, pred_dim, 4 * pred_dim, pred_depth) + 2 * nctx * embed_dim * pred_dim
                          + 2 * npred * pred_dim * embed_dim)
     return (target + 3 * (context + predictor)) / 1e9
+
+
+def videomae_gflop(config, mask_ratio=0.9):
+    """Algorithmic GFLOP of one VideoMAE pre-training clip, BASELINE.md section 3's counting (202.295 for base): tube masking hides
+    int(mask_ratio x patches per frame) patches of every frame; the patch embedding runs on the visible tokens and needs no input
+    gradient (2x), everything else - encoder, encoder-to-decoder, decoder on all tokens, head on the masked ones - counts 3x."""
+    c = config
+    g = c.image_size // c.patch_size
+    per, T = g * g, c.num_frames // c.tubelet_size
+    L = T * per
+    nmask = T * int(mask_ratio * per)
+    nvis = L - nmask
+    P = c.num_channels * c.tubelet_size * c.patch_size * c.patch_size
+
+    def layers(n, d, i, count):
+        return count * (8 * n * d * d + 4 * n * d * i + 4 * n * n * d)
+    D, Dd = c.hidden_size, c.decoder_hidden_size
+    patch = 2 * nvis * P * D
+    rest = (layers(nvis, D, c.intermediate_size, c.num_hidden_layers) + 2 * nvis * D * Dd
+            + layers(L, Dd, c.decoder_intermediate_size, c.decoder_num_hidden_layers) + 2 * nmask * Dd * P)
+    return (2 * patch + 3 * rest) / 1e9
 
 
 def _timed(step, warmup, steps):
@@ -84,6 +106,39 @@ def jepa_leg(bvc, dev, model="vit_large", batch=16, nctx=100, npred=25, warmup=6
                         "encoders, predictor, smooth-L1, bwd, SGD-Nesterov, EMA)" + ("; target forward on a second stream" if overlap_target else ""),
             "value": round(B / dt, 1), "unit": "samples/s", "ms_per_step": round(1e3 * dt, 3), "steps": steps,
             "tflops": round(gf * B / dt / 1e3, 1), "frac_of_mfma_peak": round(gf * B / dt / 1e3 / 2500.0, 4), "final_loss": round(loss, 5)}
+
+
+def videomae_leg(bvc, dev, arch="base", batch=16, warmup=5, steps=10, mask_ratio=0.9):
+    """VideoMAE pre-training step of one VIDEOMAE_ARCHS size: synthetic 16 x 224^2 clips, tube masking at mask_ratio, bf16 autocast,
+    backward, fused SGD-Nesterov with GradScaler - the headline's step at another model size."""
+    torch.manual_seed(0)
+    cfg = bvc.videomae_config(arch)
+    model = bvc.VideoMAEForPreTraining(cfg).to(dev).train()
+    model._ensure_flat(dev)
+    # bench.py's optimiser and scaler: the fused SGD-Nesterov over the flat parameters, bvc.amp.GradScaler
+    opt = bvc.optim.SGD(model.parameters(), lr=0.1, momentum=0.9, nesterov=True, weight_decay=0.0)
+    scaler = bvc.amp.GradScaler("cuda")
+    B, T, g = batch, cfg.num_frames // cfg.tubelet_size, cfg.image_size // cfg.patch_size
+    gen = torch.Generator().manual_seed(1234)
+    clips = torch.randn(B, cfg.num_frames, 3, cfg.image_size, cfg.image_size, generator=gen).to(dev)
+    mgen = bvc.TubeMaskingGenerator((T, g, g), mask_ratio, rng=np.random.RandomState(1234))
+    mask = torch.from_numpy(np.stack([mgen() for _ in range(B)])).bool().to(dev)
+
+    def step():
+        opt.zero_grad()
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            loss = model(clips, bool_masked_pos=mask).loss
+        scaler.scale(loss).backward()
+        scaler.step(opt)
+        scaler.update()
+        return loss
+
+    dt, loss = _timed(step, warmup, steps)
+    gf = videomae_gflop(cfg, mask_ratio)
+    return {"workload": f"VideoMAE-{arch} pre-training, 16x224^2 clips, mask {mask_ratio}, {B} clips/GPU, full step (fwd, bwd, SGD-Nesterov, "
+                        "GradScaler)", "value": round(B / dt, 2), "unit": "clips/s", "ms_per_step": round(1e3 * dt, 3), "steps": steps,
+            "gflop_per_clip": round(gf, 3), "tflops": round(gf * B / dt / 1e3, 1), "frac_of_mfma_peak": round(gf * B / dt / 1e3 / 2500.0, 4),
+            "final_loss": round(loss, 5)}
 
 
 def simclr_leg(bvc, dev, images=512, warmup=3, steps=10):

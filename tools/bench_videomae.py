@@ -1,0 +1,30 @@
+"""VideoMAE pre-training throughput of the VIDEOMAE_ARCHS sizes on one MI355X (tools/bench_legs.videomae_leg: synthetic 16 x 224^2
+clips, tube mask 0.9, bf16 autocast, backward, fused SGD-Nesterov, GradScaler).  One JSON line per (arch, batch) on stdout.
+
+    python tools/bench_videomae.py --arch small,base,large,huge --batch 16,64 [--steps 10] [--warmup 5]"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge   # noqa: E402
+from tools.bench_legs import videomae_leg   # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--arch", default="base", help="comma-separated VIDEOMAE_ARCHS keys")
+ap.add_argument("--batch", default="16", help="comma-separated clips per step")
+ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--warmup", type=int, default=5)
+args = ap.parse_args()
+ge.build()
+bvc = ge.load_package()
+dev = torch.device("cuda:0")
+for arch in args.arch.split(","):
+    for b in (int(x) for x in args.batch.split(",")):
+        r = videomae_leg(bvc, dev, arch=arch, batch=b, warmup=args.warmup, steps=args.steps)
+        print(json.dumps({"arch": arch, "batch": b, **r}), flush=True)
+        torch.cuda.empty_cache()

@@ -115,7 +115,14 @@ SYMBOLS = {
     "bvc_videomae_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "bvc_videomae_encode_px": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PixelFormatC), c_int, c_void_p, c_void_p, c_void_p, c_float,
                                        c_void_p, c_void_p, c_void_p]),
-    "bvc_vit_param_count": (c_int, [ctypes.POINTER(VitConfigC)]),
+    "bvc_videomae_encoder_fc_norm_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bvc_videomae_cls_create": (c_int, [ctypes.POINTER(VideoMAEConfigC), c_int, ctypes.POINTER(c_void_p)]),
+    "bvc_videomae_cls_destroy": (None, [c_void_p]),
+    "bvc_videomae_cls_forward_px": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PixelFormatC), c_int, c_void_p, c_void_p, c_void_p,
+                                            c_float, c_void_p, c_void_p, c_void_p]),
+    "bvc_videomae_cls_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, BUCKET_FN, c_void_p, c_void_p]),
+    "bvc_videomae_cls_shadow": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int64)]),
+    "bvc_vit_param_count":(c_int, [ctypes.POINTER(VitConfigC)]),
     "bvc_vit_param_numel": (c_int64, [ctypes.POINTER(VitConfigC)]),
     "bvc_vit_param_info": (c_int, [ctypes.POINTER(VitConfigC), c_int, ctypes.c_char_p, c_int, ctypes.POINTER(c_int64),
                                    ctypes.POINTER(c_int64), ctypes.POINTER(c_int), ctypes.POINTER(c_int64)]),

@@ -38,6 +38,11 @@ int launch_colsum_bf16_scaled(const bf16_t* X, int M, int N, int ld, float alpha
 int launch_colsum_f32(const float* X, RowMap rm, int M, int D, float* out, hipStream_t s);
 int launch_token_mean(const float* x, int B, int N, int D, float* out, hipStream_t s);
 int launch_token_mean_bwd(const float* dmean, int B, int N, int D, float* dx, hipStream_t s);
+// backward of y = LayerNorm(p) over B pooled rows p = token_mean(x) (saved mean / rstd of p), in one launch and a fixed order:
+// dgamma / dbeta (written, not accumulated) and, unless dres is nullptr, d/dx broadcast to all N token rows of each clip as f32
+// dres [B*N][D] and its bf16 copy dres_bf
+int launch_fcnorm_bwd_bcast(const float* dy, const float* p, const float* mean, const float* rstd, const float* gamma, float* dres,
+                            bf16_t* dres_bf, float* dgamma, float* dbeta, int B, int N, int D, hipStream_t s);
 int launch_cast_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int launch_gather_rows_bf16(const float* in, RowMap rm, bf16_t* out, int M, int D, hipStream_t s);
 int launch_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, hipStream_t s);

@@ -359,6 +359,68 @@ __global__ void token_mean_bwd_kernel(const float* __restrict__ dmean, float* __
     *reinterpret_cast<f32x4*>(dx + e) = g;
 }
 
+// Backward of fc_norm(token_mean(x)) (VideoMAEForVideoClassification fine-tuning) in one launch, no atomics.
+// Workgroup (x, b) with b < B re-derives clip b's LayerNorm backward from its pooled row p (D <= 1536 floats):
+//   g = dy * gamma,  dp = rstd * (g - mean(g) - xhat * mean(g * xhat)),  xhat = (p - mean) * rstd,
+// keeps dp / N in LDS and writes it to token rows [x * kFcRows, x * kFcRows + kFcRows) of the clip, in f32 (dres) and as the bf16 copy
+// (dres_bf) the last encoder layer's backward reads.  Workgroups of row y == pblk write dgamma = sum_b dy * xhat and dbeta = sum_b dy for
+// 256 columns each, over the B rows in order: the same bits on every run.  dres == nullptr (pblk = 0): the parameter gradients only.
+constexpr int kFcRows = 32;
+__global__ __launch_bounds__(256) void fcnorm_bwd_bcast_kernel(const float* __restrict__ dy, const float* __restrict__ p,
+                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                               const float* __restrict__ gamma, float* __restrict__ dres,
+                                                               bf16_t* __restrict__ dres_bf, float* __restrict__ dgamma,
+                                                               float* __restrict__ dbeta, int B, int N, int D, int pblk) {
+    const int b = blockIdx.y;
+    if (b == pblk) {
+        const int d = blockIdx.x * 256 + threadIdx.x;
+        if (d >= D) return;
+        float sg = 0.f, sb = 0.f;
+        for (int r = 0; r < B; ++r) {
+            const float g = dy[(size_t)r * D + d];
+            sg += g * ((p[(size_t)r * D + d] - mean[r]) * rstd[r]);
+            sb += g;
+        }
+        dgamma[d] = sg;
+        dbeta[d] = sb;
+        return;
+    }
+    const int r0 = blockIdx.x * kFcRows;
+    if (r0 >= N) return;
+    __shared__ __attribute__((aligned(16))) float dps[1536];
+    __shared__ float red[2][4];
+    const float mu = mean[b], rs = rstd[b];
+    const float* dyr = dy + (size_t)b * D;
+    const float* pr = p + (size_t)b * D;
+    float s1 = 0.f, s2 = 0.f;
+    for (int d = threadIdx.x; d < D; d += 256) {
+        const float g = dyr[d] * gamma[d];
+        s1 += g;
+        s2 += g * ((pr[d] - mu) * rs);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[0][wave] = s1; red[1][wave] = s2; }
+    __syncthreads();
+    const float m1 = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)D;
+    const float m2 = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)D;
+    for (int d = threadIdx.x; d < D; d += 256) {
+        const float g = dyr[d] * gamma[d];
+        dps[d] = (rs * (g - m1 - ((pr[d] - mu) * rs) * m2)) / (float)N;
+    }
+    __syncthreads();
+    const int nch = D >> 2, rows = min(N - r0, kFcRows);
+    const size_t base = ((size_t)b * N + r0) * D;
+    for (int i = threadIdx.x; i < rows * nch; i += 256) {
+        const int r = i / nch, c = i - r * nch;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(dps + c * 4);
+        const size_t o = base + (size_t)r * D + (size_t)c * 4;
+        *reinterpret_cast<f32x4*>(dres + o) = v;
+        *reinterpret_cast<uint2*>(dres_bf + o) = uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+    }
+}
+
 // ============================================================================ elementwise
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, size_t n) {
     const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
@@ -1316,6 +1378,24 @@ int launch_token_mean_bwd(const float* dmean, int B, int N, int D, float* dx, hi
     BVC_REQUIRE(D % 4 == 0, "token_mean_bwd: D must be a multiple of 4");
     const size_t total4 = (size_t)B * N * D / 4;
     hipLaunchKernelGGL(token_mean_bwd_kernel, dim3(blocks_for(total4)), dim3(256), 0, s, dmean, dx, N, D, total4);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_fcnorm_bwd_bcast(const float* dy, const float* p, const float* mean, const float* rstd, const float* gamma, float* dres,
+                            bf16_t* dres_bf, float* dgamma, float* dbeta, int B, int N, int D, hipStream_t s) {
+    BVC_REQUIRE(dy && p && mean && rstd && gamma && dgamma && dbeta && B >= 1 && N >= 1, "fcnorm_bwd_bcast: bad argument");
+    BVC_REQUIRE(D % 4 == 0 && D <= 1536, "fcnorm_bwd_bcast: D=%d unsupported (a multiple of 4 up to 1536)", D);
+    BVC_REQUIRE((dres == nullptr) == (dres_bf == nullptr), "fcnorm_bwd_bcast: dres and its bf16 copy go together");
+    const int pcols = (D + 255) / 256;
+    if (!dres) {
+        hipLaunchKernelGGL(fcnorm_bwd_bcast_kernel, dim3(pcols, 1), dim3(256), 0, s, dy, p, mean, rstd, gamma, dres, dres_bf, dgamma, dbeta,
+                           B, N, D, 0);
+    } else {
+        const int chunks = (N + kFcRows - 1) / kFcRows;
+        hipLaunchKernelGGL(fcnorm_bwd_bcast_kernel, dim3(std::max(chunks, pcols), B + 1), dim3(256), 0, s, dy, p, mean, rstd, gamma, dres,
+                           dres_bf, dgamma, dbeta, B, N, D, B);
+    }
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

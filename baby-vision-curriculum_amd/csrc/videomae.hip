@@ -463,6 +463,7 @@ struct bvc_encoder_ctx {
     float *pos_enc, *xa, *xb, *pooled, *mean, *rstd;
     bf16_t *wbf, *Ape;
     int* idx_all;
+    int pooled_batch = 0;    // clips whose pre-norm pooled rows and fc_norm statistics the last encode left (0: none)
 };
 
 void bvc_videomae_encoder_destroy(bvc_encoder_ctx* c) {
@@ -546,12 +547,174 @@ int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc
         TRY(layer_forward(c->w, c->st, 0, L.enc[i], x, dst, B, N, st));
         if (dst == y) std::swap(x, y); else x = dst;
     }
+    c->pooled_batch = 0;
     if (pooled) {
         float* mp = fc_norm_w ? c->pooled : pooled;
         TRY(launch_token_mean(x, B, N, D, mp, st));
         if (fc_norm_w)
             TRY(launch_ln_fwd(mp, identity_rows(), fc_norm_w, fc_norm_b, nullptr, c->mean, c->rstd, B, D, fc_norm_eps, st, pooled));
+        if (fc_norm_w) c->pooled_batch = B;
     }
+    return BVC_OK;
+}
+
+int bvc_videomae_encoder_fc_norm_backward(bvc_encoder_ctx* c, const float* dpooled, const float* fc_norm_w, float* dfc_norm_w,
+                                          float* dfc_norm_b, void* stream) {
+    BVC_REQUIRE(c && dpooled && fc_norm_w && dfc_norm_w && dfc_norm_b, "encoder_fc_norm_backward: null argument");
+    if (c->pooled_batch < 1) {
+        set_error("encoder_fc_norm_backward: the last encode ran no fc_norm (call bvc_videomae_encode_px with fc_norm weights first)");
+        return BVC_ERR_STATE;
+    }
+    return launch_fcnorm_bwd_bcast(dpooled, c->pooled, c->mean, c->rstd, fc_norm_w, nullptr, nullptr, dfc_norm_w, dfc_norm_b,
+                                   c->pooled_batch, c->L, c->cfg.hidden_size, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ fine-tuning (VideoMAEForVideoClassification with labels)
+// The encoder of the inference context above at full sequence length, with autograd: every layer keeps its own LayerAct (M = B * L
+// tokens) for the backward, as the pre-training encoder does for its visible tokens.  The forward issues the launches of
+// bvc_videomae_encode_px in the same order on the same shapes (layer_forward without the next layer's LayerNorm in the fc2 epilogue,
+// as the inference context runs it), so its pooled rows equal the inference context's bit for bit.
+struct bvc_cls_ctx {
+    bvc_videomae_config cfg;
+    Layout lay;
+    int max_batch, L, P;
+    Arena arena;
+    Work w;
+    Stack enc;         // num_hidden_layers LayerActs
+    float *pos_enc, *pooled_pre, *mean, *rstd, *fcw, *dres;
+    bf16_t *wbf, *Ape;
+    int* idx_all;
+    int batch = 0;
+    bool have_forward = false;
+    bool shadow_valid = false;   // as bvc_ctx::shadow_valid
+};
+
+void bvc_videomae_cls_destroy(bvc_cls_ctx* c) {
+    if (!c) return;
+    free_work(c->w);
+    c->arena.release();
+    delete c;
+}
+
+int bvc_videomae_cls_create(const bvc_videomae_config* cfg, int max_batch, bvc_cls_ctx** out) {
+    BVC_REQUIRE(cfg && out, "cls_create: null argument");
+    TRY(check_config(*cfg));
+    BVC_REQUIRE(max_batch >= 1, "cls_create: max_batch must be >= 1");
+    const int g = cfg->image_size / cfg->patch_size;
+    const size_t L = (size_t)(cfg->num_frames / cfg->tubelet_size) * g * g;
+    const size_t P = (size_t)cfg->num_channels * cfg->tubelet_size * cfg->patch_size * cfg->patch_size;
+    const int D = cfg->hidden_size, I = cfg->intermediate_size, H = cfg->num_attention_heads;
+    const size_t Da = (size_t)H * attn_width(D / H);
+    {   // every bf16 operand travels with a 32-bit byte extent: refuse before allocating anything (the widest is fc1's output, or
+        // the qkv product's when the heads are padded; VideoMAE-B: 1568 x 3072 per clip, 4 GiB at 446 clips)
+        const size_t w = std::max(std::max(3 * Da, (size_t)I), P);
+        const size_t per_clip = L * w * 2, bytes = (size_t)max_batch * per_clip;
+        if (bytes >= 0xFFFFFFF0ull) {
+            set_error("cls_create: max_batch %d exceeds the 4 GiB operand extent: %zu tokens x %zu bf16 columns are %.2f GiB; at most %zu clips",
+                      max_batch, (size_t)max_batch * L, w, bytes / 1073741824.0, (size_t)(0xFFFFFFEFull / per_clip));
+            return BVC_ERR_INVALID;
+        }
+    }
+    bvc_cls_ctx* c = new bvc_cls_ctx();
+    c->cfg = *cfg;
+    c->lay = make_layout(*cfg);
+    c->max_batch = max_batch;
+    c->L = (int)L;
+    c->P = (int)P;
+    const size_t M = (size_t)max_batch * L;
+    int rc = BVC_OK;
+    auto fail = [&](int r) { bvc_videomae_cls_destroy(c); return r; };
+#define A(expr) if ((rc = (expr)) != BVC_OK) return fail(rc)
+    A(c->arena.alloc(&c->pos_enc, L * D));
+    A(c->arena.alloc(&c->wbf, (size_t)c->lay.e2d_w));
+    A(c->arena.alloc(&c->idx_all, M));
+    A(c->arena.alloc(&c->Ape, M * P));
+    A(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, M, (size_t)max_batch * H * L));
+    A(c->arena.alloc(&c->pooled_pre, (size_t)max_batch * D));
+    A(c->arena.alloc(&c->mean, (size_t)max_batch));
+    A(c->arena.alloc(&c->rstd, (size_t)max_batch));
+    A(c->arena.alloc(&c->fcw, (size_t)D));
+    A(c->arena.alloc(&c->dres, M * D));
+    A(alloc_work(c->arena, c->w, M * std::max((size_t)D, (size_t)c->enc.Da), M * I, (size_t)max_batch * H * L,
+                 ln_bwd_workspace_floats_upto((int)M, D)));
+    A(launch_iota_mod(c->idx_all, (int)M, c->L, nullptr));
+#undef A
+    std::vector<float> tab;
+    sinusoid(tab, c->L, D);
+    if (hipMemcpy(c->pos_enc, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("cls_create: pos upload failed"); return fail(BVC_ERR_HIP); }
+    *out = c;
+    return BVC_OK;
+}
+
+int bvc_videomae_cls_forward_px(bvc_cls_ctx* c, const void* pixels_any, const bvc_pixel_format* fmt, int batch, const float* params,
+                                const float* fc_norm_w, const float* fc_norm_b, float fc_norm_eps, float* pooled, float* tokens,
+                                void* stream) {
+    BVC_REQUIRE(c && pixels_any && params && fc_norm_w && fc_norm_b && pooled, "cls_forward: null argument");
+    PixelSrc pixels;
+    TRY(pixel_src(pixels_any, fmt, c->cfg.num_channels, &pixels));
+    BVC_REQUIRE(batch >= 1 && batch <= c->max_batch, "cls_forward: batch %d outside [1, %d]", batch, c->max_batch);
+    hipStream_t st = (hipStream_t)stream;
+    const bvc_videomae_config& cf = c->cfg;
+    const Layout& L = c->lay;
+    const int B = batch, N = c->L, M = B * N, D = cf.hidden_size, P = c->P;
+    c->have_forward = false;
+    c->batch = B;
+    c->w.params = params;
+    c->w.wbf = c->wbf;
+    const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
+    if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
+    c->shadow_valid = false;
+    TRY(launch_gather_patches(pixels, c->idx_all, c->Ape, B, N, pg, st));
+    {
+        GemmProblem p = gemm(c->Ape, (size_t)M * P, P, c->wbf + L.pe_w, (size_t)D * P, P, M, D, P, EPI_POS, c->enc.act[0].x_in, D);
+        p.bias = params + L.pe_b; p.rowtok = c->idx_all; p.pos = c->pos_enc;
+        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
+    }
+    const int nl = c->enc.nlayers;
+    for (int i = 0; i < nl; ++i)
+        TRY(layer_forward(c->w, c->enc, i, L.enc[i], c->enc.act[i].x_in, i + 1 < nl ? c->enc.act[i + 1].x_in : c->enc.x_out, B, N, st));
+    TRY(launch_token_mean(c->enc.x_out, B, N, D, c->pooled_pre, st));
+    TRY(launch_ln_fwd(c->pooled_pre, identity_rows(), fc_norm_w, fc_norm_b, nullptr, c->mean, c->rstd, B, D, fc_norm_eps, st, pooled));
+    BVC_CHECK_HIP(hipMemcpyAsync(c->fcw, fc_norm_w, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
+    if (tokens) BVC_CHECK_HIP(hipMemcpyAsync(tokens, c->enc.x_out, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+    c->have_forward = true;
+    return BVC_OK;
+}
+
+int bvc_videomae_cls_backward(bvc_cls_ctx* c, const float* dpooled, float* G, float* dfc_norm_w, float* dfc_norm_b,
+                              bvc_bucket_fn on_bucket, void* user, void* stream) {
+    BVC_REQUIRE(c && dpooled && G && dfc_norm_w && dfc_norm_b, "cls_backward: null argument");
+    if (!c->have_forward) { set_error("cls_backward: no forward state (call bvc_videomae_cls_forward_px first; one backward per forward)"); return BVC_ERR_STATE; }
+    c->have_forward = false;
+    hipStream_t st = (hipStream_t)stream;
+    const Layout& L = c->lay;
+    const int B = c->batch, N = c->L, M = B * N, D = c->cfg.hidden_size;
+    begin_backward(c->w);
+    BVC_CHECK_HIP(hipMemsetAsync(G, 0, (size_t)L.e2d_w * 4, st));
+    // fc_norm backward on the B pooled rows and the token-mean broadcast into the last layer's residual gradient, one pass
+    TRY(launch_fcnorm_bwd_bcast(dpooled, c->pooled_pre, c->mean, c->rstd, c->fcw, c->dres, c->w.dyb[c->w.seq % 3], dfc_norm_w, dfc_norm_b,
+                                B, N, D, st));
+    for (int i = c->enc.nlayers - 1; i >= 0; --i)
+        TRY(layer_backward(c->w, c->enc, i, L.enc[i], c->enc.act[i].x_in, c->dres, G, B, N, st, on_bucket, user));
+    // patch embedding: weight and bias over all B * L tokens (pixels need no gradient)
+    {
+        GemmProblem p = gemm(c->w.dyb[c->w.seq % 3], (size_t)M * D, D, c->Ape, (size_t)M * c->P, c->P, D, c->P, M, EPI_F32, G + L.pe_w, c->P);
+        p.rowsum = G + L.pe_b;
+        const int tile = plan_dw(&p, 1);
+        TRY(launch_gemm(&p, 1, GEMM_TN, tile, st));
+    }
+    // fence the last side-stream launches (older one first so ranges keep arriving tail-first)
+    TRY(join_side(c->w, c->w.seq & 1, st, on_bucket, user));
+    TRY(join_side(c->w, (c->w.seq + 1) & 1, st, on_bucket, user));
+    if (on_bucket) on_bucket(0, L.enc.front().ln1w, user);
+    return BVC_OK;
+}
+
+int bvc_videomae_cls_shadow(bvc_cls_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
+    BVC_REQUIRE(c, "videomae_cls_shadow: null context");
+    if (shadow_bf16) *shadow_bf16 = c->wbf;
+    if (numel) *numel = (int64_t)c->lay.e2d_w;
+    if (valid >= 0) c->shadow_valid = valid != 0;
     return BVC_OK;
 }
 

@@ -112,7 +112,9 @@ class DistributedDataParallel(nn.Module):
             m = st.module
             if hasattr(m, "_ensure_flat") and self._device is not None:
                 m._ensure_flat(self._device)
-            if isinstance(m, nn.Module):
+            if hasattr(m, "_names"):      # the parameters in its flat buffer (a flat module may also hold ordinary sub-modules)
+                owned.update(id(m._param(n)) for n in m._names)
+            elif isinstance(m, nn.Module):
                 owned.update(id(p) for p in m.parameters())
         self._loose = [p for p in module.parameters() if id(p) not in owned] if isinstance(module, nn.Module) else []
         self._loose_grad = [p for p in self._loose if p.requires_grad]

@@ -108,9 +108,13 @@ class FlatParamModule(nn.Module):
         """For writers that change the parameters through raw pointers without writing the copy (EMA, library broadcast)."""
         self._shadow_stamp = None
 
+    def _shadow_ctx(self):
+        """The library context whose bf16 copy `_shadow_fn` reports (a module with several contexts names the one that trains)."""
+        return getattr(self, "_ctx", None)
+
     def _shadow_base(self):
         """Address of the copy if it is current (so that an optimiser step may keep it current), else None."""
-        h = getattr(self, "_ctx", None)
+        h = self._shadow_ctx()
         if self._shadow_fn is None or h is None or self._shadow_stamp is None or self._shadow_stamp != self._shadow_key(h):
             return None
         p = ctypes.c_void_p()

@@ -13,6 +13,7 @@ parameter / gradient buffers and the autograd bridge.
 from __future__ import annotations
 
 import ctypes
+import warnings
 from dataclasses import dataclass
 from typing import Optional
 
@@ -253,15 +254,124 @@ class ImageClassifierOutput:
     last_hidden_state: Optional[torch.Tensor] = None
 
 
-class VideoMAEForVideoClassification(FlatParamModule):
-    """Encoder-only inference model of the embedding benchmark (benchmarks/compute_embeddings_videomae.py:78-96,253-264).
+def classification_path(training, grad_enabled, encoder_trainable):
+    """Which library context a VideoMAEForVideoClassification forward runs: "train" (the fine-tuning context, the encoder receives
+    gradients) only in train mode with grad mode on and some ``videomae.*`` parameter requiring grad; otherwise "encode" (the
+    inference context: forward only through the encoder, fc_norm and the classifier still under autograd when grad mode is on)."""
+    return "train" if (training and grad_enabled and encoder_trainable) else "encode"
 
-    Same sub-module tree / state-dict keys as transformers.VideoMAEForVideoClassification: ``videomae.embeddings.*``,
-    ``videomae.encoder.*`` (so ``adapt_videomae``'s ``target.videomae.embeddings.load_state_dict(source.videomae.embeddings
-    .state_dict())`` works against a pre-training model), ``fc_norm.*`` and, for ``num_labels > 0``, ``classifier.*``.
-    ``forward(pixel_values).logits`` = classifier(fc_norm(mean over all tokens of the encoder output)); the reference uses
-    ``num_labels=0`` (classifier = Identity), i.e. the logits ARE the embedding.  Forward only (no autograd).
+
+def infer_problem_type(num_labels, labels):
+    """transformers' ForSequenceClassificationLoss rule when config.problem_type is None."""
+    if num_labels == 1:
+        return "regression"
+    if num_labels > 1 and labels.dtype in (torch.long, torch.int):
+        return "single_label_classification"
+    return "multi_label_classification"
+
+
+def classification_loss(config, logits, labels):
+    """transformers 5.15.0 VideoMAEForVideoClassification.forward -> loss_utils.ForSequenceClassificationLoss: infers
+    config.problem_type when it is None and writes it back, then MSE (regression) / cross-entropy with ignore_index -100 /
+    BCEWithLogits on the [B, num_labels] logits."""
+    num_labels = int(getattr(config, "num_labels", 2))
+    if getattr(config, "problem_type", None) is None:
+        config.problem_type = infer_problem_type(num_labels, labels)
+    labels = labels.to(logits.device)
+    if config.problem_type == "regression":
+        if num_labels == 1:
+            return nn.functional.mse_loss(logits.squeeze(), labels.squeeze())
+        return nn.functional.mse_loss(logits, labels)
+    if config.problem_type == "single_label_classification":
+        return nn.functional.cross_entropy(logits.view(-1, num_labels), labels.view(-1), ignore_index=-100)
+    if config.problem_type == "multi_label_classification":
+        return nn.functional.binary_cross_entropy_with_logits(logits, labels)
+    raise ValueError(f"problem_type {config.problem_type!r} unknown")
+
+
+class _TrainCtx:
+    """The fine-tuning context of one model.  Owned: destroyed with its holder, and a deepcopy starts without one."""
+
+    def __init__(self):
+        self.h, self.key = None, None
+
+    def free(self):
+        if self.h is not None:
+            _lib.lib().bvc_videomae_cls_destroy(self.h)
+            self.h, self.key = None, None
+
+    def __deepcopy__(self, memo):
+        return _TrainCtx()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class _ClsTrain(torch.autograd.Function):
+    """pooled = fc_norm(mean over tokens(encoder(pixels))) on the fine-tuning context; backward fills the encoder's flat gradient
+    buffer (views as .grad) and returns fc_norm's gradients to autograd."""
+
+    @staticmethod
+    def forward(ctx, anchor, fc_w, fc_b, model, pixels, want_tokens):
+        ctx.model = model
+        pooled, tokens = model._run_train_forward(pixels, fc_w, fc_b, want_tokens)
+        ctx.stamp = model._stamp_forward()
+        ctx.mark_non_differentiable(tokens) if tokens is not None else None
+        return pooled, tokens
+
+    @staticmethod
+    def backward(ctx, dpooled, _dtokens):
+        ctx.model._check_generation(ctx.stamp)
+        dw, db = ctx.model._run_train_backward(dpooled)
+        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None
+
+
+class _FcNormProbe(torch.autograd.Function):
+    """The inference context's encode (today's call, the same bits) with fc_norm under autograd: the linear-probe case."""
+
+    @staticmethod
+    def forward(ctx, fc_w, fc_b, model, pixels, want_tokens):
+        ctx.model = model
+        pooled, tokens = model._run_encode(pixels, fc_w, fc_b, want_tokens)
+        ctx.stamp = model._stamp_forward()
+        ctx.save_for_backward(fc_w)
+        ctx.mark_non_differentiable(tokens) if tokens is not None else None
+        return pooled, tokens
+
+    @staticmethod
+    def backward(ctx, dpooled, _dtokens):
+        ctx.model._check_generation(ctx.stamp)
+        (fc_w,) = ctx.saved_tensors
+        m = ctx.model
+        g = dpooled.detach().to(dtype=torch.float32).contiguous()
+        w = fc_w.detach().to(dtype=torch.float32).contiguous()
+        dw, db = torch.empty_like(w), torch.empty_like(w)
+        _lib.check(_lib.lib().bvc_videomae_encoder_fc_norm_backward(m._ctx, g.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                                                    _lib.current_stream_ptr()), "bvc_videomae_encoder_fc_norm_backward")
+        return dw if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None
+
+
+class VideoMAEForVideoClassification(FlatParamModule):
+    """Drop-in for transformers.VideoMAEForVideoClassification: the embedding benchmark's inference
+    (benchmarks/compute_embeddings_videomae.py:78-96,253-264), a linear probe and full fine-tuning.
+
+    Same sub-module tree / state-dict keys as transformers: ``videomae.embeddings.*``, ``videomae.encoder.*`` (so ``adapt_videomae``'s
+    ``target.videomae.embeddings.load_state_dict(source.videomae.embeddings.state_dict())`` works against a pre-training model),
+    ``fc_norm.*`` and, for ``num_labels > 0``, ``classifier.*``.  ``forward(pixel_values, labels=None).logits`` = classifier(fc_norm(mean
+    over all tokens of the encoder output)); the reference uses ``num_labels=0`` (classifier = Identity), i.e. the logits ARE the
+    embedding.  ``labels`` adds transformers' loss (``classification_loss``).
+
+    The encoder (a flat module: its parameters and gradients are views of one buffer each) runs in the library; fc_norm and the
+    classifier are ordinary torch modules.  Which context runs (``classification_path``): in train mode with grad mode on and a trainable
+    encoder parameter, the fine-tuning context, whose every layer keeps its activations for the backward (about 36 x hidden bytes per
+    token and layer: 0.52 GB per clip at base size); otherwise the inference context, forward only through the encoder, with fc_norm's
+    gradient from the library's LayerNorm backward when fc_norm is trainable.  Both give the same logits bit for bit.
     """
+
+    _shadow_fn = "bvc_videomae_cls_shadow"
 
     def __init__(self, config: VideoMAEConfig):
         super().__init__()
@@ -291,8 +401,11 @@ class VideoMAEForVideoClassification(FlatParamModule):
             nn.init.zeros_(self.classifier.bias)
         self._ctx = None
         self._ctx_key = None
+        self._train = _TrainCtx()
+        self._warned_eval_grad = False
         self.pixel_mean, self.pixel_std = 0.5, 0.25      # for uint8 pixel_values, as in VideoMAEForPreTraining
 
+    # ---- library contexts: _ctx = inference (encode), _train.h = fine-tuning
     def _get_ctx(self, batch):
         key = (batch, self._flat.device.index)
         if self._ctx is not None and self._ctx_key[1] == key[1] and self._ctx_key[0] >= batch:
@@ -303,6 +416,30 @@ class VideoMAEForVideoClassification(FlatParamModule):
         _lib.check(_lib.lib().bvc_videomae_encoder_create(ctypes.byref(cc), batch, ctypes.byref(h)), "bvc_videomae_encoder_create")
         self._ctx, self._ctx_key = h, key
         return h
+
+    def _get_train_ctx(self, batch):
+        """Re-created when the device changes or the batch grows (VideoMAEForPreTraining._get_ctx)."""
+        t = self._train
+        key = (batch, self._flat.device.index)
+        if t.h is not None and t.key[1] == key[1] and t.key[0] >= batch:
+            return t.h
+        t.free()
+        h = ctypes.c_void_p()
+        cc = self.config.to_c()
+        _lib.check(_lib.lib().bvc_videomae_cls_create(ctypes.byref(cc), batch, ctypes.byref(h)), "bvc_videomae_cls_create")
+        t.h, t.key = h, key
+        return h
+
+    def _shadow_ctx(self):
+        return self._train.h
+
+    def __deepcopy__(self, memo):
+        # FlatParamModule's copy rebuilds the flat parameters only: fc_norm and the classifier are ordinary sub-modules
+        import copy
+        new = super().__deepcopy__(memo)
+        new.fc_norm = copy.deepcopy(self.fc_norm, memo)
+        new.classifier = copy.deepcopy(self.classifier, memo)
+        return new
 
     def _free_ctx(self):
         if self._ctx is not None:
@@ -315,10 +452,57 @@ class VideoMAEForVideoClassification(FlatParamModule):
         except Exception:
             pass
 
-    @torch.no_grad()
+    def _encoder_trainable(self):
+        return any(self._param(n).requires_grad for n in self._names)
+
+    # ---- the two paths
+    def _fc_norm_args(self, fc_w, fc_b, dev):
+        return fc_w.detach().to(device=dev, dtype=torch.float32).contiguous(), fc_b.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    def _run_encode(self, pixels, fc_w, fc_b, want_tokens):
+        cfg = self.config
+        B, dev = pixels.shape[0], pixels.device
+        fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
+        h = self._get_ctx(B)
+        w, b = self._fc_norm_args(fc_w, fc_b, dev)
+        pooled = torch.empty((B, cfg.hidden_size), dtype=torch.float32, device=dev)
+        tokens = torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev) if want_tokens else None
+        _lib.check(_lib.lib().bvc_videomae_encode_px(
+            h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
+            float(self.fc_norm.eps),
+            tokens.data_ptr() if tokens is not None else None, pooled.data_ptr(), _lib.current_stream_ptr()), "bvc_videomae_encode")
+        return pooled, tokens
+
+    def _run_train_forward(self, pixels, fc_w, fc_b, want_tokens):
+        cfg = self.config
+        B, dev = pixels.shape[0], pixels.device
+        fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
+        h = self._get_train_ctx(B)
+        w, b = self._fc_norm_args(fc_w, fc_b, dev)
+        pooled = torch.empty((B, cfg.hidden_size), dtype=torch.float32, device=dev)
+        tokens = torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev) if want_tokens else None
+        self._shadow_vouch(h)
+        _lib.check(_lib.lib().bvc_videomae_cls_forward_px(
+            h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
+            float(self.fc_norm.eps), pooled.data_ptr(), tokens.data_ptr() if tokens is not None else None, _lib.current_stream_ptr()),
+            "bvc_videomae_cls_forward")
+        self._shadow_established(h)
+        self._live = pixels       # keep the borrowed input alive until backward
+        return pooled, tokens
+
+    def _run_train_backward(self, dpooled):
+        target, accumulate = self._grad_target()
+        g = dpooled.detach().to(dtype=torch.float32).contiguous()
+        dw = torch.empty(self.config.hidden_size, dtype=torch.float32, device=g.device)
+        db = torch.empty_like(dw)
+        cb = self._bucket_callback(accumulate)
+        self._library_backward("bvc_videomae_cls_backward", _lib.lib().bvc_videomae_cls_backward(
+            self._train.h, g.data_ptr(), target.data_ptr(), dw.data_ptr(), db.data_ptr(), cb, None, _lib.current_stream_ptr()))
+        self._publish_grads(target, accumulate)
+        self._live = None
+        return dw.to(self.fc_norm.weight.dtype), db.to(self.fc_norm.bias.dtype)
+
     def forward(self, pixel_values=None, labels=None, output_last_hidden_state=False, **kwargs):
-        if labels is not None:
-            raise NotImplementedError("the classification loss / fine-tuning path is outside the pre-training hot path")
         if pixel_values is None or not pixel_values.is_cuda:
             raise _lib.BvcError("VideoMAEForVideoClassification runs on a GPU only (libbvc_hip.so has no CPU path)")
         cfg = self.config
@@ -329,18 +513,26 @@ class VideoMAEForVideoClassification(FlatParamModule):
         self._ensure_flat(dev)
         pixels = pixel_values.detach()
         pixels = (pixels if pixels.dtype == torch.uint8 else pixels.to(dtype=torch.float32)).contiguous()
-        fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
-        h = self._get_ctx(B)
-        w = self.fc_norm.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-        b = self.fc_norm.bias.detach().to(device=dev, dtype=torch.float32).contiguous()
-        pooled = torch.empty((B, cfg.hidden_size), dtype=torch.float32, device=dev)
-        tokens = torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev) if output_last_hidden_state else None
-        _lib.check(_lib.lib().bvc_videomae_encode_px(
-            h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
-            float(self.fc_norm.eps),
-            tokens.data_ptr() if tokens is not None else None, pooled.data_ptr(), _lib.current_stream_ptr()), "bvc_videomae_encode")
+        grad = torch.is_grad_enabled()
+        trainable = self._encoder_trainable()
+        fc_w, fc_b = self.fc_norm.weight, self.fc_norm.bias
+        if classification_path(self.training, grad, trainable) == "train":
+            anchor = next(self._param(n) for n in self._names if self._param(n).requires_grad)
+            pooled, tokens = _ClsTrain.apply(anchor, fc_w, fc_b, self, pixels, output_last_hidden_state)
+        else:
+            if grad and trainable and not self._warned_eval_grad:
+                self._warned_eval_grad = True
+                warnings.warn("VideoMAEForVideoClassification in eval mode: the encoder receives no gradient (call .train() to "
+                              "fine-tune it); fc_norm and the classifier still do", stacklevel=2)
+            if grad and (fc_w.requires_grad or fc_b.requires_grad):
+                pooled, tokens = _FcNormProbe.apply(fc_w, fc_b, self, pixels, output_last_hidden_state)
+            else:
+                with torch.no_grad():
+                    pooled, tokens = self._run_encode(pixels, fc_w, fc_b, output_last_hidden_state)
+                self._stamp_forward()     # a pending backward of an earlier forward must not run on overwritten state
         logits = self.classifier(pooled)
-        return ImageClassifierOutput(logits=logits, last_hidden_state=tokens)
+        loss = classification_loss(cfg, logits, labels) if labels is not None else None
+        return ImageClassifierOutput(loss=loss, logits=logits, last_hidden_state=tokens)
 
 
 # The VideoMAE (v1) pre-training shapes: (hidden, layers, heads, decoder hidden, decoder heads).  All use patch 16, tubelet 2,

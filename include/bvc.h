@@ -166,6 +166,30 @@ int bvc_videomae_encode(bvc_encoder_ctx* ctx, const float* pixels_dev, int batch
 int bvc_videomae_encode_px(bvc_encoder_ctx* ctx, const void* pixels_dev, const bvc_pixel_format* fmt, int batch,
                            const float* params_dev, const float* fc_norm_w, const float* fc_norm_b, float fc_norm_eps,
                            float* tokens_dev, float* pooled_dev, void* stream);
+/* Linear probe (encoder frozen, fc_norm trainable): dfc_norm_w / dfc_norm_b (f32 [hidden], written) of the last encode's fc_norm
+ * from dpooled_dev (f32 [batch][hidden]), with the pre-norm pooled rows and statistics that encode kept.  Fixed summation order. */
+int bvc_videomae_encoder_fc_norm_backward(bvc_encoder_ctx* ctx, const float* dpooled_dev, const float* fc_norm_w, float* dfc_norm_w,
+                                          float* dfc_norm_b, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fine-tuning: VideoMAEForVideoClassification.forward(pixel_values, labels) with autograd through the encoder.  Same parameters
+ * and the same forward as bvc_videomae_encode_px (its pooled rows are bitwise equal), but every layer keeps its activations at
+ * all batch x L tokens for the backward (about 36 x hidden bytes per token and layer).  The context owns workspaces for max_batch
+ * clips; create refuses, before allocating, a batch whose widest bf16 operand reaches 4 GiB and names the largest that fits. */
+typedef struct bvc_cls_ctx bvc_cls_ctx;
+int bvc_videomae_cls_create(const bvc_videomae_config* cfg, int max_batch, bvc_cls_ctx** out);
+void bvc_videomae_cls_destroy(bvc_cls_ctx* ctx);
+/*   pooled_dev   f32 [batch][hidden] = fc_norm(mean over tokens); fc_norm_w/b are required
+ *   tokens_dev   f32 [batch][L][hidden] last_hidden_state, or NULL                                               */
+int bvc_videomae_cls_forward_px(bvc_cls_ctx* ctx, const void* pixels_dev, const bvc_pixel_format* fmt, int batch,
+                                const float* params_dev, const float* fc_norm_w, const float* fc_norm_b, float fc_norm_eps,
+                                float* pooled_dev, float* tokens_dev, void* stream);
+/* dpooled_dev f32 [batch][hidden] -> grads_dev (the encoder's flat f32 gradients, overwritten), dfc_norm_w / dfc_norm_b (f32 [hidden],
+ * overwritten).  Gradient ranges of grads_dev are reported tail-first through on_bucket (may be NULL), as bvc_videomae_backward does. */
+int bvc_videomae_cls_backward(bvc_cls_ctx* ctx, const float* dpooled_dev, float* grads_dev, float* dfc_norm_w, float* dfc_norm_b,
+                              bvc_bucket_fn on_bucket, void* user, void* stream);
+/* as bvc_videomae_shadow (the copy covers the encoder's parameters) */
+int bvc_videomae_cls_shadow(bvc_cls_ctx* ctx, int valid, void** shadow_bf16, int64_t* numel);
 
 /* ------------------------------------------------------------------------------------------------
  * JEPA encoder and predictor (pretraining/predictive/vision_transformer.py).  Same conventions as above: flat f32

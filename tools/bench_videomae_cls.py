@@ -1,0 +1,80 @@
+"""Fine-tuning step time on one MI355X: VideoMAEForVideoClassification (train mode, labels) forward + backward + bvc.optim.AdamW step
+on synthetic 16 x 224^2 clips, every one of the 1568 tokens through the encoder.  One JSON line:
+
+    python tools/bench_videomae_cls.py --arch {small,base,large,huge} --batch B [--steps K --warmup W]
+
+Algorithmic cost per clip: forward = patch embedding 2 N D P (P = 1536 pixels per tube) + layers x (24 N D^2 + 4 N^2 D); a step
+counts the encoder 3x (forward, dX, dW) and the patch embedding 2x (forward, dW; pixels need no gradient).  VideoMAE-base:
+3.699 + 12 x 29.749 GFLOP forward, 1078.37 GFLOP per step.  `frac_peak` is against 2.5 PFLOP/s (dense bf16)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge   # noqa: E402
+
+PEAK_TFLOPS = 2500.0
+
+
+def gflop_per_clip(cfg):
+    g = cfg.image_size // cfg.patch_size
+    N = (cfg.num_frames // cfg.tubelet_size) * g * g
+    D, P = cfg.hidden_size, cfg.num_channels * cfg.tubelet_size * cfg.patch_size ** 2
+    pe = 2.0 * N * D * P
+    layer = 24.0 * N * D * D + 4.0 * N * N * D
+    return (3 * cfg.num_hidden_layers * layer + 2 * pe) / 1e9, pe / 1e9, layer / 1e9
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", default="base", choices=["small", "base", "large", "huge"])
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--num-labels", type=int, default=400)
+    args = ap.parse_args()
+    ge.build()
+    bvc = ge.load_package()
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    cfg = bvc.videomae_config(args.arch, num_labels=args.num_labels)
+    B = args.batch
+    free0 = torch.cuda.mem_get_info(dev)[0]
+    m = bvc.VideoMAEForVideoClassification(cfg).to(dev).train()
+    opt = bvc.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.05)
+    g = torch.Generator().manual_seed(1)
+    clips = torch.randint(0, 256, (B, cfg.num_frames, 3, cfg.image_size, cfg.image_size), generator=g, dtype=torch.uint8).to(dev)
+    labels = torch.randint(0, args.num_labels, (B,), generator=g).to(dev)
+
+    def step():
+        opt.zero_grad()
+        out = m(pixel_values=clips, labels=labels)
+        out.loss.backward()
+        opt.step()
+        return out.loss
+
+    for _ in range(args.warmup):
+        loss = step()
+    torch.cuda.synchronize()
+    used = free0 - torch.cuda.mem_get_info(dev)[0]
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        loss = step()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / args.steps
+    gf, pe, layer = gflop_per_clip(cfg)
+    tflops = gf * B / dt / 1e3
+    print(json.dumps({"metric": f"VideoMAE-{args.arch} fine-tuning step (forward + backward + AdamW), all tokens, bf16 operands",
+                      "arch": args.arch, "batch": B, "ms_per_step": round(1e3 * dt, 3), "clips_per_s": round(B / dt, 1),
+                      "gflop_per_clip": round(gf, 2), "gflop_patch_embed_fwd": round(pe, 3), "gflop_layer_fwd": round(layer, 3),
+                      "tflops": round(tflops, 1), "frac_peak": round(tflops / PEAK_TFLOPS, 4), "device_mem_gb": round(used / 1e9, 2),
+                      "loss": round(float(loss), 4), "finite": bool(torch.isfinite(loss).all())}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

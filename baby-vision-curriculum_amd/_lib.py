@@ -87,6 +87,23 @@ class GemmDesc(ctypes.Structure):
     ]
 
 
+class BranchDropC(ctypes.Structure):
+    """bvc_branch_drop (include/bvc.h): the gate on the two residual branches of every layer of a context"""
+    _fields_ = [("hidden_p", c_float), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("path_scale", c_void_p),
+                ("rows_per_sample", c_int)]
+
+
+def branch_drop(hidden_p, seed, offset, path_scale, rows_per_sample):
+    """A BranchDropC; path_scale = a contiguous f32 device tensor [layers][2][samples] or None."""
+    d = BranchDropC()
+    d.hidden_p = float(hidden_p)
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    d.offset = int(offset) & 0xFFFFFFFFFFFFFFFF
+    d.path_scale = path_scale.data_ptr() if path_scale is not None else None
+    d.rows_per_sample = int(rows_per_sample)
+    return d
+
+
 BUCKET_FN = ctypes.CFUNCTYPE(None, c_int64, c_int64, c_void_p)
 
 # every symbol include/bvc.h declares: name -> (restype, argtypes)
@@ -151,6 +168,16 @@ SYMBOLS = {
     "bvc_op_gemm_num_tiles": (c_int, [ctypes.POINTER(GemmDesc), c_int]),
     "bvc_op_gemm_kernel": (c_int, [ctypes.POINTER(GemmDesc), c_int, c_int, c_int, c_int, ctypes.c_char_p, c_int]),
     "bvc_op_gemm_plan_dw": (c_int, [ctypes.POINTER(GemmDesc), c_int]),
+    "bvc_op_gemm_gate": (c_int, [ctypes.POINTER(GemmDesc), ctypes.POINTER(BranchDropC), c_int, c_int, c_int, c_void_p]),
+    "bvc_op_gemm_gate_kernel": (c_int, [ctypes.POINTER(GemmDesc), c_int, ctypes.c_char_p, c_int]),
+    "bvc_op_layernorm_bwd_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_int, ctypes.POINTER(BranchDropC), c_int, c_int, c_void_p]),
+    "bvc_op_dropout_mask": (c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "bvc_dropout_mask_host": (c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "bvc_videomae_cls_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
+    "bvc_videomae_encoder_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
+    "bvc_vit_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
+    "bvc_predictor_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_op_attention_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_op_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_op_attention_bwd_part": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

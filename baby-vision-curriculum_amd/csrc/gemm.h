@@ -1,6 +1,7 @@
 // bf16 MFMA GEMM for gfx950: problem descriptors and launcher (internal to libbvc_hip.so).
 #pragma once
 #include "common.h"
+#include "dropgate.h"
 #include "../../include/bvc.h"
 
 namespace bvc {
@@ -27,7 +28,8 @@ enum GemmEpilogue {
     EPI_NCE = BVC_EPI_NCE,           // SimCLR loss partials (no C): see gemm.hip
     EPI_NCE_BWD = BVC_EPI_NCE_BWD,   // C bf16 = d loss / d (cos/T)
     EPI_RESID_LN = BVC_EPI_RESID_LN, // C f32 = resid + v + bias, C2 bf16 = LayerNorm(C) (N = 384: full rows in one tile; gemm8.hip only)
-    EPI_DLN = BVC_EPI_DLN            // LayerNorm backward fused into the dX product that feeds it (N = 384; gemm8.hip only)
+    EPI_DLN = BVC_EPI_DLN,           // LayerNorm backward fused into the dX product that feeds it (N = 384; gemm8.hip only)
+    EPI_RESID_GATE = BVC_EPI_RESID_GATE // C f32 = resid + gate .* (v + bias) (dropgate.h; gemm_gate_kernel through launch_gemm_gate only)
 };
 
 // the public descriptor IS the internal problem record (include/bvc.h)
@@ -69,6 +71,11 @@ DryRun& dry_run();
 // tile_cfg: -1 = pick from the tile count; 0 = 128x128, 1 = 128x64, 2 = 64x64.
 // stages: -1 = pick from the grid size; 2..4 = LDS ring depth (K-steps of LDS-DMA in flight + 1).
 int launch_gemm(const GemmProblem* probs, int nprob, GemmLayout layout, int tile_cfg, hipStream_t stream, int stages = -1);
+
+// One NT product with the gated residual epilogue (EPI_RESID_GATE; split_k == 1) on the 128 x 128 / 128 x 64 / 64 x 64 kernel.
+// tile_cfg: -1 = pick from the tile count, 0 / 1 / 2 as for launch_gemm.  The caller vouches that gate.path_scale (if any) holds
+// ceil(M / gate.rows) entries.
+int launch_gemm_gate(const GemmProblem& p, const Gate& gate, int tile_cfg, hipStream_t stream);
 
 // number of loss partials an EPI_LOSS problem writes with the tile config launch_gemm would pick
 int gemm_num_tiles(const GemmProblem& p, int tile_cfg);

@@ -61,6 +61,16 @@ __global__ __launch_bounds__(256, 2) void gemm_det_kernel(const GemmGroup g) {
 #include "gemm_kernel_body.inc"
 }
 
+// The gated residual product (EPI_RESID_GATE, dropgate.h): the same K loop, NT operands, one epilogue.  An instantiation of its own,
+// so that the kernels above stay what they are for every context that has no gate switched on.
+template <int BM, int BN>
+__global__ __launch_bounds__(256, 2) void gemm_gate_kernel(const GemmGroup g, const Gate gate) {
+    constexpr bool DET = false, EARLY_ = true, AT = false, BT = false;
+#define BVC_BODY_GATE 1
+#include "gemm_kernel_body.inc"
+#undef BVC_BODY_GATE
+}
+
 // ------------------------------------------------------------------ deterministic mode: workspace and fixed-order reduce
 // One pass over the slabs a gemm_det_kernel / gemm8_kernel<.., 6> launch wrote: C[m][n] = C[m][n] + slab[0][m][n] + slab[1][m][n] + ...
 // (left to right, split order) for the problems whose outputs were split or accumulating, rowsum[m] = rowsum[m] + rslab[0][m] + ... for
@@ -380,8 +390,50 @@ static int pick_gemm8(const GemmProblem* probs, int nprob, GemmLayout layout) {
     return -1;
 }
 
+template <int BM, int BN>
+static int launch_gate_one(const GemmGroup& g, const Gate& gate, int nblocks, hipStream_t stream) {
+    constexpr size_t lds = (size_t)2 * (BM + BN) * 64 * 2;
+    static_assert(lds <= 65536, "gemm_gate_kernel: dynamic LDS above 64 KiB would need the attribute");
+    if (dry_run().on) {
+        snprintf(dry_run().name, sizeof(dry_run().name), "bvc::gemm_gate_kernel<%d, %d>", BM, BN);
+        return BVC_OK;
+    }
+    hipLaunchKernelGGL((gemm_gate_kernel<BM, BN>), dim3(nblocks), dim3(256), lds, stream, g, gate);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_gemm_gate(const GemmProblem& p0, const Gate& gate, int tile_cfg, hipStream_t stream) {
+    GemmProblem p = p0;
+    p.epi = EPI_RESID_GATE;
+    BVC_REQUIRE(tile_cfg >= -1 && tile_cfg <= 2, "launch_gemm_gate: tile config %d (the gated epilogue runs on tile configs 0 / 1 / 2)", tile_cfg);
+    BVC_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "launch_gemm_gate: empty problem (%d,%d,%d)", p.M, p.N, p.K);
+    BVC_REQUIRE(p.N % 8 == 0 && p.K % 64 == 0, "launch_gemm_gate: N=%d must be a multiple of 8 and K=%d of 64", p.N, p.K);
+    BVC_REQUIRE(p.lda % 8 == 0 && p.ldb % 8 == 0 && p.ldc % 8 == 0, "launch_gemm_gate: leading dims must be multiples of 8");
+    BVC_REQUIRE(p.split_k == 1, "launch_gemm_gate: split_k must be 1");
+    BVC_REQUIRE(p.A && p.B && p.C && p.resid, "launch_gemm_gate: null operand, output or residual");
+    BVC_REQUIRE(gate.rows >= 1 && (double)p.M * p.N < 4398046511104.0, "launch_gemm_gate: bad gate (rows per sample %d) or more than 2^42 elements", gate.rows);
+    const int cfg = gemm_pick_tile(&p, 1, tile_cfg);
+    GemmGroup g;
+    g.nprob = 1;
+    g.bal_units = g.bal_lb = g.bal_tiles = 0;
+    g.accum = 0;
+    g.stagger = 0;
+    g.dbg = 0;
+    const int total = tiles_for(p, cfg);
+    for (int i = 0; i < kMaxGroup; ++i) { g.prob[i] = p; g.panel[i] = pick_panel(p, cfg, GEMM_NT); g.tile_start[i] = i == 0 ? 0 : total; }
+    g.tile_start[kMaxGroup] = total;
+    switch (cfg) {
+        case 0: return launch_gate_one<128, 128>(g, gate, total, stream);
+        case 1: return launch_gate_one<128, 64>(g, gate, total, stream);
+        default: return launch_gate_one<64, 64>(g, gate, total, stream);
+    }
+}
+
 int launch_gemm(const GemmProblem* probs, int nprob, GemmLayout layout, int tile_cfg, hipStream_t stream, int stages) {
     BVC_REQUIRE(nprob >= 1 && nprob <= kMaxGroup, "launch_gemm: nprob %d out of range", nprob);
+    for (int i = 0; i < nprob; ++i)
+        BVC_REQUIRE(probs[i].epi != EPI_RESID_GATE, "launch_gemm: BVC_EPI_RESID_GATE needs its gate (bvc_op_gemm_gate / a context with bvc_*_set_drop)");
     static thread_local bool skip_g8 = false;      // set while an auto-picked gemm8 launch that turned the problem down is re-planned
     bool auto_g8 = false;
     if (probs[0].epi == EPI_RESID_LN || probs[0].epi == EPI_DLN) {

@@ -1,6 +1,11 @@
 // Body of gemm_kernel / gemm_det_kernel (gemm.hip), included inside each: one source for the two kernels, each with its own kernel
 // argument `g` (a helper function taking the group would copy it to scratch, dynamically indexed).  Expects BM, BN, AT, BT, EARLY_
-// and DET in scope.
+// and DET in scope.  With BVC_BODY_GATE defined (gemm_gate_kernel) the one epilogue is EPI_RESID_GATE and a `Gate gate` is in scope.
+#ifdef BVC_BODY_GATE
+#define BVC_IS_RESID(e) ((e) == EPI_RESID_GATE)
+#else
+#define BVC_IS_RESID(e) ((e) == EPI_RESID)
+#endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BK = 64;
     constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_BYTES;
@@ -179,7 +184,11 @@
     // per instruction and the write path reaches only ~2.2 TB/s (measured).  Instead every wave parks its f32 tile in
     // LDS (free after the K loop; XOR-swizzled 16-B units, no bank conflicts) and re-reads it row-major, so each lane
     // owns 8 consecutive columns and every global load / store of the epilogue is a full 128-B line per 8 lanes.
+#ifdef BVC_BODY_GATE
+    constexpr int epi = EPI_RESID_GATE;
+#else
     const int epi = p.epi;
+#endif
     const float alpha = p.alpha_dev ? p.alpha * p.alpha_dev[0] : p.alpha;
     float sumsq = 0.f, possum = 0.f;
     const bool atomic = p.split_k > 1;
@@ -232,7 +241,7 @@
             bias1 = *reinterpret_cast<const f32x4*>(p.bias + n + 4);
         }
         f32x4 side0[NCH], side1[NCH];     // f32 addend (residual / positional row / labels) or the 4 dwords of the bf16 aux row
-        const bool side_f32 = (epi == EPI_RESID && !atomic) || epi == EPI_POS || epi == EPI_E2D || epi == EPI_LOSS;
+        const bool side_f32 = (BVC_IS_RESID(epi) && !atomic) || epi == EPI_POS || epi == EPI_E2D || epi == EPI_LOSS;
         const bool side_aux = epi == EPI_DGELU || epi == EPI_DRELU;
         if (side_f32 || side_aux) {
 #pragma unroll
@@ -244,7 +253,7 @@
                 if (side_aux) {
                     side0[it] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const bf16_t*>(p.aux) + (size_t)m * p.ldaux + n);
                 } else {
-                    const float* src = epi == EPI_RESID ? p.resid + (size_t)m * p.ldc + n
+                    const float* src = BVC_IS_RESID(epi) ? p.resid + (size_t)m * p.ldc + n
                                      : epi == EPI_LOSS  ? p.labels + (size_t)m * p.ldc + n
                                                         : p.pos + (size_t)p.rowtok[m] * p.N + n;
                     side0[it] = *reinterpret_cast<const f32x4*>(src);
@@ -366,6 +375,17 @@
                     }
                     store_bf16(p.C, idx, w);
                 } break;
+#ifdef BVC_BODY_GATE
+                case EPI_RESID_GATE: {   // C f32 = resid + gate .* (v + bias): the gate multiplies the branch before the residual is added
+                    const uint64_t q = ((uint64_t)m * p.N + n) >> 2;
+                    const f32x4 g0 = gate_apply4(gate, m, q, f32x4{v[0], v[1], v[2], v[3]});
+                    const f32x4 g1 = gate_apply4(gate, m, q + 1, f32x4{v[4], v[5], v[6], v[7]});
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { v[e] = g0[e]; v[4 + e] = g1[e]; }
+                    add_side();
+                    store_f32(reinterpret_cast<float*>(p.C) + idx);
+                } break;
+#endif
                 default: break;
             }
         }
@@ -400,3 +420,4 @@
         __syncthreads();
         if (tid == 0) p.partial[tile] = (red[0] + red[1]) + (red[2] + red[3]);
     }
+#undef BVC_IS_RESID

@@ -115,6 +115,7 @@ struct bvc_vit_ctx {
     float *meanf, *rstdf;
     bf16_t* dout_bf;   // bf16 [B*N][D]
     float* dres;
+    DropState drop;    // bvc_vit_set_drop
 };
 
 struct bvc_pred_ctx {
@@ -136,6 +137,7 @@ struct bvc_pred_ctx {
     bf16_t* dout_bf;   // bf16 [nsets*B*Np][D]
     float* dres;       // f32 [nsets*B*(Nc+Np)][Dp]
     bf16_t* dxe;       // bf16 [B*Nc][Dp]
+    DropState drop;    // bvc_predictor_set_drop
 };
 
 extern "C" {
@@ -181,6 +183,7 @@ int bvc_vit_create(const bvc_vit_config* cfg, int max_batch, bvc_vit_ctx** out) 
     A(c->arena.alloc(&c->idx_all, M));
     A(c->arena.alloc(&c->Ape, M * c->Kp));
     A(alloc_stack(c->arena, c->st, D, I, H, cfg->depth, cfg->eps, M, (size_t)max_batch * H * c->L));
+    A(alloc_drop(c->arena, c->drop, cfg->depth, max_batch));
     A(c->arena.alloc(&c->meanf, M));
     A(c->arena.alloc(&c->rstdf, M));
     A(c->arena.alloc(&c->dout_bf, M * D));
@@ -225,6 +228,8 @@ int bvc_vit_forward_px(bvc_vit_ctx* c, const void* imgs_any, const bvc_pixel_for
     c->batch = B; c->ntok = N;
     c->idx = idx ? idx : c->idx_all;
     c->w.params = params; c->w.wbf = c->wbf;
+    c->w.drop = &c->drop;
+    TRY(take_drop(c->drop, B, N, "vit_forward"));
     const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
     if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.total, st));     // see bvc_vit_shadow
     c->shadow_valid = false;
@@ -252,6 +257,11 @@ int bvc_vit_shadow(bvc_vit_ctx* c, int valid, void** shadow_bf16, int64_t* numel
     return BVC_OK;
 }
 
+int bvc_vit_set_drop(bvc_vit_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
+    BVC_REQUIRE(c, "vit_set_drop: null context");
+    return set_drop(c->drop, drop, samples, "vit_set_drop", (hipStream_t)stream);
+}
+
 int bvc_vit_backward(bvc_vit_ctx* c, const float* dout, float* G, bvc_bucket_fn on_bucket, void* user, void* stream) {
     BVC_REQUIRE(c && dout && G, "vit_backward: null argument");
     if (!c->have_forward) { set_error("vit_backward: no forward state"); return BVC_ERR_STATE; }
@@ -263,8 +273,9 @@ int bvc_vit_backward(bvc_vit_ctx* c, const float* dout, float* G, bvc_bucket_fn 
     begin_backward(c->w);
     BVC_CHECK_HIP(hipMemsetAsync(G, 0, (size_t)L.total * 4, st));
     TRY(launch_gather_rows_bf16(dout, identity_rows(), c->dout_bf, M, D, st));
+    Gate gtop;     // (the first bf16 copy feeds the last block's MLP branch: gated here when the context has a gate on)
     TRY(launch_ln_bwd(c->dout_bf, c->st.x_out, identity_rows(), c->meanf, c->rstdf, params + L.norm_w, c->dres, 0, c->w.dyb[0],
-                      G + L.norm_w, G + L.norm_b, c->w.ln_part, M, D, st));
+                      G + L.norm_w, G + L.norm_b, c->w.ln_part, M, D, st, top_gate(c->drop, gtop)));
     if (on_bucket) on_bucket(L.norm_w, L.total - L.norm_w, user);
     for (int i = c->st.nlayers - 1; i >= 0; --i)
         TRY(layer_backward(c->w, c->st, i, L.blocks[i], c->st.act[i].x_in, c->dres, G, B, N, st, on_bucket, user));
@@ -320,6 +331,7 @@ int bvc_predictor_create(const bvc_predictor_config* cfg, int max_batch, int max
     A(c->arena.alloc(&c->z_bf, Mc * D));
     A(c->arena.alloc(&c->xe, Mc * Dp));
     A(alloc_stack(c->arena, c->st, Dp, I, H, cfg->depth, cfg->eps, M, S * H * max_tokens));
+    A(alloc_drop(c->arena, c->drop, cfg->depth, (int)S));
     A(c->arena.alloc(&c->meanf, M));
     A(c->arena.alloc(&c->rstdf, M));
     A(c->arena.alloc(&c->lnf, M * Dp));
@@ -349,6 +361,8 @@ int bvc_predictor_forward(bvc_pred_ctx* c, const float* z, const int* idx_ctx, c
     c->B = B; c->Nc = Nc; c->Np = Np; c->nsets = nsets;
     c->idx_ctx = idx_ctx; c->idx_pred = idx_pred;
     c->w.params = params; c->w.wbf = c->wbf;
+    c->w.drop = &c->drop;
+    TRY(take_drop(c->drop, S, T, "predictor_forward"));
     if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.total, st));     // see bvc_predictor_shadow
     c->shadow_valid = false;
     TRY(launch_gather_rows_bf16(z, identity_rows(), c->z_bf, Mc, D, st));
@@ -380,6 +394,11 @@ int bvc_predictor_shadow(bvc_pred_ctx* c, int valid, void** shadow_bf16, int64_t
     if (numel) *numel = (int64_t)c->lay.total;
     if (valid >= 0) c->shadow_valid = valid != 0;
     return BVC_OK;
+}
+
+int bvc_predictor_set_drop(bvc_pred_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
+    BVC_REQUIRE(c, "predictor_set_drop: null context");
+    return set_drop(c->drop, drop, samples, "predictor_set_drop", (hipStream_t)stream);
 }
 
 int bvc_predictor_backward(bvc_pred_ctx* c, const float* dout, float* G, float* dz, void* stream) {
@@ -415,8 +434,9 @@ int bvc_predictor_backward_cb(bvc_pred_ctx* c, const float* dout, float* G, floa
     BVC_CHECK_HIP(hipMemsetAsync(c->dres, 0, (size_t)M * Dp * 4, st));        // context rows get no gradient from the output slice
     BVC_CHECK_HIP(hipMemsetAsync(c->w.dyb[0], 0, (size_t)M * Dp * 2, st));
     const RowMap tail{Np, T, Nc};
+    Gate gtop;
     TRY(launch_ln_bwd(c->w.dln, c->st.x_out, tail, c->meanf, c->rstdf, params + L.norm_w, c->dres, 0, c->w.dyb[0],
-                      G + L.norm_w, G + L.norm_b, c->w.ln_part, Mo, Dp, st));
+                      G + L.norm_w, G + L.norm_b, c->w.ln_part, Mo, Dp, st, top_gate(c->drop, gtop)));
     if (on_bucket) on_bucket(L.norm_w, L.total - L.norm_w, user);
     for (int i = c->st.nlayers - 1; i >= 0; --i)
         TRY(layer_backward(c->w, c->st, i, L.blocks[i], c->st.act[i].x_in, c->dres, G, S, T, st, on_bucket, user));

@@ -1,6 +1,7 @@
 // HBM-bound row / element kernels (internal to libbvc_hip.so).
 #pragma once
 #include "common.h"
+#include "dropgate.h"
 
 namespace bvc {
 
@@ -29,7 +30,8 @@ int launch_ln_fwd(const float* x, RowMap rm, const float* gamma, const float* be
 size_t ln_bwd_workspace_floats(int M, int D);
 size_t ln_bwd_workspace_floats_upto(int Mmax, int D);
 int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean, const float* rstd, const float* gamma,
-                  float* dres, int accumulate, bf16_t* dres_bf, float* dgamma, float* dbeta, float* part, int M, int D, hipStream_t s);
+                  float* dres, int accumulate, bf16_t* dres_bf, float* dgamma, float* dbeta, float* part, int M, int D, hipStream_t s,
+                  const Gate* gate = nullptr);     // gate: dres_bf = bf16(gate .* dres) (ln_bwd_gate_kernel), dres itself ungated
 // dgamma[c] += sum_b part[b][0][c], dbeta[c] += sum_b part[b][1][c] over nblk partial rows of [2][D] floats (what ln_bwd and the fused
 // LayerNorm-backward epilogue of gemm8.hip leave behind)
 int launch_ln_param_reduce(const float* part, int nblk, int D, float* dgamma, float* dbeta, hipStream_t s);
@@ -42,7 +44,10 @@ int launch_token_mean_bwd(const float* dmean, int B, int N, int D, float* dx, hi
 // dgamma / dbeta (written, not accumulated) and, unless dres is nullptr, d/dx broadcast to all N token rows of each clip as f32
 // dres [B*N][D] and its bf16 copy dres_bf
 int launch_fcnorm_bwd_bcast(const float* dy, const float* p, const float* mean, const float* rstd, const float* gamma, float* dres,
-                            bf16_t* dres_bf, float* dgamma, float* dbeta, int B, int N, int D, hipStream_t s);
+                            bf16_t* dres_bf, float* dgamma, float* dbeta, int B, int N, int D, hipStream_t s, const Gate* gate = nullptr);
+// out[e] = 1 where element e of the gate's element mask is kept (n = M * N elements, row-major), on the device and on the host
+int launch_dropout_mask(const Gate& gate, size_t n, uint8_t* out, hipStream_t s);
+void dropout_mask_host(const Gate& gate, size_t n, uint8_t* out);
 int launch_cast_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int launch_gather_rows_bf16(const float* in, RowMap rm, bf16_t* out, int M, int D, hipStream_t s);
 int launch_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, hipStream_t s);

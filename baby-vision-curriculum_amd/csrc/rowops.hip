@@ -81,12 +81,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // per-workgroup partials of dgamma = sum_rows dy * xhat and dbeta = sum_rows dy go to part[block][2][D]
 // (every workgroup hammering the same D addresses with atomics serialises: measured 2x on the kernel);
 // ln_param_reduce_kernel folds them into the gradients
-template <int RPB, int LPR, int NC>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x, RowMap rm,
-                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                     const float* __restrict__ gamma, float* __restrict__ dres,
-                                                     int accumulate, bf16_t* __restrict__ dres_bf, float* __restrict__ part,
-                                                     int M, int D) {
+// GATED: the bf16 copy alone is multiplied by the gate of the residual branch it feeds (dropgate.h; element index = physical row * D +
+// column); dres itself, the residual gradient, passes ungated.
+template <int RPB, int LPR, int NC, bool GATED>
+__device__ __forceinline__ void ln_bwd_body(const bf16_t* __restrict__ dy, const float* __restrict__ x, RowMap rm,
+                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                            const float* __restrict__ gamma, float* __restrict__ dres,
+                                            int accumulate, bf16_t* __restrict__ dres_bf, float* __restrict__ part,
+                                            int M, int D, const Gate& gate) {
     // per-wave (per half-wave for LPR = 32) column partials, [4 RPW][dgamma | dbeta][D]: sized by D at launch (a static 32 KiB array
     // capped the kernel at 5 workgroups per CU; at D = 384 this is 24 KiB and the register budget decides: 6-7)
     extern __shared__ __attribute__((aligned(16))) float red[];
@@ -148,7 +150,15 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
                 f32x4 dx = (g[i] - s1 - xh[i] * s2) * rs;
                 if (accumulate) dx += dr[c];
                 dr[c] = dx;
-                if (db16) db16[c] = uint2{pack2bf(dx[0], dx[1]), pack2bf(dx[2], dx[3])};
+                if constexpr (GATED) {
+                    if (db16) {
+                        const int prow = map_row(mc, rm);
+                        const f32x4 w = gate_apply4(gate, prow, (uint64_t)prow * nch + c, dx);
+                        db16[c] = uint2{pack2bf(w[0], w[1]), pack2bf(w[2], w[3])};
+                    }
+                } else {
+                    if (db16) db16[c] = uint2{pack2bf(dx[0], dx[1]), pack2bf(dx[2], dx[3])};
+                }
             }
         }
     }
@@ -171,6 +181,23 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
         pg[col] = a;
         pg[D + col] = b;
     }
+}
+
+template <int RPB, int LPR, int NC>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x, RowMap rm,
+                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                     const float* __restrict__ gamma, float* __restrict__ dres,
+                                                     int accumulate, bf16_t* __restrict__ dres_bf, float* __restrict__ part,
+                                                     int M, int D) {
+    ln_bwd_body<RPB, LPR, NC, false>(dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, Gate{});
+}
+template <int RPB, int LPR, int NC>
+__global__ __launch_bounds__(256) void ln_bwd_gate_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x, RowMap rm,
+                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                          const float* __restrict__ gamma, float* __restrict__ dres,
+                                                          int accumulate, bf16_t* __restrict__ dres_bf, float* __restrict__ part,
+                                                          int M, int D, const Gate gate) {
+    ln_bwd_body<RPB, LPR, NC, true>(dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, gate);
 }
 
 // dgamma[c] += sum_b part[b][0][c], dbeta[c] += sum_b part[b][1][c]; grid (ceil(2D/256), ceil(nblk/16))
@@ -366,11 +393,12 @@ __global__ void token_mean_bwd_kernel(const float* __restrict__ dmean, float* __
 // (dres_bf) the last encoder layer's backward reads.  Workgroups of row y == pblk write dgamma = sum_b dy * xhat and dbeta = sum_b dy for
 // 256 columns each, over the B rows in order: the same bits on every run.  dres == nullptr (pblk = 0): the parameter gradients only.
 constexpr int kFcRows = 32;
-__global__ __launch_bounds__(256) void fcnorm_bwd_bcast_kernel(const float* __restrict__ dy, const float* __restrict__ p,
-                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                               const float* __restrict__ gamma, float* __restrict__ dres,
-                                                               bf16_t* __restrict__ dres_bf, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta, int B, int N, int D, int pblk) {
+template <bool GATED>     // GATED: the bf16 copy is multiplied by the gate of the last layer's MLP branch (dropgate.h), as in ln_bwd_body
+__device__ __forceinline__ void fcnorm_bwd_bcast_body(const float* __restrict__ dy, const float* __restrict__ p,
+                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                      const float* __restrict__ gamma, float* __restrict__ dres,
+                                                      bf16_t* __restrict__ dres_bf, float* __restrict__ dgamma,
+                                                      float* __restrict__ dbeta, int B, int N, int D, int pblk, const Gate& gate) {
     const int b = blockIdx.y;
     if (b == pblk) {
         const int d = blockIdx.x * 256 + threadIdx.x;
@@ -417,8 +445,39 @@ __global__ __launch_bounds__(256) void fcnorm_bwd_bcast_kernel(const float* __re
         const f32x4 v = *reinterpret_cast<const f32x4*>(dps + c * 4);
         const size_t o = base + (size_t)r * D + (size_t)c * 4;
         *reinterpret_cast<f32x4*>(dres + o) = v;
-        *reinterpret_cast<uint2*>(dres_bf + o) = uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+        if constexpr (GATED) {
+            const f32x4 w = gate_apply4(gate, b * N + r0 + r, (uint64_t)(o >> 2), v);
+            *reinterpret_cast<uint2*>(dres_bf + o) = uint2{pack2bf(w[0], w[1]), pack2bf(w[2], w[3])};
+        } else {
+            *reinterpret_cast<uint2*>(dres_bf + o) = uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+        }
     }
+}
+__global__ __launch_bounds__(256) void fcnorm_bwd_bcast_kernel(const float* __restrict__ dy, const float* __restrict__ p,
+                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                               const float* __restrict__ gamma, float* __restrict__ dres,
+                                                               bf16_t* __restrict__ dres_bf, float* __restrict__ dgamma,
+                                                               float* __restrict__ dbeta, int B, int N, int D, int pblk) {
+    fcnorm_bwd_bcast_body<false>(dy, p, mean, rstd, gamma, dres, dres_bf, dgamma, dbeta, B, N, D, pblk, Gate{});
+}
+__global__ __launch_bounds__(256) void fcnorm_bwd_bcast_gate_kernel(const float* __restrict__ dy, const float* __restrict__ p,
+                                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                    const float* __restrict__ gamma, float* __restrict__ dres,
+                                                                    bf16_t* __restrict__ dres_bf, float* __restrict__ dgamma,
+                                                                    float* __restrict__ dbeta, int B, int N, int D, int pblk, const Gate gate) {
+    fcnorm_bwd_bcast_body<true>(dy, p, mean, rstd, gamma, dres, dres_bf, dgamma, dbeta, B, N, D, pblk, gate);
+}
+
+// ============================================================================ dropout mask (what the gates above apply, made visible)
+// out[e] = 1 where element e of the (layer, branch) mask is KEPT; one thread per four elements, any M x N
+__global__ __launch_bounds__(256) void dropout_mask_kernel(const Gate gate, size_t n, uint8_t* __restrict__ out) {
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q * 4 >= n) return;
+    uint32_t r[4];
+    gate_draws(gate, q, r);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (q * 4 + e < n) out[q * 4 + e] = r[e] >= gate.thr ? 1 : 0;
 }
 
 // ============================================================================ elementwise
@@ -1295,7 +1354,8 @@ size_t ln_bwd_workspace_floats_upto(int Mmax, int D) {
 }
 
 int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean, const float* rstd, const float* gamma,
-                  float* dres, int accumulate, bf16_t* dres_bf, float* dgamma, float* dbeta, float* part, int M, int D, hipStream_t s) {
+                  float* dres, int accumulate, bf16_t* dres_bf, float* dgamma, float* dbeta, float* part, int M, int D, hipStream_t s,
+                  const Gate* gate) {
     BVC_REQUIRE(D % 4 == 0 && D <= kWideChunks * 256, "ln_bwd: D=%d unsupported", D);
     BVC_REQUIRE(part != nullptr, "ln_bwd: workspace missing");
     // rows per workgroup: enough workgroups to keep >= 16 waves per CU streaming (the kernel is HBM-bound and
@@ -1306,10 +1366,18 @@ int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean
     const bool half = ln_half_wave_rows(D);
     const size_t lds = (size_t)(half ? 16 : 8) * D * sizeof(float);
 #define BVC_LN_BWD(RPB_, LPR_, NC_) hipLaunchKernelGGL((ln_bwd_kernel<RPB_, LPR_, NC_>), dim3(nblk), dim3(256), lds, s, dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D)
-    if (D > kMaxChunks * 256) { if (rpb == 16) BVC_LN_BWD(16, 64, kWideChunks); else BVC_LN_BWD(4, 64, kWideChunks); }
+#define BVC_LN_BWD_G(RPB_, LPR_, NC_) hipLaunchKernelGGL((ln_bwd_gate_kernel<RPB_, LPR_, NC_>), dim3(nblk), dim3(256), lds, s, dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, *gate)
+    if (gate) {      // the same grid and instantiation choice, the bf16 copy gated
+        BVC_REQUIRE(dres_bf && gate->rows >= 1 && (double)M * D < 4398046511104.0, "ln_bwd: a gate needs the bf16 copy and rows per sample >= 1");
+        if (D > kMaxChunks * 256) { if (rpb == 16) BVC_LN_BWD_G(16, 64, kWideChunks); else BVC_LN_BWD_G(4, 64, kWideChunks); }
+        else if (rpb == 16) { if (half) BVC_LN_BWD_G(16, 32, kMaxChunks); else BVC_LN_BWD_G(16, 64, kMaxChunks); }
+        else { if (half) BVC_LN_BWD_G(8, 32, kMaxChunks); else BVC_LN_BWD_G(4, 64, kMaxChunks); }
+    }
+    else if (D > kMaxChunks * 256) { if (rpb == 16) BVC_LN_BWD(16, 64, kWideChunks); else BVC_LN_BWD(4, 64, kWideChunks); }
     else if (rpb == 16) { if (half) BVC_LN_BWD(16, 32, kMaxChunks); else BVC_LN_BWD(16, 64, kMaxChunks); }
     else { if (half) BVC_LN_BWD(8, 32, kMaxChunks); else BVC_LN_BWD(4, 64, kMaxChunks); }
 #undef BVC_LN_BWD
+#undef BVC_LN_BWD_G
     BVC_CHECK_HIP(hipGetLastError());
     return launch_ln_param_reduce(part, nblk, D, dgamma, dbeta, s);
 }
@@ -1382,8 +1450,23 @@ int launch_token_mean_bwd(const float* dmean, int B, int N, int D, float* dx, hi
     return BVC_OK;
 }
 
+int launch_dropout_mask(const Gate& gate, size_t n, uint8_t* out, hipStream_t s) {
+    BVC_REQUIRE(out && n > 0 && (double)n < 4398046511104.0, "dropout_mask: bad argument");
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(blocks_for((n + 3) / 4)), dim3(256), 0, s, gate, n, out);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+void dropout_mask_host(const Gate& gate, size_t n, uint8_t* out) {
+    for (size_t q = 0; q * 4 < n; ++q) {
+        uint32_t r[4];
+        gate_draws(gate, q, r);
+        for (int e = 0; e < 4 && q * 4 + e < n; ++e) out[q * 4 + e] = r[e] >= gate.thr ? 1 : 0;
+    }
+}
+
 int launch_fcnorm_bwd_bcast(const float* dy, const float* p, const float* mean, const float* rstd, const float* gamma, float* dres,
-                            bf16_t* dres_bf, float* dgamma, float* dbeta, int B, int N, int D, hipStream_t s) {
+                            bf16_t* dres_bf, float* dgamma, float* dbeta, int B, int N, int D, hipStream_t s, const Gate* gate) {
     BVC_REQUIRE(dy && p && mean && rstd && gamma && dgamma && dbeta && B >= 1 && N >= 1, "fcnorm_bwd_bcast: bad argument");
     BVC_REQUIRE(D % 4 == 0 && D <= 1536, "fcnorm_bwd_bcast: D=%d unsupported (a multiple of 4 up to 1536)", D);
     BVC_REQUIRE((dres == nullptr) == (dres_bf == nullptr), "fcnorm_bwd_bcast: dres and its bf16 copy go together");
@@ -1393,8 +1476,14 @@ int launch_fcnorm_bwd_bcast(const float* dy, const float* p, const float* mean, 
                            B, N, D, 0);
     } else {
         const int chunks = (N + kFcRows - 1) / kFcRows;
-        hipLaunchKernelGGL(fcnorm_bwd_bcast_kernel, dim3(std::max(chunks, pcols), B + 1), dim3(256), 0, s, dy, p, mean, rstd, gamma, dres,
-                           dres_bf, dgamma, dbeta, B, N, D, B);
+        if (gate) {
+            BVC_REQUIRE(gate->rows == N, "fcnorm_bwd_bcast: the gate's rows per sample (%d) must be the token count %d", gate->rows, N);
+            hipLaunchKernelGGL(fcnorm_bwd_bcast_gate_kernel, dim3(std::max(chunks, pcols), B + 1), dim3(256), 0, s, dy, p, mean, rstd, gamma, dres,
+                               dres_bf, dgamma, dbeta, B, N, D, B, *gate);
+        } else {
+            hipLaunchKernelGGL(fcnorm_bwd_bcast_kernel, dim3(std::max(chunks, pcols), B + 1), dim3(256), 0, s, dy, p, mean, rstd, gamma, dres,
+                               dres_bf, dgamma, dbeta, B, N, D, B);
+        }
     }
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;

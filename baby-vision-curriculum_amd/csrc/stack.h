@@ -96,6 +96,10 @@ struct Work {
     int seq = 0;
     bool join_pending[2] = {false, false};
     int64_t pend_lo[2], pend_hi[2];
+    // Gate on the residual branches (dropgate.h): nullptr / inactive = none, and layer_forward / layer_backward launch what they
+    // always launched.  drop_layer >= 0 overrides the layer index the gate is keyed by (a context that reuses one LayerAct).
+    const DropState* drop = nullptr;
+    int drop_layer = -1;
 };
 
 // the head width a stack runs attention at (attention.hip): 80 / 88 in place unless bvc_set_option("head_pad", 1) asks for the
@@ -122,6 +126,17 @@ int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_i
                   const LayerOff* next = nullptr);
 // Do the LayerNorms of this stack run inside the epilogues of the 384-wide products next to them (gemm8.hip, EPI_RESID_LN / EPI_DLN)?
 bool fuse_row_ln(const Stack& s, int M);
+// bvc_*_set_drop: validates the public description and copies path_scale ([nlayers][2][samples], device) into the context's buffer
+int set_drop(DropState& d, const bvc_branch_drop* drop, int samples, const char* who, hipStream_t st);
+int alloc_drop(Arena& a, DropState& d, int nlayers, int max_samples);
+// a forward takes the armed state (one forward and its backward); checks it against the call's row groups
+int take_drop(DropState& d, int samples, int rows, const char* who);
+// the gate the producer of a stack's first backward bf16 copy applies (the last layer's MLP branch), or nullptr
+inline const Gate* top_gate(const DropState& d, Gate& store) {
+    if (!d.active) return nullptr;
+    store = d.gate(d.nlayers - 1, 1);
+    return &store;
+}
 int layer_backward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* dres, float* G, int B, int N,
                    hipStream_t st, bvc_bucket_fn on_bucket, void* user);
 

@@ -250,6 +250,42 @@ bool fuse_row_ln(const Stack& s, int M) {
     return M >= 128 * 128;     // (16 clips of 1568 tokens = 196 units: -0.5 %; 32: -1.3 %; 64: -1.3 %; 128: -2.0 %; 256: -2.2 % of the step)
 }
 
+int alloc_drop(Arena& a, DropState& d, int nlayers, int max_samples) {
+    d.nlayers = nlayers;
+    d.max_samples = max_samples;
+    return a.alloc(&d.path_scale, (size_t)nlayers * 2 * max_samples);
+}
+
+int set_drop(DropState& d, const bvc_branch_drop* drop, int samples, const char* who, hipStream_t st) {
+    d.armed = false;
+    if (!drop || (drop->hidden_p == 0.f && drop->path_scale == nullptr)) return BVC_OK;      // off
+    BVC_REQUIRE(drop->hidden_p >= 0.f && drop->hidden_p < 1.f, "%s: hidden_p %g outside [0, 1)", who, (double)drop->hidden_p);
+    BVC_REQUIRE(samples >= 1 && samples <= d.max_samples, "%s: %d samples outside [1, %d]", who, samples, d.max_samples);
+    BVC_REQUIRE(drop->rows_per_sample >= 1, "%s: rows_per_sample must be >= 1", who);
+    d.hidden_p = drop->hidden_p;
+    d.seed = drop->seed;
+    d.offset = drop->offset;
+    d.samples = samples;
+    d.rows = drop->rows_per_sample;
+    d.has_path = drop->path_scale != nullptr;
+    if (d.has_path)
+        BVC_CHECK_HIP(hipMemcpyAsync(d.path_scale, drop->path_scale, (size_t)d.nlayers * 2 * samples * sizeof(float), hipMemcpyDeviceToDevice, st));
+    d.armed = true;
+    return BVC_OK;
+}
+
+int take_drop(DropState& d, int samples, int rows, const char* who) {
+    d.active = d.armed;
+    d.armed = false;
+    if (!d.active) return BVC_OK;
+    if (d.samples != samples || d.rows != rows) {
+        d.active = false;
+        set_error("%s: the gate was set for %d samples of %d rows, the call has %d of %d", who, d.samples, d.rows, samples, rows);
+        return BVC_ERR_INVALID;
+    }
+    return BVC_OK;
+}
+
 int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* x_out, int B, int N, hipStream_t st,
                   const LayerOff* next) {
     LayerAct& a = s.act[li];
@@ -257,7 +293,10 @@ int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_i
     const float* P = w.params;
     const bf16_t* W = w.wbf;
     const float eps = s.eps;
-    const bool fuse = fuse_row_ln(s, M);
+    // a gate on the branches: both branch products take the gated epilogue of the 128 x 128 kernel, the LayerNorms run as separate passes
+    const bool gated = w.drop != nullptr && w.drop->active;
+    const int gl = w.drop_layer >= 0 ? w.drop_layer : li;
+    const bool fuse = !gated && fuse_row_ln(s, M);
     if (li == 0) s.ln1_ready = false;
     // (the previous layer's fc2 epilogue may have left this layer's first LayerNorm behind)
     if (!(fuse && s.ln1_ready)) TRY(launch_ln_fwd(x_in, identity_rows(), P + o.ln1w, P + o.ln1b, a.ln1o, a.mean1, a.rstd1, M, D, eps, st));
@@ -281,7 +320,8 @@ int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_i
         GemmProblem p = gemm(a.ctx, (size_t)M * Da, Da, Wo, (size_t)D * Da, Da, M, D, Da, fuse ? EPI_RESID_LN : EPI_RESID, a.h, D);
         p.bias = P + o.bo; p.resid = x_in;
         if (fuse) { p.C2 = a.ln2o; p.ln_gamma = P + o.ln2w; p.ln_beta = P + o.ln2b; p.ln_mean = a.mean2; p.ln_rstd = a.rstd2; p.ln_eps = eps; }
-        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
+        if (gated) TRY(launch_gemm_gate(p, w.drop->gate(gl, 0), -1, st));
+        else TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
     if (!fuse) TRY(launch_ln_fwd(a.h, identity_rows(), P + o.ln2w, P + o.ln2b, a.ln2o, a.mean2, a.rstd2, M, D, eps, st));
     {
@@ -297,7 +337,8 @@ int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_i
             LayerAct& an = s.act[li + 1];
             p.C2 = an.ln1o; p.ln_gamma = P + next->ln1w; p.ln_beta = P + next->ln1b; p.ln_mean = an.mean1; p.ln_rstd = an.rstd1; p.ln_eps = eps;
         }
-        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
+        if (gated) TRY(launch_gemm_gate(p, w.drop->gate(gl, 1), -1, st));
+        else TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
         s.ln1_ready = fuse_next;
     }
     return BVC_OK;
@@ -333,7 +374,13 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
         p.aux = a.pre; p.ldaux = I;
         TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
     }
-    const bool fuse = fuse_row_ln(s, M);
+    // Gated branches (dropgate.h): dres passes ungated; the bf16 copies that feed a branch are gated where they are produced - dhb by this
+    // layer's attention gate, the next step's dyb by the MLP gate of the layer below (the copy after layer 0 feeds the patch
+    // embedding: ungated).  The weight and bias gradients then need no change.
+    const bool gated = c_.drop != nullptr && c_.drop->active;
+    Gate g_attn, g_below;
+    if (gated) { g_attn = c_.drop->gate(li, 0); if (li > 0) g_below = c_.drop->gate(li - 1, 1); }
+    const bool fuse = !gated && fuse_row_ln(s, M);
     if (fuse) {      // dX of fc1 with the second LayerNorm's backward in its epilogue: dres += ..., dhb = bf16(dres), dgamma / dbeta
         GemmProblem p = gemm(dh, (size_t)M * I, I, W + o.w1, (size_t)I * D, D, M, D, I, EPI_DLN, dres, D);
         p.C2 = dhb; p.ln_x = a.h; p.ln_mean = a.mean2; p.ln_rstd = a.rstd2; p.ln_gamma = P + o.ln2w;
@@ -342,7 +389,8 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
     } else {
         GemmProblem p = gemm(dh, (size_t)M * I, I, W + o.w1, (size_t)I * D, D, M, D, I, EPI_BF16, c_.dln, D);
         TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
-        TRY(launch_ln_bwd(c_.dln, a.h, identity_rows(), a.mean2, a.rstd2, P + o.ln2w, dres, 1, dhb, G + o.ln2w, G + o.ln2b, c_.ln_part, M, D, st));
+        TRY(launch_ln_bwd(c_.dln, a.h, identity_rows(), a.mean2, a.rstd2, P + o.ln2w, dres, 1, dhb, G + o.ln2w, G + o.ln2b, c_.ln_part, M, D, st,
+                          gated ? &g_attn : nullptr));
     }
     // attention
     const int Da = s.Da;
@@ -394,7 +442,8 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
         if (pad)
             TRY(launch_unpad_head_grads(s.gwqkv_pad, s.gbqkv_pad, s.gwo_pad, G + o.wqkv, G + o.bqkv, G + o.wo, D, s.H, s.hd, s.hdp, ws));
     }
-    if (!fuse) TRY(launch_ln_bwd(c_.dln, x_in, identity_rows(), a.mean1, a.rstd1, P + o.ln1w, dres, 1, dyb_next, G + o.ln1w, G + o.ln1b, c_.ln_part, M, D, st));
+    if (!fuse) TRY(launch_ln_bwd(c_.dln, x_in, identity_rows(), a.mean1, a.rstd1, P + o.ln1w, dres, 1, dyb_next, G + o.ln1w, G + o.ln1b, c_.ln_part, M, D, st,
+                                 gated && li > 0 ? &g_below : nullptr));
     if (c_.overlap) {
         BVC_CHECK_HIP(hipEventRecord(c_.ev_join[par], c_.side));
         c_.join_pending[par] = true;

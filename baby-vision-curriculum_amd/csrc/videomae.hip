@@ -464,6 +464,7 @@ struct bvc_encoder_ctx {
     bf16_t *wbf, *Ape;
     int* idx_all;
     int pooled_batch = 0;    // clips whose pre-norm pooled rows and fc_norm statistics the last encode left (0: none)
+    DropState drop;          // bvc_videomae_encoder_set_drop: the forward gate of a train-mode module on the forward-only path
 };
 
 void bvc_videomae_encoder_destroy(bvc_encoder_ctx* c) {
@@ -498,6 +499,7 @@ int bvc_videomae_encoder_create(const bvc_videomae_config* cfg, int max_batch, b
     A(c->arena.alloc(&c->idx_all, M));
     A(c->arena.alloc(&c->Ape, M * c->P));
     A(alloc_stack(c->arena, c->st, D, I, H, 1, cfg->layer_norm_eps, M, (size_t)max_batch * H * c->L));
+    A(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
     A(c->arena.alloc(&c->xa, M * D));
     A(c->arena.alloc(&c->xb, M * D));
     A(c->arena.alloc(&c->pooled, (size_t)max_batch * D));
@@ -531,6 +533,8 @@ int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc
     const int B = batch, N = c->L, M = B * N, D = cf.hidden_size, P = c->P;
     c->w.params = params;
     c->w.wbf = c->wbf;
+    c->w.drop = &c->drop;
+    TRY(take_drop(c->drop, B, N, "encode"));
     const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
     TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
     TRY(launch_gather_patches(pixels, c->idx_all, c->Ape, B, N, pg, st));
@@ -544,9 +548,11 @@ int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc
     const int nl = (int)L.enc.size();
     for (int i = 0; i < nl; ++i) {
         float* dst = (i + 1 == nl && tokens) ? tokens : y;     // the last layer writes straight into the caller's buffer
+        c->w.drop_layer = i;     // one LayerAct serves every layer: the gate is keyed by the real layer
         TRY(layer_forward(c->w, c->st, 0, L.enc[i], x, dst, B, N, st));
         if (dst == y) std::swap(x, y); else x = dst;
     }
+    c->drop.active = false;      // forward only: nothing follows that would need the gate
     c->pooled_batch = 0;
     if (pooled) {
         float* mp = fc_norm_w ? c->pooled : pooled;
@@ -556,6 +562,11 @@ int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc
         if (fc_norm_w) c->pooled_batch = B;
     }
     return BVC_OK;
+}
+
+int bvc_videomae_encoder_set_drop(bvc_encoder_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
+    BVC_REQUIRE(c, "encoder_set_drop: null context");
+    return set_drop(c->drop, drop, samples, "encoder_set_drop", (hipStream_t)stream);
 }
 
 int bvc_videomae_encoder_fc_norm_backward(bvc_encoder_ctx* c, const float* dpooled, const float* fc_norm_w, float* dfc_norm_w,
@@ -587,6 +598,7 @@ struct bvc_cls_ctx {
     int batch = 0;
     bool have_forward = false;
     bool shadow_valid = false;   // as bvc_ctx::shadow_valid
+    DropState drop;              // bvc_videomae_cls_set_drop
 };
 
 void bvc_videomae_cls_destroy(bvc_cls_ctx* c) {
@@ -630,6 +642,7 @@ int bvc_videomae_cls_create(const bvc_videomae_config* cfg, int max_batch, bvc_c
     A(c->arena.alloc(&c->idx_all, M));
     A(c->arena.alloc(&c->Ape, M * P));
     A(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, M, (size_t)max_batch * H * L));
+    A(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
     A(c->arena.alloc(&c->pooled_pre, (size_t)max_batch * D));
     A(c->arena.alloc(&c->mean, (size_t)max_batch));
     A(c->arena.alloc(&c->rstd, (size_t)max_batch));
@@ -661,6 +674,8 @@ int bvc_videomae_cls_forward_px(bvc_cls_ctx* c, const void* pixels_any, const bv
     c->batch = B;
     c->w.params = params;
     c->w.wbf = c->wbf;
+    c->w.drop = &c->drop;
+    TRY(take_drop(c->drop, B, N, "cls_forward"));
     const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
     if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
     c->shadow_valid = false;
@@ -692,8 +707,9 @@ int bvc_videomae_cls_backward(bvc_cls_ctx* c, const float* dpooled, float* G, fl
     begin_backward(c->w);
     BVC_CHECK_HIP(hipMemsetAsync(G, 0, (size_t)L.e2d_w * 4, st));
     // fc_norm backward on the B pooled rows and the token-mean broadcast into the last layer's residual gradient, one pass
+    Gate gtop;     // (the first bf16 copy feeds the last layer's MLP branch: gated here when that context has a gate on)
     TRY(launch_fcnorm_bwd_bcast(dpooled, c->pooled_pre, c->mean, c->rstd, c->fcw, c->dres, c->w.dyb[c->w.seq % 3], dfc_norm_w, dfc_norm_b,
-                                B, N, D, st));
+                                B, N, D, st, top_gate(c->drop, gtop)));
     for (int i = c->enc.nlayers - 1; i >= 0; --i)
         TRY(layer_backward(c->w, c->enc, i, L.enc[i], c->enc.act[i].x_in, c->dres, G, B, N, st, on_bucket, user));
     // patch embedding: weight and bias over all B * L tokens (pixels need no gradient)
@@ -710,6 +726,11 @@ int bvc_videomae_cls_backward(bvc_cls_ctx* c, const float* dpooled, float* G, fl
     return BVC_OK;
 }
 
+int bvc_videomae_cls_set_drop(bvc_cls_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
+    BVC_REQUIRE(c, "cls_set_drop: null context");
+    return set_drop(c->drop, drop, samples, "cls_set_drop", (hipStream_t)stream);
+}
+
 int bvc_videomae_cls_shadow(bvc_cls_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
     BVC_REQUIRE(c, "videomae_cls_shadow: null context");
     if (shadow_bf16) *shadow_bf16 = c->wbf;
@@ -723,6 +744,49 @@ int bvc_op_gemm(const bvc_gemm_desc* problems, int count, int layout, int tile_c
     BVC_REQUIRE(problems, "op_gemm: null problems");
     BVC_REQUIRE(layout >= 0 && layout <= 2, "op_gemm: bad layout %d", layout);
     return launch_gemm(problems, count, (GemmLayout)layout, tile_cfg, (hipStream_t)stream, stages);
+}
+static int op_gate(const bvc_branch_drop* drop, int layer, int branch, int M, Gate* g) {
+    BVC_REQUIRE(drop && layer >= 0 && layer < (1 << 22) && (branch == 0 || branch == 1), "gate: null description, or layer / branch out of range");
+    BVC_REQUIRE(drop->hidden_p >= 0.f && drop->hidden_p < 1.f && drop->rows_per_sample >= 1, "gate: hidden_p outside [0, 1) or rows_per_sample < 1");
+    const int samples = (M + drop->rows_per_sample - 1) / drop->rows_per_sample;
+    *g = make_gate(drop->hidden_p, drop->seed, drop->offset,
+                   drop->path_scale ? drop->path_scale + ((size_t)layer * 2 + branch) * samples : nullptr, drop->rows_per_sample, layer, branch);
+    return BVC_OK;
+}
+int bvc_op_gemm_gate(const bvc_gemm_desc* problem, const bvc_branch_drop* drop, int layer, int branch, int tile_cfg, void* stream) {
+    BVC_REQUIRE(problem, "op_gemm_gate: null problem");
+    Gate g;
+    TRY(op_gate(drop, layer, branch, problem->M, &g));
+    return launch_gemm_gate(*problem, g, tile_cfg, (hipStream_t)stream);
+}
+int bvc_op_gemm_gate_kernel(const bvc_gemm_desc* problem, int tile_cfg, char* name, int name_cap) {
+    BVC_REQUIRE(problem && name && name_cap > 0, "op_gemm_gate_kernel: null argument");
+    DryRun& d = dry_run();
+    d.on = true;
+    d.name[0] = 0;
+    const int rc = launch_gemm_gate(*problem, make_gate(0.f, 0, 0, nullptr, 1, 0, 0), tile_cfg, nullptr);
+    d.on = false;
+    if (rc == BVC_OK) snprintf(name, name_cap, "%s", d.name);
+    return rc;
+}
+int bvc_op_dropout_mask(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_dev, void* stream) {
+    BVC_REQUIRE(out_dev && M >= 1 && N >= 1 && layer >= 0 && layer < (1 << 22) && (branch == 0 || branch == 1) && p >= 0.f && p < 1.f,
+                "op_dropout_mask: bad argument");
+    return launch_dropout_mask(make_gate(p, seed, offset, nullptr, 1, layer, branch), (size_t)M * N, out_dev, (hipStream_t)stream);
+}
+int bvc_dropout_mask_host(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_host) {
+    BVC_REQUIRE(out_host && M >= 1 && N >= 1 && layer >= 0 && layer < (1 << 22) && (branch == 0 || branch == 1) && p >= 0.f && p < 1.f,
+                "dropout_mask_host: bad argument");
+    dropout_mask_host(make_gate(p, seed, offset, nullptr, 1, layer, branch), (size_t)M * N, out_host);
+    return BVC_OK;
+}
+int bvc_op_layernorm_bwd_gate(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dres,
+                              int accumulate, void* dres_bf16, float* dgamma, float* dbeta, float* workspace, int M, int D,
+                              const bvc_branch_drop* drop, int layer, int branch, void* stream) {
+    Gate g;
+    TRY(op_gate(drop, layer, branch, M, &g));
+    return launch_ln_bwd((const bf16_t*)dy, x, identity_rows(), mean, rstd, gamma, dres, accumulate, (bf16_t*)dres_bf16, dgamma, dbeta,
+                         workspace, M, D, (hipStream_t)stream, &g);
 }
 int bvc_op_gemm_kernel(const bvc_gemm_desc* problems, int count, int layout, int tile_cfg, int stages, char* name, int name_cap) {
     BVC_REQUIRE(problems && name && name_cap > 0, "op_gemm_kernel: null argument");

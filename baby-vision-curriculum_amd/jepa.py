@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .dropgate import BranchGate
 from .flat import FlatParamModule, query_layout
 
 
@@ -89,6 +90,13 @@ def _init_like_reference(name, shape, init_std, fan_in_conv, layer_scale):
     return torch.zeros(shape)
 
 
+def _refuse_dropout(drop_rate, attn_drop_rate):
+    if drop_rate:
+        raise ValueError(f"drop_rate={drop_rate}: dropout on the projection / MLP outputs is not implemented (only 0.0)")
+    if attn_drop_rate:
+        raise ValueError(f"attn_drop_rate={attn_drop_rate}: dropout on the attention probabilities is not implemented (only 0.0)")
+
+
 # ----------------------------------------------------------------------------- encoder
 class _PatchEmbedInfo:
     def __init__(self, num_patches, patch_size, tubelet_size, img_size):
@@ -119,8 +127,12 @@ class VisionTransformer(FlatParamModule):
                  qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0, norm_layer=None, init_std=0.02,
                  norm_eps=1e-6, **kwargs):
         super().__init__()
-        if not qkv_bias or qk_scale is not None or drop_rate or attn_drop_rate or drop_path_rate:
-            raise ValueError("only qkv_bias=True, default scale and zero dropout / drop-path are implemented (the reference's settings)")
+        _refuse_dropout(drop_rate, attn_drop_rate)
+        if not qkv_bias or qk_scale is not None:
+            raise ValueError("only qkv_bias=True and the default scale are implemented (the reference's settings)")
+        # stochastic depth (vision_transformer.py:332,145-164): applied whenever self.training is set; a sample = the kept tokens of a clip
+        self.drop_path_rate = float(drop_path_rate)
+        self._gate = BranchGate(depth, drop_path_rate)
         self.num_features = self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.sequence_shape = (num_frames // tubelet_size, img_size[0] // patch_size, img_size[0] // patch_size)
@@ -147,6 +159,11 @@ class VisionTransformer(FlatParamModule):
     @property
     def num_patches(self):
         return self._pe_info.num_patches
+
+    @property
+    def drop_path_scale(self):
+        """[depth, 2, B] f32 stochastic-depth factors of the last train-mode forward (None when drop_path_rate is 0)."""
+        return self._gate.scale
 
     def _get_ctx(self, batch):
         dev = self._flat.device.index
@@ -176,6 +193,8 @@ class VisionTransformer(FlatParamModule):
         out = torch.empty((B, N, self.embed_dim), dtype=torch.float32, device=imgs.device)
         fmt = _lib.pixel_format(imgs, self.pixel_mean, self.pixel_std, self.in_chans)
         self._shadow_vouch(h)
+        if self.training and self._gate.enabled:
+            self._gate.arm(_lib.lib().bvc_vit_set_drop, h, imgs.device, B, N)
         _lib.check(_lib.lib().bvc_vit_forward_px(h, imgs.data_ptr(), ctypes.byref(fmt) if fmt is not None else None,
                                                  idx.data_ptr() if idx is not None else None, B, N, self._flat.data_ptr(),
                                                  out.data_ptr(), _lib.current_stream_ptr()), "bvc_vit_forward")
@@ -241,8 +260,12 @@ class VisionTransformerPredictor(FlatParamModule):
                  qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0, norm_layer=None,
                  init_std=0.02, norm_eps=1e-6, **kwargs):
         super().__init__()
-        if not qkv_bias or qk_scale is not None or drop_rate or attn_drop_rate or drop_path_rate:
-            raise ValueError("only qkv_bias=True, default scale and zero dropout / drop-path are implemented")
+        _refuse_dropout(drop_rate, attn_drop_rate)
+        if not qkv_bias or qk_scale is not None:
+            raise ValueError("only qkv_bias=True and the default scale are implemented")
+        # stochastic depth (vision_transformer.py:465,145-164): a sample = one of the len(masks) * B sequences of the call
+        self.drop_path_rate = float(drop_path_rate)
+        self._gate = BranchGate(depth, drop_path_rate)
         self.embed_dim, self.predictor_embed_dim, self.num_heads = embed_dim, predictor_embed_dim, num_heads
         self.sequence_shape = tuple(sequence_shape)
         self.num_patches = int(np.prod(sequence_shape))
@@ -263,6 +286,11 @@ class VisionTransformerPredictor(FlatParamModule):
 
         self._init_flat(layout, numel, init, frozen=("predictor_pos_embed",))
         self._ctx, self._ctx_key = None, None
+
+    @property
+    def drop_path_scale(self):
+        """[depth, 2, len(masks) * B] f32 stochastic-depth factors of the last train-mode forward (None when drop_path_rate is 0)."""
+        return self._gate.scale
 
     def _get_ctx(self, B, nsets, tokens):
         dev = self._flat.device.index
@@ -294,6 +322,8 @@ class VisionTransformerPredictor(FlatParamModule):
         zf = z.detach().to(torch.float32).contiguous()
         out = torch.empty((nsets * B, Np, self.embed_dim), dtype=torch.float32, device=z.device)
         self._shadow_vouch(h)
+        if self.training and self._gate.enabled:
+            self._gate.arm(_lib.lib().bvc_predictor_set_drop, h, z.device, nsets * B, Nc + Np)
         _lib.check(_lib.lib().bvc_predictor_forward(h, zf.data_ptr(), idx_ctx.data_ptr(), idx_pred.data_ptr(), B, Nc, nsets, Np,
                                                     self._flat.data_ptr(), out.data_ptr(), _lib.current_stream_ptr()),
                    "bvc_predictor_forward")
@@ -375,12 +405,14 @@ _FACTORIES = {'vit_tiny': vit_tiny, 'vit_small': vit_small, 'vit_base': vit_base
 
 
 def get_model(device, patch_size=16, tubelet_size=1, num_frames=1, model_name='vit_base', image_size=224, pred_depth=6,
-              pred_emb_dim=384):
+              pred_emb_dim=384, drop_path_rate=0.0):
     """pretrain_jepa.py:84-124: builds both modules, then re-draws every Linear with trunc_normal(std=0.02) (which also
     overwrites fix_init_weight's depth rescale) and resets LayerNorms."""
-    encoder = _FACTORIES[model_name](img_size=[image_size], patch_size=patch_size, num_frames=num_frames, tubelet_size=tubelet_size)
+    encoder = _FACTORIES[model_name](img_size=[image_size], patch_size=patch_size, num_frames=num_frames, tubelet_size=tubelet_size,
+                                     drop_path_rate=drop_path_rate)
     predictor = vit_predictor(sequence_shape=encoder.sequence_shape, embed_dim=encoder.embed_dim,
-                              predictor_embed_dim=pred_emb_dim, depth=pred_depth, num_heads=encoder.num_heads)
+                              predictor_embed_dim=pred_emb_dim, depth=pred_depth, num_heads=encoder.num_heads,
+                              drop_path_rate=drop_path_rate)
     for mod in (encoder, predictor):
         for name, p in mod.named_parameters():
             if name.startswith("patch_embed."):

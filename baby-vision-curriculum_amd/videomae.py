@@ -21,17 +21,32 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .dropgate import BranchGate
 from .flat import FlatParamModule, query_layout
 
 
 class VideoMAEConfig:
-    """The fields of transformers.VideoMAEConfig that the path reads; unknown kwargs are kept as attributes."""
+    """The fields of transformers.VideoMAEConfig that the path reads; unknown kwargs are kept as attributes.
+
+    ``hidden_dropout_prob`` (transformers' field: dropout on the two branch outputs of every encoder layer, HF:270-274, 316-320) and
+    the extension ``drop_path_rate`` (stochastic depth, rates ``linspace(0, rate, depth)`` as the published fine-tuning recipes use
+    it) take effect in ``VideoMAEForVideoClassification`` in train mode.  ``attention_probs_dropout_prob`` must stay 0.0: dropout on
+    the attention probabilities is not implemented, and a config that asks for it is refused instead of training another model."""
 
     def __init__(self, image_size=224, patch_size=16, num_channels=3, num_frames=16, tubelet_size=2,
                  hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                  hidden_act="gelu", layer_norm_eps=1e-12, initializer_range=0.02, qkv_bias=True,
                  use_mean_pooling=True, decoder_num_attention_heads=6, decoder_hidden_size=384,
-                 decoder_num_hidden_layers=4, decoder_intermediate_size=1536, norm_pix_loss=True, **kwargs):
+                 decoder_num_hidden_layers=4, decoder_intermediate_size=1536, norm_pix_loss=True,
+                 hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, drop_path_rate=0.0, **kwargs):
+        if attention_probs_dropout_prob:
+            raise ValueError(f"attention_probs_dropout_prob={attention_probs_dropout_prob}: dropout on the attention probabilities is not "
+                             "implemented (only 0.0)")
+        for name, v in (("hidden_dropout_prob", hidden_dropout_prob), ("drop_path_rate", drop_path_rate)):
+            if not 0.0 <= float(v) < 1.0:
+                raise ValueError(f"{name}={v} must lie in [0, 1)")
+        self.hidden_dropout_prob, self.attention_probs_dropout_prob = float(hidden_dropout_prob), float(attention_probs_dropout_prob)
+        self.drop_path_rate = float(drop_path_rate)
         if hidden_act != "gelu":
             raise ValueError("only hidden_act='gelu' (exact erf GELU) is implemented")
         if not qkv_bias:
@@ -101,6 +116,10 @@ class VideoMAEForPreTraining(FlatParamModule):
 
     def __init__(self, config: VideoMAEConfig):
         super().__init__()
+        for field in ("hidden_dropout_prob", "drop_path_rate", "attention_probs_dropout_prob"):
+            if getattr(config, field, 0.0):
+                raise ValueError(f"{field}={getattr(config, field)}: dropout / stochastic depth in pre-training is not implemented "
+                                 "(VideoMAEForVideoClassification applies hidden_dropout_prob and drop_path_rate)")
         self.config = config
         layout, numel = param_layout(config)
         std = config.initializer_range
@@ -369,6 +388,11 @@ class VideoMAEForVideoClassification(FlatParamModule):
     encoder parameter, the fine-tuning context, whose every layer keeps its activations for the backward (about 36 x hidden bytes per
     token and layer: 0.52 GB per clip at base size); otherwise the inference context, forward only through the encoder, with fc_norm's
     gradient from the library's LayerNorm backward when fc_norm is trainable.  Both give the same logits bit for bit.
+
+    ``config.hidden_dropout_prob`` and ``config.drop_path_rate`` gate the two residual branches of every encoder layer whenever the
+    module is in train mode - on either context, with or without grad mode, as ``nn.Dropout`` follows ``training`` alone - with draws
+    from torch's generator of the device (``torch.manual_seed`` reproduces them; both contexts draw alike, so the two paths still agree
+    bit for bit under one seed).  ``drop_path_scale`` / ``dropout_state`` report what the last gated forward used.
     """
 
     _shadow_fn = "bvc_videomae_cls_shadow"
@@ -377,7 +401,12 @@ class VideoMAEForVideoClassification(FlatParamModule):
         super().__init__()
         if not getattr(config, "use_mean_pooling", True):
             raise ValueError("only use_mean_pooling=True (the reference's setting) is implemented")
+        if getattr(config, "attention_probs_dropout_prob", 0.0):
+            raise ValueError(f"attention_probs_dropout_prob={config.attention_probs_dropout_prob}: dropout on the attention "
+                             "probabilities is not implemented (only 0.0)")
         self.config = config
+        # the gate on every layer's two residual branches, applied whenever self.training is set (dropgate.py)
+        self._gate = BranchGate(config.num_hidden_layers, getattr(config, "drop_path_rate", 0.0), getattr(config, "hidden_dropout_prob", 0.0))
         self.num_labels = int(getattr(config, "num_labels", 2))
         full, _ = param_layout(config)
         cc = config.to_c()
@@ -452,6 +481,22 @@ class VideoMAEForVideoClassification(FlatParamModule):
         except Exception:
             pass
 
+    @property
+    def drop_path_scale(self):
+        """[depth, 2, clips] f32: the stochastic-depth factors of the last train-mode forward (0 = branch dropped for that clip,
+        1 / (1 - rate) = kept; branch 0 = attention, 1 = MLP), or None when drop_path_rate is 0."""
+        return self._gate.scale
+
+    @property
+    def dropout_state(self):
+        """(seed, offset, p) of the last train-mode forward's hidden dropout: dropgate.dropout_mask(seed, offset, layer, branch,
+        clips * seq_length, hidden_size, p, device) is the keep mask a branch used.  None before the first gated forward."""
+        return self._gate.state
+
+    def _arm_gate(self, set_drop, h, B, dev):
+        if self.training and self._gate.enabled:
+            self._gate.arm(set_drop, h, dev, B, self.config.seq_length)
+
     def _encoder_trainable(self):
         return any(self._param(n).requires_grad for n in self._names)
 
@@ -467,6 +512,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
         w, b = self._fc_norm_args(fc_w, fc_b, dev)
         pooled = torch.empty((B, cfg.hidden_size), dtype=torch.float32, device=dev)
         tokens = torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev) if want_tokens else None
+        self._arm_gate(_lib.lib().bvc_videomae_encoder_set_drop, h, B, dev)     # train mode on the forward-only path: the same gate
         _lib.check(_lib.lib().bvc_videomae_encode_px(
             h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
             float(self.fc_norm.eps),
@@ -482,6 +528,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
         pooled = torch.empty((B, cfg.hidden_size), dtype=torch.float32, device=dev)
         tokens = torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev) if want_tokens else None
         self._shadow_vouch(h)
+        self._arm_gate(_lib.lib().bvc_videomae_cls_set_drop, h, B, dev)
         _lib.check(_lib.lib().bvc_videomae_cls_forward_px(
             h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
             float(self.fc_norm.eps), pooled.data_ptr(), tokens.data_ptr() if tokens is not None else None, _lib.current_stream_ptr()),

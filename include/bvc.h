@@ -192,6 +192,39 @@ int bvc_videomae_cls_backward(bvc_cls_ctx* ctx, const float* dpooled_dev, float*
 int bvc_videomae_cls_shadow(bvc_cls_ctx* ctx, int valid, void** shadow_bf16, int64_t* numel);
 
 /* ------------------------------------------------------------------------------------------------
+ * Stochastic depth and hidden dropout: a gate on the two residual branches of every pre-LN layer of a context,
+ *     h     = x_in + g1 .* (proj(ctx) + b_o)        g(row, col) = path_scale[layer][branch][row / rows_per_sample]
+ *     x_out = h    + g2 .* (fc2(act) + b_2)                       * keep(row, col) / (1 - hidden_p)
+ * Replaces DropPath / drop_path (pretraining/predictive/vision_transformer.py:145-164, Block.forward :229-230) and
+ * VideoMAESelfOutput.dropout / VideoMAEOutput.dropout (HF:270-274, 316-320).
+ *   path_scale      device f32 [layers][2][samples] (branch 0 = attention, 1 = MLP): 0 for a dropped sample, 1 / (1 - rate) for a
+ *                   kept one; NULL = no stochastic depth.  Copied into the context by the set_drop call (stream-ordered).
+ *   rows_per_sample rows that share one path_scale entry: the tokens of one sequence of the call (a clip's seq_len; ntok for
+ *                   bvc_vit_forward; Nc + Np for the predictor, whose samples are its nsets * B sequences)
+ *   hidden_p        element dropout probability in [0, 1) on both branch outputs; the keep mask is NOT stored: it is a function of
+ *                   (seed, offset, layer, branch, element index row * width + col) - Philox4x32-10, counter = {index / 4 low,
+ *                   index / 4 high | (2 layer + branch) << 8, offset low, offset high}, key = seed; output (index % 4) below
+ *                   hidden_p * 2^32 drops the element - that the backward evaluates again.  bvc_op_dropout_mask /
+ *                   bvc_dropout_mask_host give the same mask as bytes (1 = kept).
+ * bvc_*_set_drop sets the gate for the NEXT forward of the context and the backward that belongs to it; later forwards run ungated
+ * until it is called again.  drop == NULL, or hidden_p == 0 with path_scale == NULL, switches it off.  With the gate off a context
+ * launches exactly the kernels it launches without this interface.  While it is on, the two branch products of a layer run the
+ * BVC_EPI_RESID_GATE epilogue of the 128 x 128 / 128 x 64 / 64 x 64 kernel and the LayerNorms run as separate passes; in the
+ * backward the residual gradient passes ungated and the bf16 copies that feed a branch are gated where they are produced. */
+typedef struct bvc_branch_drop {
+    float hidden_p;
+    uint64_t seed, offset;
+    const float* path_scale;
+    int rows_per_sample;
+} bvc_branch_drop;
+int bvc_videomae_cls_set_drop(bvc_cls_ctx* ctx, const bvc_branch_drop* drop, int samples, void* stream);
+/* forward only (a train-mode module under torch.no_grad(), a train-mode linear probe) */
+int bvc_videomae_encoder_set_drop(bvc_encoder_ctx* ctx, const bvc_branch_drop* drop, int samples, void* stream);
+/* keep bytes (1 = kept, 0 = dropped) of the M x N element mask of one branch, row-major, on the device and on the host */
+int bvc_op_dropout_mask(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_dev, void* stream);
+int bvc_dropout_mask_host(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_host);
+
+/* ------------------------------------------------------------------------------------------------
  * JEPA encoder and predictor (pretraining/predictive/vision_transformer.py).  Same conventions as above: flat f32
  * parameter / gradient buffers whose entries carry the reference's state-dict keys (pos_embed, patch_embed.proj.*,
  * blocks.N.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}.*, norm.* / mask_token, predictor_pos_embed,
@@ -220,6 +253,8 @@ int bvc_vit_forward_px(bvc_vit_ctx* ctx, const void* imgs_dev, const bvc_pixel_f
 int bvc_vit_backward(bvc_vit_ctx* ctx, const float* dout_dev, float* grads_dev, bvc_bucket_fn on_bucket, void* user, void* stream);
 /* as bvc_videomae_shadow */
 int bvc_vit_shadow(bvc_vit_ctx* ctx, int valid, void** shadow_bf16, int64_t* numel);
+/* stochastic depth / hidden dropout of the next forward and its backward (bvc_branch_drop above); samples = batch */
+int bvc_vit_set_drop(bvc_vit_ctx* ctx, const bvc_branch_drop* drop, int samples, void* stream);
 
 typedef struct bvc_predictor_config {
     int seq_len;    /* tokens of the full grid (num_patches of the encoder) */
@@ -243,6 +278,8 @@ int bvc_predictor_forward(bvc_pred_ctx* ctx, const float* z_dev, const int* idx_
 int bvc_predictor_backward(bvc_pred_ctx* ctx, const float* dout_dev, float* grads_dev, float* dz_dev, void* stream);
 /* as bvc_videomae_shadow */
 int bvc_predictor_shadow(bvc_pred_ctx* ctx, int valid, void** shadow_bf16, int64_t* numel);
+/* as bvc_vit_set_drop; samples = nsets * B sequences, ordered as the predictor's rows (mask-set-major) */
+int bvc_predictor_set_drop(bvc_pred_ctx* ctx, const bvc_branch_drop* drop, int samples, void* stream);
 /* The same, reporting gradient ranges tail-first (bvc_bucket_fn, as bvc_videomae_backward / bvc_vit_backward do) so that the
  * data-parallel wrapper can start the predictor's all-reduce per block: DDP(predictor, static_graph=True), pretrain_jepa.py:303. */
 int bvc_predictor_backward_cb(bvc_pred_ctx* ctx, const float* dout_dev, float* grads_dev, float* dz_dev, bvc_bucket_fn on_bucket,
@@ -269,7 +306,7 @@ enum { BVC_GEMM_NT = 0, BVC_GEMM_NN = 1, BVC_GEMM_TN = 2 };
 enum {
     BVC_EPI_F32 = 0, BVC_EPI_BF16 = 1, BVC_EPI_GELU = 2, BVC_EPI_RESID = 3, BVC_EPI_POS = 4, BVC_EPI_E2D = 5,
     BVC_EPI_LOSS = 6, BVC_EPI_DGELU = 7, BVC_EPI_F32_BF16 = 8, BVC_EPI_RELU = 9, BVC_EPI_DRELU = 10,
-    BVC_EPI_NCE = 11, BVC_EPI_NCE_BWD = 12, BVC_EPI_RESID_LN = 13, BVC_EPI_DLN = 14
+    BVC_EPI_NCE = 11, BVC_EPI_NCE_BWD = 12, BVC_EPI_RESID_LN = 13, BVC_EPI_DLN = 14, BVC_EPI_RESID_GATE = 15
 };
 /* BVC_EPI_GELU writes TWO bf16 outputs: C2 = gelu(v + bias) and C = gelu'(v + bias), the factor the backward product needs (the
  * forward epilogue has the erf and the exponential at hand; the backward epilogue BVC_EPI_DGELU, C = v * aux with aux = that C, is
@@ -310,6 +347,12 @@ typedef struct bvc_gemm_desc {
  * (3-5 and 8 are experiment kernels that exist only in a -DBVC_EXPERIMENTS build.)  stages: -1 auto, 2..4 = K-loop variant. */
 int bvc_op_gemm(const bvc_gemm_desc* problems, int count, int layout, int tile_cfg, int stages, void* stream);
 int bvc_op_gemm_num_tiles(const bvc_gemm_desc* problem, int tile_cfg);
+/* BVC_EPI_RESID_GATE: one NT product C f32 = resid + gate .* (alpha AB + bias) with the gate of (layer, branch) of `drop`
+ * (path_scale indexed [(2 layer + branch) * samples + m / rows_per_sample], samples = ceil(M / rows_per_sample)); split_k == 1,
+ * tile_cfg -1 / 0 / 1 / 2.  bvc_op_gemm rejects this epilogue (it has no gate to give it).  bvc_op_gemm_gate_kernel: the
+ * instantiation it runs, as bvc_op_gemm_kernel reports the others. */
+int bvc_op_gemm_gate(const bvc_gemm_desc* problem, const bvc_branch_drop* drop, int layer, int branch, int tile_cfg, void* stream);
+int bvc_op_gemm_gate_kernel(const bvc_gemm_desc* problem, int tile_cfg, char* name, int name_cap);
 /* Introspection of the selection above, nothing is launched: the kernel instantiation bvc_op_gemm would run for these problems,
  * named as rocprofv3 prints it (e.g. "bvc::gemm8_kernel<256, true, true, 2>"), so that per-product timings can be attributed to the
  * rows of a kernel-stats table (bench.py's `roofline.kernels`); and the (tile_cfg, split_k) plan the step uses for a group of
@@ -346,6 +389,10 @@ int bvc_op_layernorm_bwd(const void* dy_bf16, const float* x, int rin, int rout,
                          const float* rstd, const float* gamma, float* dres, int accumulate, void* dres_bf16,
                          float* dgamma, float* dbeta, float* workspace, int M, int D, void* stream);
 int64_t bvc_op_layernorm_bwd_workspace(int M, int D);
+/* the same over dense rows with the bf16 copy alone gated: dres_bf16 = bf16(gate .* dres) for (layer, branch) of `drop` */
+int bvc_op_layernorm_bwd_gate(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, float* dres,
+                              int accumulate, void* dres_bf16, float* dgamma, float* dbeta, float* workspace, int M, int D,
+                              const bvc_branch_drop* drop, int layer, int branch, void* stream);
 int bvc_op_colsum_bf16(const void* X, int M, int N, int ld, float alpha, const float* alpha_dev, float* out, void* stream);
 /* out[n] += sum over rows m of X f32 [M][D] (rows strided by (rin, rout, roff) as for LayerNorm, rin <= 0 = dense): the mask-token
  * gradient of the VideoMAE decoder / JEPA predictor; D % 4 == 0 */

@@ -2,6 +2,10 @@
 on synthetic 16 x 224^2 clips, every one of the 1568 tokens through the encoder.  One JSON line:
 
     python tools/bench_videomae_cls.py --arch {small,base,large,huge} --batch B [--steps K --warmup W]
+                                       [--hidden-dropout P] [--drop-path R]
+
+--hidden-dropout / --drop-path switch the gate on the residual branches on (config.hidden_dropout_prob / config.drop_path_rate);
+left at 0 the step is the ungated one, kernel for kernel.
 
 Algorithmic cost per clip: forward = patch embedding 2 N D P (P = 1536 pixels per tube) + layers x (24 N D^2 + 4 N^2 D); a step
 counts the encoder 3x (forward, dX, dW) and the patch embedding 2x (forward, dW; pixels need no gradient).  VideoMAE-base:
@@ -37,12 +41,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--num-labels", type=int, default=400)
+    ap.add_argument("--hidden-dropout", type=float, default=0.0)
+    ap.add_argument("--drop-path", type=float, default=0.0)
     args = ap.parse_args()
     ge.build()
     bvc = ge.load_package()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    cfg = bvc.videomae_config(args.arch, num_labels=args.num_labels)
+    drop = {}
+    if args.hidden_dropout:
+        drop["hidden_dropout_prob"] = args.hidden_dropout
+    if args.drop_path:
+        drop["drop_path_rate"] = args.drop_path
+    cfg = bvc.videomae_config(args.arch, num_labels=args.num_labels, **drop)
     B = args.batch
     free0 = torch.cuda.mem_get_info(dev)[0]
     m = bvc.VideoMAEForVideoClassification(cfg).to(dev).train()
@@ -70,7 +81,7 @@ def main():
     gf, pe, layer = gflop_per_clip(cfg)
     tflops = gf * B / dt / 1e3
     print(json.dumps({"metric": f"VideoMAE-{args.arch} fine-tuning step (forward + backward + AdamW), all tokens, bf16 operands",
-                      "arch": args.arch, "batch": B, "ms_per_step": round(1e3 * dt, 3), "clips_per_s": round(B / dt, 1),
+                      "arch": args.arch, "batch": B, "hidden_dropout": args.hidden_dropout, "drop_path": args.drop_path, "ms_per_step": round(1e3 * dt, 3), "clips_per_s": round(B / dt, 1),
                       "gflop_per_clip": round(gf, 2), "gflop_patch_embed_fwd": round(pe, 3), "gflop_layer_fwd": round(layer, 3),
                       "tflops": round(tflops, 1), "frac_peak": round(tflops / PEAK_TFLOPS, 4), "device_mem_gb": round(used / 1e9, 2),
                       "loss": round(float(loss), 4), "finite": bool(torch.isfinite(loss).all())}), flush=True)

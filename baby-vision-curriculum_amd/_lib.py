@@ -120,10 +120,13 @@ SYMBOLS = {
                                         ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), ctypes.POINTER(c_int),
                                         ctypes.POINTER(c_int64)]),
     "bvc_videomae_create": (c_int, [ctypes.POINTER(VideoMAEConfigC), c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "bvc_videomae_create_dual": (c_int, [ctypes.POINTER(VideoMAEConfigC), c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "bvc_videomae_destroy": (None, [c_void_p]),
     "bvc_videomae_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_videomae_forward_px": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PixelFormatC), c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "bvc_videomae_forward_dual": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PixelFormatC), c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
     "bvc_videomae_backward": (c_int, [c_void_p, c_void_p, c_void_p, BUCKET_FN, c_void_p, c_void_p]),
     "bvc_videomae_tap": (c_int, [c_void_p, c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
     "bvc_videomae_encoder_param_numel": (c_int64, [ctypes.POINTER(VideoMAEConfigC)]),
@@ -211,6 +214,7 @@ SYMBOLS = {
                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bvc_op_nonfinite_check": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "bvc_op_mask_index": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_dual_mask_index": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_gather_patches": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_op_pixel_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_comm_unique_id": (c_int, [c_void_p]),

@@ -51,10 +51,15 @@ void dropout_mask_host(const Gate& gate, size_t n, uint8_t* out);
 int launch_cast_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int launch_gather_rows_bf16(const float* in, RowMap rm, bf16_t* out, int M, int D, hipStream_t s);
 int launch_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, hipStream_t s);
+// mask + decode mask (a subset of the mask) -> visible list and the list of decoded masked tokens, both in ascending token order
+int launch_dual_mask_index(const uint8_t* mask, const uint8_t* decode, int B, int L, int nvis, int ndec, int* vis_idx, int* dec_idx,
+                           int* status, hipStream_t s);
 int launch_gather_patches(PixelSrc clip, const int* vis_idx, bf16_t* A, int B, int nvis, PatchGeom pg, hipStream_t s);
-int launch_labels(PixelSrc clip, const int* msk_idx, float* labels, int B, int nmask, PatchGeom pg, int norm_pix, hipStream_t s);
-int launch_fill_masked(float* xfull, const float* mask_token, const float* pos, const int* msk_idx, int B, int L, int nvis,
-                       int nmask, int D, hipStream_t s);
+// dec_idx [B][ndec]: the tokens the decoder reconstructs (every masked token, or the decoded subset), ascending per clip;
+// Ld = nvis + ndec: the decoder's rows per clip
+int launch_labels(PixelSrc clip, const int* dec_idx, float* labels, int B, int ndec, PatchGeom pg, int norm_pix, hipStream_t s);
+int launch_fill_masked(float* xfull, const float* mask_token, const float* pos, const int* dec_idx, int B, int Ld, int nvis,
+                       int ndec, int D, hipStream_t s);
 int launch_sgd_step(float* p, float* g, float* buf, size_t n, float lr, float momentum, float dampening, float wd, int nesterov,
                     int first, int maximize, const float* grad_scale, const float* found_inf, int write_grad, bf16_t* shadow,
                     hipStream_t s);

@@ -522,6 +522,30 @@ __global__ void mask_index_kernel(const uint8_t* __restrict__ mask, int L, int n
     if (lane == 0 && (nv != nvis || nm != nmask)) atomicOr(status, 1);
 }
 
+// The same with a second byte mask that picks the masked tokens the decoder reconstructs (VideoMAE V2's decoder masking): vis_idx as
+// above, dec_idx the decoded tokens in ascending token order, so the boolean-gather order (HF:578-582) holds for the subset.  The
+// status word is raised when a clip's visible count is not nvis, its decoded count is not ndec, or a decoded token is not masked (a
+// decoded token the encoder sees would leak its target into the loss).
+__global__ void dual_mask_index_kernel(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ decode, int L, int nvis, int ndec,
+                                       int* __restrict__ vis_idx, int* __restrict__ dec_idx, int* __restrict__ status) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int nv = 0, nd = 0, nbad = 0;
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    for (int base = 0; base < L; base += 64) {
+        const int t = base + lane;
+        const bool in = t < L;
+        const bool mk = in && mask[(size_t)b * L + t] != 0;
+        const bool dk = in && decode[(size_t)b * L + t] != 0;
+        const unsigned long long bv = __ballot(in && !mk), bd = __ballot(dk);
+        if (dk) { const int p = nd + __popcll(bd & below); if (p < ndec) dec_idx[(size_t)b * ndec + p] = t; }
+        if (in && !mk) { const int p = nv + __popcll(bv & below); if (p < nvis) vis_idx[(size_t)b * nvis + p] = t; }
+        nd += __popcll(bd);
+        nv += __popcll(bv);
+        nbad += __popcll(__ballot(dk && !mk));
+    }
+    if (lane == 0 && (nv != nvis || nd != ndec || nbad != 0)) atomicOr(status, 1);
+}
+
 // four consecutive pixels of channel c starting at element `src` (a multiple of 4)
 __device__ __forceinline__ f32x4 load_pixels4(const PixelSrc& px, size_t src, int c) {
     if (!px.is_u8) return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(px.ptr) + src);
@@ -557,8 +581,8 @@ __global__ void gather_patches_kernel(const PixelSrc clip, const int* __restrict
 // ============================================================================ pixel targets (HF:588-661)
 // one workgroup per masked token: un-normalise, per-channel mean / unbiased variance over ts*ps*ps
 // values, labels[(dt,dy,dx,c)] = (f - mean) / (sqrt(var) + 1e-6)
-__global__ __launch_bounds__(256) void labels_kernel(const PixelSrc clip, const int* __restrict__ msk_idx,
-                                                     float* __restrict__ labels, int nmask, PatchGeom pg, int norm_pix) {
+__global__ __launch_bounds__(256) void labels_kernel(const PixelSrc clip, const int* __restrict__ dec_idx,
+                                                     float* __restrict__ labels, int ndec, PatchGeom pg, int norm_pix) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* buf = reinterpret_cast<float*>(smem);   // [C][E]
     const int E = pg.ts * pg.ps * pg.ps, C = pg.C;
@@ -570,7 +594,7 @@ __global__ __launch_bounds__(256) void labels_kernel(const PixelSrc clip, const 
     // the line: 4.45 GB read for 2.2 GB of pixels at 256 clips.  Each XCD takes a contiguous run of tokens instead.
     const int nb = gridDim.x, xq = nb >> 3, xr = nb & 7, xcd = blockIdx.x & 7;
     const int m = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
-    const int b = m / nmask, tok = msk_idx[m];
+    const int b = m / ndec, tok = dec_idx[m];
     const int wp = pg.W / pg.ps, hp = pg.H / pg.ps;
     const int tp = tok / (hp * wp), yp = (tok / wp) % hp, xp = tok % wp;
     const float mean3[3] = {0.485f, 0.456f, 0.406f}, std3[3] = {0.229f, 0.224f, 0.225f};
@@ -613,8 +637,8 @@ __global__ __launch_bounds__(256) void labels_kernel(const PixelSrc clip, const 
 // and never meet a workgroup barrier; 24 tokens per CU are in flight.  Same arithmetic in the same order as labels_kernel (per channel:
 // lane-strided sums, wave_sum, two passes), so the labels are bit-identical.  Tokens are taken XCD by XCD like above.
 template <int NCH>
-__global__ __launch_bounds__(256, 6) void labels_wave_kernel(const PixelSrc clip, const int* __restrict__ msk_idx,
-                                                          float* __restrict__ labels, int ntok, int nmask, PatchGeom pg, int norm_pix) {
+__global__ __launch_bounds__(256, 6) void labels_wave_kernel(const PixelSrc clip, const int* __restrict__ dec_idx,
+                                                          float* __restrict__ labels, int ntok, int ndec, PatchGeom pg, int norm_pix) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int E = pg.ts * pg.ps * pg.ps, C = pg.C;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -625,7 +649,7 @@ __global__ __launch_bounds__(256, 6) void labels_wave_kernel(const PixelSrc clip
     const int blk = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
     const int m = blk * 4 + wave;
     if (m >= ntok) return;                       // whole waves leave; nothing below synchronises across waves
-    const int b = m / nmask, tok = msk_idx[m];
+    const int b = m / ndec, tok = dec_idx[m];
     const int wp = pg.W / pg.ps, hp = pg.H / pg.ps;
     const int tp = tok / (hp * wp), yp = (tok / wp) % hp, xp = tok % wp;
     const float mean3[3] = {0.485f, 0.456f, 0.406f}, std3[3] = {0.229f, 0.224f, 0.225f};
@@ -687,8 +711,8 @@ __global__ __launch_bounds__(256, 6) void labels_wave_kernel(const PixelSrc clip
 // rounding of (f - mean) / (sqrt(var) + 1e-6).  The per-lane channel of output position 4 lane + 256 k + j is (lane + k + j) mod 3, so
 // with the channel statistics rotated by lane mod 3 once, every use is a compile-time register.
 template <int NE>      // NE = E / 256: chunks per lane and channel
-__global__ __launch_bounds__(256, 6) void labels_wave3_kernel(const PixelSrc clip, const int* __restrict__ msk_idx, float* __restrict__ labels,
-                                                              int ntok, int nmask, PatchGeom pg, int norm_pix) {
+__global__ __launch_bounds__(256, 6) void labels_wave3_kernel(const PixelSrc clip, const int* __restrict__ dec_idx, float* __restrict__ labels,
+                                                              int ntok, int ndec, PatchGeom pg, int norm_pix) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int C = 3, E = 256 * NE, CE = C * E, NCH = C * NE;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -697,7 +721,7 @@ __global__ __launch_bounds__(256, 6) void labels_wave3_kernel(const PixelSrc cli
     const int blk = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
     const int m = blk * 4 + wave;
     if (m >= ntok) return;
-    const int b = m / nmask, tok = msk_idx[m];
+    const int b = m / ndec, tok = dec_idx[m];
     const int wp = pg.W / pg.ps, hp = pg.H / pg.ps;
     const int tp = tok / (hp * wp), yp = (tok / wp) % hp, xp = tok % wp;
     const float mean3[3] = {0.485f, 0.456f, 0.406f}, std3[3] = {0.229f, 0.224f, 0.225f};
@@ -757,17 +781,17 @@ __global__ __launch_bounds__(256, 6) void labels_wave3_kernel(const PixelSrc cli
     }
 }
 
-// x_full[b][nvis + j][:] = mask_token + pos[msk_idx[b][j]]   (HF:580-582)
+// x_full[b][nvis + j][:] = mask_token + pos[dec_idx[b][j]]   (HF:580-582)
 __global__ void fill_masked_kernel(float* __restrict__ xfull, const float* __restrict__ mask_token, const float* __restrict__ pos,
-                                   const int* __restrict__ msk_idx, int B, int L, int nvis, int nmask, int D) {
+                                   const int* __restrict__ dec_idx, int B, int Ld, int nvis, int ndec, int D) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int nch = D >> 2;
-    if (i >= (size_t)B * nmask * nch) return;
+    if (i >= (size_t)B * ndec * nch) return;
     const int m = (int)(i / nch), c = (int)(i % nch);
-    const int b = m / nmask, j = m % nmask;
+    const int b = m / ndec, j = m % ndec;
     const f32x4 mt = reinterpret_cast<const f32x4*>(mask_token)[c];
-    const f32x4 pe = reinterpret_cast<const f32x4*>(pos + (size_t)msk_idx[m] * D)[c];
-    reinterpret_cast<f32x4*>(xfull + ((size_t)b * L + nvis + j) * D)[c] = mt + pe;
+    const f32x4 pe = reinterpret_cast<const f32x4*>(pos + (size_t)dec_idx[m] * D)[c];
+    reinterpret_cast<f32x4*>(xfull + ((size_t)b * Ld + nvis + j) * D)[c] = mt + pe;
 }
 
 // loss = sum(partials) / count, fixed summation order; NaN if the mask index kernel flagged a bad mask
@@ -1507,6 +1531,13 @@ int launch_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, in
     return BVC_OK;
 }
 
+int launch_dual_mask_index(const uint8_t* mask, const uint8_t* decode, int B, int L, int nvis, int ndec, int* vis_idx, int* dec_idx,
+                           int* status, hipStream_t s) {
+    hipLaunchKernelGGL(dual_mask_index_kernel, dim3(B), dim3(64), 0, s, mask, decode, L, nvis, ndec, vis_idx, dec_idx, status);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
 int launch_gather_patches(PixelSrc clip, const int* vis_idx, bf16_t* A, int B, int nvis, PatchGeom pg, hipStream_t s) {
     BVC_REQUIRE(pg.ps % 8 == 0 && pg.W % 4 == 0, "gather_patches: patch size must be a multiple of 8");
     const size_t items = (size_t)B * nvis * (pg.C * pg.ts * pg.ps * pg.ps / 8);
@@ -1515,16 +1546,16 @@ int launch_gather_patches(PixelSrc clip, const int* vis_idx, bf16_t* A, int B, i
     return BVC_OK;
 }
 
-int launch_labels(PixelSrc clip, const int* msk_idx, float* labels, int B, int nmask, PatchGeom pg, int norm_pix, hipStream_t s) {
+int launch_labels(PixelSrc clip, const int* dec_idx, float* labels, int B, int ndec, PatchGeom pg, int norm_pix, hipStream_t s) {
     BVC_REQUIRE(pg.ps % 4 == 0, "labels: patch size must be a multiple of 4");
     const int E = pg.ts * pg.ps * pg.ps;
     const size_t lds = (size_t)(pg.C * E + 2 * pg.C) * 4;
     // one wave per token when a token is at most 8 x 64 chunks of 16 bytes (C E <= 2048 values: every configuration of the reference)
-    const int nchunk = pg.C * (E >> 2), ntok = B * nmask;
+    const int nchunk = pg.C * (E >> 2), ntok = B * ndec;
     if (pg.C == 3 && (E == 512 || E == 256)) {      // the reference's tubes: constant channel count, statistics from registers
         const int nblk = (ntok + 3) / 4;
-        if (E == 512) hipLaunchKernelGGL(labels_wave3_kernel<2>, dim3(nblk), dim3(256), (size_t)4 * 3 * E * 4, s, clip, msk_idx, labels, ntok, nmask, pg, norm_pix);
-        else hipLaunchKernelGGL(labels_wave3_kernel<1>, dim3(nblk), dim3(256), (size_t)4 * 3 * E * 4, s, clip, msk_idx, labels, ntok, nmask, pg, norm_pix);
+        if (E == 512) hipLaunchKernelGGL(labels_wave3_kernel<2>, dim3(nblk), dim3(256), (size_t)4 * 3 * E * 4, s, clip, dec_idx, labels, ntok, ndec, pg, norm_pix);
+        else hipLaunchKernelGGL(labels_wave3_kernel<1>, dim3(nblk), dim3(256), (size_t)4 * 3 * E * 4, s, clip, dec_idx, labels, ntok, ndec, pg, norm_pix);
         BVC_CHECK_HIP(hipGetLastError());
         return BVC_OK;
     }
@@ -1532,20 +1563,20 @@ int launch_labels(PixelSrc clip, const int* msk_idx, float* labels, int B, int n
         const int per_wave = (pg.C * E + 2 * pg.C + 3) & ~3;
         const int nblk = (ntok + 3) / 4;
         if (nchunk <= 384)
-            hipLaunchKernelGGL(labels_wave_kernel<6>, dim3(nblk), dim3(256), (size_t)per_wave * 16, s, clip, msk_idx, labels, ntok, nmask, pg, norm_pix);
+            hipLaunchKernelGGL(labels_wave_kernel<6>, dim3(nblk), dim3(256), (size_t)per_wave * 16, s, clip, dec_idx, labels, ntok, ndec, pg, norm_pix);
         else
-            hipLaunchKernelGGL(labels_wave_kernel<8>, dim3(nblk), dim3(256), (size_t)per_wave * 16, s, clip, msk_idx, labels, ntok, nmask, pg, norm_pix);
+            hipLaunchKernelGGL(labels_wave_kernel<8>, dim3(nblk), dim3(256), (size_t)per_wave * 16, s, clip, dec_idx, labels, ntok, ndec, pg, norm_pix);
         BVC_CHECK_HIP(hipGetLastError());
         return BVC_OK;
     }
-    hipLaunchKernelGGL(labels_kernel, dim3(B * nmask), dim3(256), lds, s, clip, msk_idx, labels, nmask, pg, norm_pix);
+    hipLaunchKernelGGL(labels_kernel, dim3(B * ndec), dim3(256), lds, s, clip, dec_idx, labels, ndec, pg, norm_pix);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }
 
-int launch_fill_masked(float* xfull, const float* mask_token, const float* pos, const int* msk_idx, int B, int L, int nvis,
-                       int nmask, int D, hipStream_t s) {
-    hipLaunchKernelGGL(fill_masked_kernel, dim3(blocks_for((size_t)B * nmask * (D / 4))), dim3(256), 0, s, xfull, mask_token, pos, msk_idx, B, L, nvis, nmask, D);
+int launch_fill_masked(float* xfull, const float* mask_token, const float* pos, const int* dec_idx, int B, int Ld, int nvis,
+                       int ndec, int D, hipStream_t s) {
+    hipLaunchKernelGGL(fill_masked_kernel, dim3(blocks_for((size_t)B * ndec * (D / 4))), dim3(256), 0, s, xfull, mask_token, pos, dec_idx, B, Ld, nvis, ndec, D);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

@@ -93,6 +93,9 @@ struct bvc_ctx {
     bvc_videomae_config cfg;
     Layout lay;
     int max_batch, nmask, nvis, L, P, Kp;
+    // the decoder reconstructs ndec of the nmask masked tokens (all of them unless the context was made by bvc_videomae_create_dual):
+    // Ld = nvis + ndec rows per clip, the visible tokens first
+    int ndec, Ld;
     Arena arena;
     Work w;
     // constants
@@ -103,14 +106,14 @@ struct bvc_ctx {
     bf16_t* wbf;       // bf16 copy of the flat parameters
     bool shadow_valid = false;   // set by bvc_videomae_shadow for ONE forward: wbf already matches the parameters it will be given
     const float* params = nullptr;
-    int *vis_idx, *msk_idx, *status;
+    int *vis_idx, *dec_idx, *status;     // dec_idx [B][ndec]: the decoded masked tokens, ascending
     bf16_t* Ape;       // bf16 [B*nvis][Kp] gathered visible tubes
     Stack enc, dec;
     bf16_t* xe_bf;     // bf16 [B*nvis][D] encoder output
     float *meanf, *rstdf;
-    bf16_t* lnf;       // bf16 [B*nmask][Dd]
-    float* labels;     // f32 [B*nmask][P]
-    bf16_t* diff;      // bf16 [B*nmask][P]  logits - labels
+    bf16_t* lnf;       // bf16 [B*ndec][Dd]
+    float* labels;     // f32 [B*ndec][P]
+    bf16_t* diff;      // bf16 [B*ndec][P]  logits - labels
     float* partial;
     int npartial = 0;
     float *dres_enc, *dres_dec;
@@ -207,6 +210,10 @@ void bvc_videomae_destroy(bvc_ctx* c) {
 }
 
 int bvc_videomae_create(const bvc_videomae_config* cfg, int max_batch, int num_masked, bvc_ctx** out) {
+    return bvc_videomae_create_dual(cfg, max_batch, num_masked, num_masked, out);
+}
+
+int bvc_videomae_create_dual(const bvc_videomae_config* cfg, int max_batch, int num_masked, int num_decoded, bvc_ctx** out) {
     BVC_REQUIRE(cfg && out, "create: null argument");
     TRY(check_config(*cfg));
     BVC_REQUIRE(max_batch >= 1, "create: max_batch must be >= 1");
@@ -225,7 +232,15 @@ int bvc_videomae_create(const bvc_videomae_config* cfg, int max_batch, int num_m
         set_error("create: num_masked=%d must leave at least one visible and one masked token of %d", num_masked, c->L);
         return BVC_ERR_INVALID;
     }
-    const size_t B = max_batch, Mv = B * c->nvis, Md = B * c->L, Mm = B * c->nmask;
+    if (!(num_decoded >= 1 && num_decoded <= num_masked)) {
+        delete c;
+        set_error("create: num_decoded=%d must lie in [1, num_masked=%d]", num_decoded, num_masked);
+        return BVC_ERR_INVALID;
+    }
+    c->ndec = num_decoded;
+    c->Ld = c->nvis + num_decoded;
+    // decoder side: Md rows of Ld per clip, Mm decoded rows
+    const size_t B = max_batch, Mv = B * c->nvis, Md = B * c->Ld, Mm = B * c->ndec;
     const int D = cfg->hidden_size, Dd = cfg->decoder_hidden_size, I = cfg->intermediate_size, Id = cfg->decoder_intermediate_size;
     const int H = cfg->num_attention_heads, Hd = cfg->decoder_num_attention_heads;
     int rc = BVC_OK;
@@ -249,10 +264,10 @@ int bvc_videomae_create(const bvc_videomae_config* cfg, int max_batch, int num_m
     A(c->arena.alloc(&c->pos_dec, (size_t)c->L * Dd));
     A(c->arena.alloc(&c->wbf, (size_t)c->lay.total));
     A(c->arena.alloc(&c->vis_idx, Mv));
-    A(c->arena.alloc(&c->msk_idx, Mm));
-    // token 0 everywhere: a clip whose mask count differs from the context's leaves entries unwritten, and the gather kernels
+    A(c->arena.alloc(&c->dec_idx, Mm));
+    // token 0 everywhere: a clip whose mask (or decode) count differs from the context's leaves entries unwritten, and the gather kernels
     // must then read in-range indices (the status word flags the clip; the Python side raises on the next step)
-    if (hipMemset(c->vis_idx, 0, (size_t)Mv * sizeof(int)) != hipSuccess || hipMemset(c->msk_idx, 0, (size_t)Mm * sizeof(int)) != hipSuccess) {
+    if (hipMemset(c->vis_idx, 0, (size_t)Mv * sizeof(int)) != hipSuccess || hipMemset(c->dec_idx, 0, (size_t)Mm * sizeof(int)) != hipSuccess) {
         set_error("videomae_create: hipMemset of the token lists failed");
         bvc_videomae_destroy(c);
         return BVC_ERR_HIP;
@@ -260,7 +275,7 @@ int bvc_videomae_create(const bvc_videomae_config* cfg, int max_batch, int num_m
     A(c->arena.alloc(&c->status, 4));
     A(c->arena.alloc(&c->Ape, Mv * c->Kp));
     A(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, Mv, B * H * c->nvis));
-    A(alloc_stack(c->arena, c->dec, Dd, Id, Hd, cfg->decoder_num_hidden_layers, cfg->layer_norm_eps, Md, B * Hd * c->L));
+    A(alloc_stack(c->arena, c->dec, Dd, Id, Hd, cfg->decoder_num_hidden_layers, cfg->layer_norm_eps, Md, B * Hd * c->Ld));
     A(c->arena.alloc(&c->xe_bf, Mv * D));
     A(c->arena.alloc(&c->meanf, Mm));
     A(c->arena.alloc(&c->rstdf, Mm));
@@ -272,7 +287,7 @@ int bvc_videomae_create(const bvc_videomae_config* cfg, int max_batch, int num_m
     A(c->arena.alloc(&c->dres_dec, Md * Dd));
     const size_t MD = std::max(Mv * D, Md * Dd), MI = std::max(Mv * I, Md * Id);
     A(c->arena.alloc(&c->de2d, Mv * Dd));
-    A(alloc_work(c->arena, c->w, MD, MI, std::max(B * H * c->nvis, B * Hd * c->L),
+    A(alloc_work(c->arena, c->w, MD, MI, std::max(B * H * c->nvis, B * Hd * c->Ld),
                  std::max(ln_bwd_workspace_floats_upto((int)Mv, D), ln_bwd_workspace_floats_upto((int)Md, Dd))));
 #undef A
     std::vector<float> tab;
@@ -291,15 +306,21 @@ int bvc_videomae_forward(bvc_ctx* c, const float* pixels, const uint8_t* mask, i
 
 int bvc_videomae_forward_px(bvc_ctx* c, const void* pixels_any, const bvc_pixel_format* fmt, const uint8_t* mask, int batch,
                             const float* params, float* loss, float* logits, void* stream) {
+    return bvc_videomae_forward_dual(c, pixels_any, fmt, mask, nullptr, batch, params, loss, logits, stream);
+}
+
+int bvc_videomae_forward_dual(bvc_ctx* c, const void* pixels_any, const bvc_pixel_format* fmt, const uint8_t* mask, const uint8_t* decode_mask,
+                              int batch, const float* params, float* loss, float* logits, void* stream) {
     BVC_REQUIRE(c && pixels_any && mask && params && loss, "forward: null argument");
+    BVC_REQUIRE(decode_mask || c->ndec == c->nmask, "forward: the context decodes %d of %d masked tokens and needs a decode mask", c->ndec, c->nmask);
     PixelSrc pixels;
     TRY(pixel_src(pixels_any, fmt, c->cfg.num_channels, &pixels));
     BVC_REQUIRE(batch >= 1 && batch <= c->max_batch, "forward: batch %d outside [1, %d]", batch, c->max_batch);
     hipStream_t st = (hipStream_t)stream;
     const bvc_videomae_config& cf = c->cfg;
     const Layout& L = c->lay;
-    const int B = batch, nvis = c->nvis, nmask = c->nmask, Lq = c->L;
-    const int Mv = B * nvis, Mm = B * nmask;
+    const int B = batch, nvis = c->nvis, ndec = c->ndec, Lq = c->L, Ld = c->Ld;
+    const int Mv = B * nvis, Mm = B * ndec;
     const int D = cf.hidden_size, Dd = cf.decoder_hidden_size, P = c->P;
     c->have_forward = false;
     c->batch = B;
@@ -313,7 +334,8 @@ int bvc_videomae_forward_px(bvc_ctx* c, const void* pixels_any, const bvc_pixel_
     if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.total, st));
     c->shadow_valid = false;
     BVC_CHECK_HIP(hipMemsetAsync(c->status, 0, 16, st));
-    TRY(launch_mask_index(mask, B, Lq, nvis, nmask, c->vis_idx, c->msk_idx, c->status, st));
+    if (decode_mask) TRY(launch_dual_mask_index(mask, decode_mask, B, Lq, nvis, ndec, c->vis_idx, c->dec_idx, c->status, st));
+    else TRY(launch_mask_index(mask, B, Lq, nvis, ndec, c->vis_idx, c->dec_idx, c->status, st));
     TRY(launch_gather_patches(pixels, c->vis_idx, c->Ape, B, nvis, pg, st));
     {   // tube patch embedding of the visible tokens + bias + sinusoid (HF:109-124,164-177)
         GemmProblem p = gemm(c->Ape, (size_t)Mv * c->Kp, c->Kp, c->wbf + L.pe_w, (size_t)D * c->Kp, c->Kp, Mv, D, c->Kp, EPI_POS,
@@ -329,18 +351,18 @@ int bvc_videomae_forward_px(bvc_ctx* c, const void* pixels_any, const bvc_pixel_
     TRY(launch_gather_rows_bf16(c->enc.x_out, identity_rows(), c->xe_bf, Mv, D, st));
     {
         GemmProblem p = gemm(c->xe_bf, (size_t)Mv * D, D, c->wbf + L.e2d_w, (size_t)Dd * D, D, Mv, Dd, D, EPI_E2D, c->dec.act[0].x_in, Dd);
-        p.rowtok = c->vis_idx; p.pos = c->pos_dec; p.rin = nvis; p.rout = Lq;
+        p.rowtok = c->vis_idx; p.pos = c->pos_dec; p.rin = nvis; p.rout = Ld;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
-    TRY(launch_fill_masked(c->dec.act[0].x_in, params + L.mask_token, c->pos_dec, c->msk_idx, B, Lq, nvis, nmask, Dd, st));
+    TRY(launch_fill_masked(c->dec.act[0].x_in, params + L.mask_token, c->pos_dec, c->dec_idx, B, Ld, nvis, ndec, Dd, st));
     for (int i = 0; i < c->dec.nlayers; ++i) {
         float* xo = i + 1 < c->dec.nlayers ? c->dec.act[i + 1].x_in : c->dec.x_out;
-        TRY(layer_forward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, xo, B, Lq, st, i + 1 < c->dec.nlayers ? &L.dec[i + 1] : nullptr));
+        TRY(layer_forward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, xo, B, Ld, st, i + 1 < c->dec.nlayers ? &L.dec[i + 1] : nullptr));
     }
-    // last nmask tokens -> LayerNorm -> head, fused with the pixel-target MSE (HF:497-501,588-664)
-    const RowMap tail{nmask, Lq, nvis};
+    // last ndec tokens -> LayerNorm -> head, fused with the pixel-target MSE (HF:497-501,588-664)
+    const RowMap tail{ndec, Ld, nvis};
     TRY(launch_ln_fwd(c->dec.x_out, tail, params + L.norm_w, params + L.norm_b, c->lnf, c->meanf, c->rstdf, Mm, Dd, cf.decoder_norm_eps, st));
-    TRY(launch_labels(pixels, c->msk_idx, c->labels, B, nmask, pg, cf.norm_pix_loss, st));
+    TRY(launch_labels(pixels, c->dec_idx, c->labels, B, ndec, pg, cf.norm_pix_loss, st));
     {
         GemmProblem p = gemm(c->lnf, (size_t)Mm * Dd, Dd, c->wbf + L.head_w, (size_t)P * Dd, Dd, Mm, P, Dd, EPI_LOSS, c->diff, P);
         p.bias = params + L.head_b; p.labels = c->labels; p.partial = c->partial; p.C2 = logits;
@@ -359,8 +381,8 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
     hipStream_t st = (hipStream_t)stream;
     const bvc_videomae_config& cf = c->cfg;
     const Layout& L = c->lay;
-    const int B = c->batch, nvis = c->nvis, nmask = c->nmask, Lq = c->L;
-    const int Mv = B * nvis, Md = B * Lq, Mm = B * nmask;
+    const int B = c->batch, nvis = c->nvis, ndec = c->ndec, Ld = c->Ld;
+    const int Mv = B * nvis, Md = B * Ld, Mm = B * ndec;
     const int D = cf.hidden_size, Dd = cf.decoder_hidden_size, P = c->P;
     const bf16_t* W = c->wbf;
     const float* params = c->params;
@@ -385,16 +407,16 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
     // visible rows of the decoder stream receive no gradient from the head
     BVC_CHECK_HIP(hipMemsetAsync(c->dres_dec, 0, (size_t)Md * Dd * 4, st));
     BVC_CHECK_HIP(hipMemsetAsync(c->w.dyb[0], 0, (size_t)Md * Dd * 2, st));
-    const RowMap tail{nmask, Lq, nvis};
+    const RowMap tail{ndec, Ld, nvis};
     TRY(launch_ln_bwd(c->w.dln, c->dec.x_out, tail, c->meanf, c->rstdf, params + L.norm_w, c->dres_dec, 0, c->w.dyb[0],
                       G + L.norm_w, G + L.norm_b, c->w.ln_part, Mm, Dd, st));
     bucket(L.norm_w, L.total);
     for (int i = c->dec.nlayers - 1; i >= 0; --i) {
-        TRY(layer_backward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, c->dres_dec, G, B, Lq, st, on_bucket, user));
+        TRY(layer_backward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, c->dres_dec, G, B, Ld, st, on_bucket, user));
     }
     // decoder input: mask token, encoder_to_decoder
     TRY(launch_colsum_f32(c->dres_dec, tail, Mm, Dd, G + L.mask_token, st));
-    const RowMap headrows{nvis, Lq, 0};
+    const RowMap headrows{nvis, Ld, 0};
     TRY(launch_gather_rows_bf16(c->dres_dec, headrows, c->de2d, Mv, Dd, st));
     {
         GemmProblem p = gemm(c->de2d, (size_t)Mv * Dd, Dd, c->xe_bf, (size_t)Mv * D, D, Dd, D, Mv, EPI_F32, G + L.e2d_w, D);
@@ -428,7 +450,7 @@ int bvc_videomae_tap(bvc_ctx* c, const char* name, float* dst, int64_t capacity,
     BVC_REQUIRE(c && name && dst && numel, "tap: null argument");
     BVC_REQUIRE(c->batch > 0, "tap: no forward has run");
     const int B = c->batch;
-    const size_t Mv = (size_t)B * c->nvis, Md = (size_t)B * c->L, Mm = (size_t)B * c->nmask;
+    const size_t Mv = (size_t)B * c->nvis, Md = (size_t)B * c->Ld, Mm = (size_t)B * c->ndec;
     const int D = c->cfg.hidden_size, Dd = c->cfg.decoder_hidden_size;
     const float* src = nullptr;
     size_t n = 0;
@@ -932,6 +954,12 @@ int bvc_op_cast_bf16(const float* in, void* out, int64_t n, void* stream) {
 int bvc_op_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, void* stream) {
     BVC_REQUIRE(mask && vis_idx && msk_idx && status, "op_mask_index: null argument");
     return launch_mask_index(mask, B, L, nvis, nmask, vis_idx, msk_idx, status, (hipStream_t)stream);
+}
+int bvc_op_dual_mask_index(const uint8_t* mask, const uint8_t* decode_mask, int B, int L, int nvis, int ndec, int* vis_idx, int* dec_idx,
+                           int* status, void* stream) {
+    BVC_REQUIRE(mask && decode_mask && vis_idx && dec_idx && status, "op_dual_mask_index: null argument");
+    BVC_REQUIRE(B >= 1 && L >= 1 && nvis >= 1 && nvis < L && ndec >= 1 && ndec <= L - nvis, "op_dual_mask_index: bad counts (L %d, nvis %d, ndec %d)", L, nvis, ndec);
+    return launch_dual_mask_index(mask, decode_mask, B, L, nvis, ndec, vis_idx, dec_idx, status, (hipStream_t)stream);
 }
 int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A, int B, int nvis, int T, int C, int H, int W, int ts,
                           int ps, void* stream) {

@@ -92,13 +92,58 @@ def param_layout(config: VideoMAEConfig):
     return query_layout(L.bvc_videomae_param_count, L.bvc_videomae_param_numel, L.bvc_videomae_param_info, config.to_c())
 
 
+class _CountCheck:
+    """Set entries per clip of a [B, L] bool mask.  One host sync on the first call per mask shape; afterwards the cached count is
+    VERIFIED asynchronously: every call leaves `count(row 0) != cached`, `rows differ` (and the caller's own `bad` condition) as a
+    flag in a pinned word that the next call reads (a ratio change at the same shape - a validation phase, a curriculum stage -
+    raises on the following step instead of training on NaN losses that GradScaler silently skips)."""
+
+    def __init__(self, changed, unequal):
+        self.changed, self.unequal = changed, unequal
+        self.cache, self.pending, self.flag = {}, None, None
+
+    def __deepcopy__(self, memo):
+        return _CountCheck(self.changed, self.unequal)
+
+    def count(self, mask, strict, bad=None, bad_message=None):
+        """`bad`: a 0-dim bool tensor on the mask's device, a further condition under which the masks must not be used."""
+        key = tuple(mask.shape)
+        if self.pending is not None:
+            ev, flag, pkey = self.pending
+            ev.synchronize()                    # the previous step's check: long done, no stall
+            self.pending = None
+            if int(flag[0]) != 0:
+                self.cache.pop(pkey, None)
+                raise ValueError(self.changed)
+        if strict or key not in self.cache:
+            counts = mask.sum(dim=1)
+            n = int(counts[0])       # one host sync, first call per shape only
+            if not bool((counts == n).all()):
+                raise ValueError(self.unequal)
+            if bad is not None and bool(bad):
+                raise ValueError(bad_message)
+            self.cache[key] = n
+            return n
+        n = self.cache[key]
+        if self.flag is None:
+            self.flag = torch.zeros(1, dtype=torch.int32).pin_memory()
+        wrong = (mask.sum(dim=1) != n).any()
+        if bad is not None:
+            wrong = wrong | bad
+        self.flag.copy_(wrong.to(torch.int32).reshape(1), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(mask.device))
+        self.pending = (ev, self.flag, key)
+        return n
+
+
 class _Step(torch.autograd.Function):
-    """loss = step(pixels, mask); backward fills the flat gradient buffer and hands out views as .grad."""
+    """loss = step(pixels, mask[, decode mask]); backward fills the flat gradient buffer and hands out views as .grad."""
 
     @staticmethod
-    def forward(ctx, anchor, model, pixels, mask, want_logits):
+    def forward(ctx, anchor, model, pixels, mask, decode, want_logits):
         ctx.model = model
-        loss, logits = model._run_forward(pixels, mask, want_logits)
+        loss, logits = model._run_forward(pixels, mask, decode, want_logits)
         ctx.stamp = model._stamp_forward()
         ctx.mark_non_differentiable(logits) if logits is not None else None
         return loss, logits
@@ -107,7 +152,7 @@ class _Step(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_logits):
         ctx.model._check_generation(ctx.stamp)
         ctx.model._run_backward(grad_loss)
-        return None, None, None, None, None
+        return None, None, None, None, None, None
 
 
 class VideoMAEForPreTraining(FlatParamModule):
@@ -137,20 +182,31 @@ class VideoMAEForPreTraining(FlatParamModule):
         self._ctx = None
         self._ctx_key = None
         self.strict_mask_check = False
-        self._nmask_cache = {}
+        self._mask_count = _CountCheck(
+            "bool_masked_pos: the number of masked patches per clip changed (or differs between clips) "
+            "without a new model object; every clip must mask the same number of patches",
+            "every clip must have the same number of masked patches")
+        self._decode_count = _CountCheck(
+            "bool_decode_pos: the number of decoded patches per clip changed (or differs between clips, or a decoded patch was not "
+            "masked) without a new model object; every clip must decode the same number of its masked patches",
+            "every clip must have the same number of decoded patches")
         # uint8 pixel_values are normalised on the GPU as (u / 255 - mean) / std, the loader's ToTensor + Normalize
         # (homeview.py:221-230 uses 0.5 / 0.25 for every channel); f32 pixel_values are taken as already normalised
         self.pixel_mean, self.pixel_std = 0.5, 0.25
 
     # ---- library context
-    def _get_ctx(self, batch, nmask):
-        key = (batch, nmask, self._flat.device.index)
-        if self._ctx is not None and self._ctx_key[1] == nmask and self._ctx_key[2] == key[2] and self._ctx_key[0] >= batch:
+    def _get_ctx(self, batch, nmask, ndec=None):
+        """ndec: decoded masked tokens per clip (None: all nmask of them, the context bvc_videomae_create makes)."""
+        key = (batch, nmask, self._flat.device.index, nmask if ndec is None else ndec)
+        if self._ctx is not None and self._ctx_key[1:] == key[1:] and self._ctx_key[0] >= batch:
             return self._ctx
         self._free_ctx()
         h = ctypes.c_void_p()
         cc = self.config.to_c()
-        _lib.check(_lib.lib().bvc_videomae_create(ctypes.byref(cc), batch, nmask, ctypes.byref(h)), "bvc_videomae_create")
+        if ndec is None:
+            _lib.check(_lib.lib().bvc_videomae_create(ctypes.byref(cc), batch, nmask, ctypes.byref(h)), "bvc_videomae_create")
+        else:
+            _lib.check(_lib.lib().bvc_videomae_create_dual(ctypes.byref(cc), batch, nmask, ndec, ctypes.byref(h)), "bvc_videomae_create_dual")
         self._ctx, self._ctx_key = h, key
         return h
 
@@ -167,54 +223,39 @@ class VideoMAEForPreTraining(FlatParamModule):
 
     # ---- step
     def _num_masked(self, mask):
-        """Masked tokens per clip.  One host sync on the first call per mask shape; afterwards the cached count is VERIFIED
-        asynchronously: every call leaves `count(row 0) != cached` and `rows differ` flags in a pinned word that the next call
-        reads (a ratio change at the same shape - a validation phase, a curriculum stage - raises on the following step
-        instead of training on NaN losses that GradScaler silently skips)."""
-        key = tuple(mask.shape)
-        pend = getattr(self, "_nmask_pending", None)
-        if pend is not None:
-            ev, flag, pkey = pend
-            ev.synchronize()                    # the previous step's check: long done, no stall
-            self._nmask_pending = None
-            if int(flag[0]) != 0:
-                self._nmask_cache.pop(pkey, None)
-                raise ValueError("bool_masked_pos: the number of masked patches per clip changed (or differs between clips) "
-                                 "without a new model object; every clip must mask the same number of patches")
-        if self.strict_mask_check or key not in self._nmask_cache:
-            counts = mask.sum(dim=1)
-            n = int(counts[0])       # one host sync, first call per shape only
-            if not bool((counts == n).all()):
-                raise ValueError("every clip must have the same number of masked patches")
-            self._nmask_cache[key] = n
-            return n
-        n = self._nmask_cache[key]
-        if not hasattr(self, "_nmask_flag"):
-            self._nmask_flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-        bad = (mask.sum(dim=1) != n).any().to(torch.int32).reshape(1)
-        self._nmask_flag.copy_(bad, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(mask.device))
-        self._nmask_pending = (ev, self._nmask_flag, key)
-        return n
+        """Masked tokens per clip (_CountCheck: cached per mask shape, verified asynchronously; strict_mask_check verifies on the spot)."""
+        return self._mask_count.count(mask, self.strict_mask_check)
 
-    def _run_forward(self, pixels, mask, want_logits):
+    def _num_decoded(self, decode, mask):
+        """Decoded tokens per clip, checked as the mask's count is, together with the subset condition: a decoded token that the
+        encoder sees would leak its target into the loss (the library makes the loss NaN; here it raises - on the spot under
+        strict_mask_check or on the first call per shape, otherwise on the following step)."""
+        return self._decode_count.count(decode, self.strict_mask_check, bad=(decode & ~mask).any(),
+                                        bad_message="bool_decode_pos must be a subset of bool_masked_pos: a decoded patch is visible to the encoder")
+
+    def _run_forward(self, pixels, mask, decode, want_logits):
         cfg = self.config
         fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
         B = pixels.shape[0]
         nmask = self._num_masked(mask)
-        h = self._get_ctx(B, nmask)
+        ndec = self._num_decoded(decode, mask) if decode is not None else None
+        h = self._get_ctx(B, nmask, ndec)
         loss = torch.empty((), dtype=torch.float32, device=pixels.device)
         logits = None
         if want_logits:
             pd = cfg.num_channels * cfg.tubelet_size * cfg.patch_size ** 2
-            logits = torch.empty((B, nmask, pd), dtype=torch.float32, device=pixels.device)
+            logits = torch.empty((B, nmask if ndec is None else ndec, pd), dtype=torch.float32, device=pixels.device)
         self._shadow_vouch(h)
-        _lib.check(_lib.lib().bvc_videomae_forward_px(
-            h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, mask.data_ptr(), B, self._flat.data_ptr(),
-            loss.data_ptr(), logits.data_ptr() if logits is not None else None, _lib.current_stream_ptr()), "bvc_videomae_forward")
+        pf = ctypes.byref(fmt) if fmt is not None else None
+        lg = logits.data_ptr() if logits is not None else None
+        if decode is None:
+            _lib.check(_lib.lib().bvc_videomae_forward_px(h, pixels.data_ptr(), pf, mask.data_ptr(), B, self._flat.data_ptr(), loss.data_ptr(), lg,
+                                                          _lib.current_stream_ptr()), "bvc_videomae_forward")
+        else:
+            _lib.check(_lib.lib().bvc_videomae_forward_dual(h, pixels.data_ptr(), pf, mask.data_ptr(), decode.data_ptr(), B, self._flat.data_ptr(),
+                                                            loss.data_ptr(), lg, _lib.current_stream_ptr()), "bvc_videomae_forward_dual")
         self._shadow_established(h)
-        self._live = (pixels, mask)   # keep the borrowed inputs alive until backward
+        self._live = (pixels, mask, decode)   # keep the borrowed inputs alive until backward
         return loss, logits
 
     def _run_backward(self, grad_loss):
@@ -226,7 +267,12 @@ class VideoMAEForPreTraining(FlatParamModule):
         self._publish_grads(target, accumulate)
         self._live = None
 
-    def forward(self, pixel_values, bool_masked_pos=None, output_logits=False, **kwargs):
+    def forward(self, pixel_values, bool_masked_pos=None, bool_decode_pos=None, output_logits=False, **kwargs):
+        """``bool_decode_pos`` ([B, L] bool, optional): the masked tokens the decoder reconstructs (VideoMAE V2's decoder masking,
+        Wang et al., CVPR 2023, section 3.2).  True = the token gets a mask-token row in the decoder and is a loss target; it must be a
+        subset of ``bool_masked_pos`` with the same count ``ndec`` in every clip.  The decoder then runs on ``nvis + ndec`` tokens, the
+        loss is the mean over the decoded tokens and ``logits`` is ``[B, ndec, patch_dim]`` in ascending token order.  ``None``: every
+        masked token, the step transformers' VideoMAEForPreTraining computes."""
         if bool_masked_pos is None:
             raise ValueError("One must provided a boolean mask ")
         if not pixel_values.is_cuda:
@@ -243,17 +289,23 @@ class VideoMAEForPreTraining(FlatParamModule):
         pixels = pixel_values.detach()
         pixels = (pixels if pixels.dtype == torch.uint8 else pixels.to(dtype=torch.float32)).contiguous()
         mask = bool_masked_pos.to(device=pixels.device, dtype=torch.bool).contiguous()
+        decode = None
+        if bool_decode_pos is not None:
+            if tuple(bool_decode_pos.shape) != (B, cfg.seq_length):
+                raise ValueError(f"bool_decode_pos must have shape {(B, cfg.seq_length)}")
+            decode = bool_decode_pos.to(device=pixels.device, dtype=torch.bool).contiguous()
         anchor = self._param(self._names[0])
         if torch.is_grad_enabled() and anchor.requires_grad:
-            loss, logits = _Step.apply(anchor, self, pixels, mask, output_logits)
+            loss, logits = _Step.apply(anchor, self, pixels, mask, decode, output_logits)
         else:
-            loss, logits = self._run_forward(pixels, mask, output_logits)
+            loss, logits = self._run_forward(pixels, mask, decode, output_logits)
             self._stamp_forward()     # a pending backward of an earlier forward must not run on these activations
         return VideoMAEForPreTrainingOutput(loss=loss, logits=logits)
 
     # ---- parity probes
     def tap(self, name):
-        """f32 copy of a saved activation of the last forward ('embed', 'enc<i>', 'x_full', 'dec<i>', 'labels')."""
+        """f32 copy of a saved activation of the last forward ('embed', 'enc<i>', 'x_full', 'dec<i>', 'labels').  With a decode mask
+        'x_full' / 'dec<i>' hold nvis + ndec rows per clip and 'labels' ndec."""
         cfg = self.config
         cap = max(self._ctx_key[0] * cfg.seq_length * max(cfg.hidden_size, cfg.decoder_hidden_size),
                   self._ctx_key[0] * self._ctx_key[1] * cfg.num_channels * cfg.tubelet_size * cfg.patch_size ** 2)

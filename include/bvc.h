@@ -96,6 +96,12 @@ int bvc_videomae_param_info(const bvc_videomae_config* cfg, int index, char* nam
 /* Allocates workspaces for up to `max_batch` clips with `num_masked` masked tokens per clip. */
 int bvc_videomae_create(const bvc_videomae_config* cfg, int max_batch, int num_masked, bvc_ctx** out);
 void bvc_videomae_destroy(bvc_ctx* ctx);
+/* The same for a step that reconstructs only `num_decoded` of the `num_masked` masked tokens of every clip (1 <= num_decoded <=
+ * num_masked; decoder masking as in VideoMAE V2, Wang et al., CVPR 2023, section 3.2): the decoder runs on (seq_len - num_masked) +
+ * num_decoded rows per clip and the loss is taken on the decoded tokens.  bvc_videomae_create is the num_decoded == num_masked case.
+ * bvc_videomae_backward, _tap, _shadow and _destroy take such a context as they take any other; the taps "x_full" / "dec<i>" then have
+ * batch * (seq_len - num_masked + num_decoded) rows and "labels" batch * num_decoded. */
+int bvc_videomae_create_dual(const bvc_videomae_config* cfg, int max_batch, int num_masked, int num_decoded, bvc_ctx** out);
 
 /* Replaces `outputs = xmodel(inputs, bool_masked_pos=m); outputs.loss` (pretrain_videomae.py:301-302,
  * i.e. VideoMAEForPreTraining.forward, HF:531-671).
@@ -126,6 +132,17 @@ typedef struct bvc_pixel_format {
 } bvc_pixel_format;
 int bvc_videomae_forward_px(bvc_ctx* ctx, const void* pixels_dev, const bvc_pixel_format* fmt, const uint8_t* mask_dev, int batch,
                             const float* params_dev, float* loss_dev, float* logits_dev, void* stream);
+/* bvc_videomae_forward_px with a decode mask:
+ *   decode_mask_dev u8 [batch][seq_len], 1 = the token gets a mask-token row in the decoder and is a loss target; every row must hold
+ *                   exactly num_decoded ones, all of them on masked tokens.  NULL (contexts with num_decoded == num_masked only) =
+ *                   every masked token: exactly bvc_videomae_forward_px, the same launches and bits.
+ *   logits_dev      optional f32 [batch][num_decoded][patch_dim], rows in ascending token order
+ *   loss_dev        the mean over batch * num_decoded * patch_dim elements
+ * A row with another count, or with a decoded token that is visible to the encoder (its target would leak into the loss), makes the
+ * loss NaN (flag checked on the device, no host sync). */
+int bvc_videomae_forward_dual(bvc_ctx* ctx, const void* pixels_dev, const bvc_pixel_format* fmt, const uint8_t* mask_dev,
+                              const uint8_t* decode_mask_dev, int batch, const float* params_dev, float* loss_dev, float* logits_dev,
+                              void* stream);
 
 /* Replaces autograd's backward of the step (scaler.scale(loss).backward(), pretrain_videomae.py:312).
  *   grad_loss_dev f32 scalar on the device: d(objective)/d(loss) (GradScaler's scale)
@@ -454,6 +471,10 @@ int bvc_op_adam_step_segments(float* params, float* grads, float* exp_avg, float
 int bvc_op_nonfinite_check(const float* x, int64_t n, float* found_inf, void* stream);
 /* boolean mask -> ascending visible / masked token lists (the order x[~mask] / x[mask] produce, HF:121,578-579) */
 int bvc_op_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, void* stream);
+/* the same with a decode mask: the visible list and the ascending list of the ndec decoded tokens per clip; *status |= 1 when a clip's
+ * visible count is not nvis, its decoded count is not ndec, or a decoded token is not masked (vis_idx [B][nvis], dec_idx [B][ndec]) */
+int bvc_op_dual_mask_index(const uint8_t* mask, const uint8_t* decode_mask, int B, int L, int nvis, int ndec, int* vis_idx, int* dec_idx,
+                           int* status, void* stream);
 /* tube patches of the visible tokens in Conv3d weight order (HF:157-177) */
 int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A_bf16, int B, int nvis, int T, int C, int H, int W,
                           int ts, int ps, void* stream);

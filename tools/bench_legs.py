@@ -30,16 +30,19 @@ def jepa_gflop(embed_dim, depth, mlp_hidden, nctx=100, npred=25, nsets=4, tokens
     return (target + 3 * (context + predictor)) / 1e9
 
 
-def videomae_gflop(config, mask_ratio=0.9):
+def videomae_gflop(config, mask_ratio=0.9, decode_ratio=None):
     """Algorithmic GFLOP of one VideoMAE pre-training clip, BASELINE.md section 3's counting (202.295 for base): tube masking hides
     int(mask_ratio x patches per frame) patches of every frame; the patch embedding runs on the visible tokens and needs no input
-    gradient (2x), everything else - encoder, encoder-to-decoder, decoder on all tokens, head on the masked ones - counts 3x."""
+    gradient (2x), everything else - encoder, encoder-to-decoder, decoder on all tokens, head on the masked ones - counts 3x.
+    decode_ratio: the decoder reconstructs int(decode_ratio x masked per frame) masked patches of every frame (DecoderSubsetGenerator):
+    it then runs on the visible and those tokens only, the head on those."""
     c = config
     g = c.image_size // c.patch_size
     per, T = g * g, c.num_frames // c.tubelet_size
     L = T * per
     nmask = T * int(mask_ratio * per)
     nvis = L - nmask
+    ndec = nmask if decode_ratio is None else T * int(decode_ratio * int(mask_ratio * per))
     P = c.num_channels * c.tubelet_size * c.patch_size * c.patch_size
 
     def layers(n, d, i, count):
@@ -47,7 +50,7 @@ def videomae_gflop(config, mask_ratio=0.9):
     D, Dd = c.hidden_size, c.decoder_hidden_size
     patch = 2 * nvis * P * D
     rest = (layers(nvis, D, c.intermediate_size, c.num_hidden_layers) + 2 * nvis * D * Dd
-            + layers(L, Dd, c.decoder_intermediate_size, c.decoder_num_hidden_layers) + 2 * nmask * Dd * P)
+            + layers(nvis + ndec, Dd, c.decoder_intermediate_size, c.decoder_num_hidden_layers) + 2 * ndec * Dd * P)
     return (2 * patch + 3 * rest) / 1e9
 
 
@@ -108,9 +111,10 @@ def jepa_leg(bvc, dev, model="vit_large", batch=16, nctx=100, npred=25, warmup=6
             "tflops": round(gf * B / dt / 1e3, 1), "frac_of_mfma_peak": round(gf * B / dt / 1e3 / 2500.0, 4), "final_loss": round(loss, 5)}
 
 
-def videomae_leg(bvc, dev, arch="base", batch=16, warmup=5, steps=10, mask_ratio=0.9):
+def videomae_leg(bvc, dev, arch="base", batch=16, warmup=5, steps=10, mask_ratio=0.9, decode_ratio=None):
     """VideoMAE pre-training step of one VIDEOMAE_ARCHS size: synthetic 16 x 224^2 clips, tube masking at mask_ratio, bf16 autocast,
-    backward, fused SGD-Nesterov with GradScaler - the headline's step at another model size."""
+    backward, fused SGD-Nesterov with GradScaler - the headline's step at another model size.  decode_ratio: the decoder reconstructs
+    that share of every frame's masked patches (bool_decode_pos from DecoderSubsetGenerator); None = all of them, no decode mask."""
     torch.manual_seed(0)
     cfg = bvc.videomae_config(arch)
     model = bvc.VideoMAEForPreTraining(cfg).to(dev).train()
@@ -122,20 +126,26 @@ def videomae_leg(bvc, dev, arch="base", batch=16, warmup=5, steps=10, mask_ratio
     gen = torch.Generator().manual_seed(1234)
     clips = torch.randn(B, cfg.num_frames, 3, cfg.image_size, cfg.image_size, generator=gen).to(dev)
     mgen = bvc.TubeMaskingGenerator((T, g, g), mask_ratio, rng=np.random.RandomState(1234))
-    mask = torch.from_numpy(np.stack([mgen() for _ in range(B)])).bool().to(dev)
+    masks = [mgen() for _ in range(B)]
+    mask = torch.from_numpy(np.stack(masks)).bool().to(dev)
+    kw = {}
+    if decode_ratio is not None:
+        dgen = bvc.DecoderSubsetGenerator((T, g, g), decode_ratio, rng=np.random.RandomState(4321))
+        kw["bool_decode_pos"] = torch.from_numpy(np.stack([dgen(m) for m in masks])).bool().to(dev)
 
     def step():
         opt.zero_grad()
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            loss = model(clips, bool_masked_pos=mask).loss
+            loss = model(clips, bool_masked_pos=mask, **kw).loss
         scaler.scale(loss).backward()
         scaler.step(opt)
         scaler.update()
         return loss
 
     dt, loss = _timed(step, warmup, steps)
-    gf = videomae_gflop(cfg, mask_ratio)
-    return {"workload": f"VideoMAE-{arch} pre-training, 16x224^2 clips, mask {mask_ratio}, {B} clips/GPU, full step (fwd, bwd, SGD-Nesterov, "
+    gf = videomae_gflop(cfg, mask_ratio, decode_ratio)
+    dual = "" if decode_ratio is None else f", decoder on {decode_ratio} of the masked patches ({int(kw['bool_decode_pos'][0].sum())} per clip)"
+    return {"workload": f"VideoMAE-{arch} pre-training, 16x224^2 clips, mask {mask_ratio}{dual}, {B} clips/GPU, full step (fwd, bwd, SGD-Nesterov, "
                         "GradScaler)", "value": round(B / dt, 2), "unit": "clips/s", "ms_per_step": round(1e3 * dt, 3), "steps": steps,
             "gflop_per_clip": round(gf, 3), "tflops": round(gf * B / dt / 1e3, 1), "frac_of_mfma_peak": round(gf * B / dt / 1e3 / 2500.0, 4),
             "final_loss": round(loss, 5)}

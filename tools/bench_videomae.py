@@ -1,7 +1,10 @@
 """VideoMAE pre-training throughput of the VIDEOMAE_ARCHS sizes on one MI355X (tools/bench_legs.videomae_leg: synthetic 16 x 224^2
 clips, tube mask 0.9, bf16 autocast, backward, fused SGD-Nesterov, GradScaler).  One JSON line per (arch, batch) on stdout.
 
-    python tools/bench_videomae.py --arch small,base,large,huge --batch 16,64 [--steps 10] [--warmup 5]"""
+    python tools/bench_videomae.py --arch small,base,large,huge --batch 16,64 [--steps 10] [--warmup 5] [--decode-ratio 0.5]
+
+--decode-ratio R: the decoder reconstructs int(R x masked patches per frame) of every frame's masked patches (bool_decode_pos from
+DecoderSubsetGenerator, VideoMAE V2's decoder masking); off by default, and then no decode mask is passed."""
 import argparse
 import json
 import os
@@ -19,12 +22,14 @@ ap.add_argument("--arch", default="base", help="comma-separated VIDEOMAE_ARCHS k
 ap.add_argument("--batch", default="16", help="comma-separated clips per step")
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=5)
+ap.add_argument("--decode-ratio", type=float, default=None, help="share of the masked patches the decoder reconstructs (default: all, no decode mask)")
 args = ap.parse_args()
 ge.build()
 bvc = ge.load_package()
 dev = torch.device("cuda:0")
 for arch in args.arch.split(","):
     for b in (int(x) for x in args.batch.split(",")):
-        r = videomae_leg(bvc, dev, arch=arch, batch=b, warmup=args.warmup, steps=args.steps)
-        print(json.dumps({"arch": arch, "batch": b, **r}), flush=True)
+        r = videomae_leg(bvc, dev, arch=arch, batch=b, warmup=args.warmup, steps=args.steps, decode_ratio=args.decode_ratio)
+        extra = {} if args.decode_ratio is None else {"decode_ratio": args.decode_ratio}
+        print(json.dumps({"arch": arch, "batch": b, **extra, **r}), flush=True)
         torch.cuda.empty_cache()

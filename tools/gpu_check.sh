@@ -69,6 +69,7 @@ PY
     probe_step) run probe_step_b${BVC_BATCH:-256} 300 python tools/step_probe.py ;;
     simclr64) run simclr64 900 python -m pytest tests/test_gpu_simclr.py -m gpu -q -x -s -p no:cacheprovider -k "64_pairs" ;;
     attntests) run attntests 400 python -m pytest tests/test_gpu_ops.py -m gpu -q -x -p no:cacheprovider -k attention ;;
+    attnedges) run attnedges 300 python -m pytest tests/test_gpu_attention_edges.py -m gpu -q -p no:cacheprovider ;;
     lossdbg) run lossdbg 300 python tools/debug/g8_loss_dbg.py ;;
     dwab)  run dwab 400 python tools/ab/dw_tile_ab.py ;;
     dwbal) run dwbal 400 python tools/ab/dw_balance_ab.py ;;

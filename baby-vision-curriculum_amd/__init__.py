@@ -10,6 +10,7 @@ Host-side mirror of the model interface the reference's entry points use
 memory, streams, the optimiser object and torch.distributed only.
 """
 from . import _lib, _ops  # noqa: F401
+from ._ops import attention_probs  # noqa: F401
 from ._lib import use_deterministic_algorithms, are_deterministic_algorithms_enabled  # noqa: F401
 from .videomae import (VideoMAEConfig, VideoMAEForPreTraining, VideoMAEForPreTrainingOutput, VideoMAEForVideoClassification,  # noqa: F401
                        get_config, get_model, VIDEOMAE_ARCHS, videomae_config)

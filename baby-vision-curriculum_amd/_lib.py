@@ -104,6 +104,21 @@ def branch_drop(hidden_p, seed, offset, path_scale, rows_per_sample):
     return d
 
 
+class IntrospectC(ctypes.Structure):
+    """bvc_introspect (include/bvc.h): where a classification context delivers its per-layer outputs; either pointer may be null"""
+    _fields_ = [("hidden_states", c_void_p), ("attentions", c_void_p)]
+
+
+def introspect(hidden_states, attentions):
+    """An IntrospectC over two contiguous f32 device tensors ([L + 1][B][N][D], [L][B][H][N][N]), either None; None when both are."""
+    if hidden_states is None and attentions is None:
+        return None
+    o = IntrospectC()
+    o.hidden_states = hidden_states.data_ptr() if hidden_states is not None else None
+    o.attentions = attentions.data_ptr() if attentions is not None else None
+    return o
+
+
 BUCKET_FN = ctypes.CFUNCTYPE(None, c_int64, c_int64, c_void_p)
 
 # every symbol include/bvc.h declares: name -> (restype, argtypes)
@@ -135,6 +150,9 @@ SYMBOLS = {
     "bvc_videomae_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "bvc_videomae_encode_px": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PixelFormatC), c_int, c_void_p, c_void_p, c_void_p, c_float,
                                        c_void_p, c_void_p, c_void_p]),
+    "bvc_videomae_encode_ex": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PixelFormatC), c_int, c_void_p, c_void_p, c_void_p, c_float,
+                                       c_void_p, c_void_p, ctypes.POINTER(IntrospectC), c_void_p]),
+    "bvc_videomae_cls_introspect": (c_int, [c_void_p, ctypes.POINTER(IntrospectC), c_void_p]),
     "bvc_videomae_encoder_fc_norm_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_videomae_cls_create": (c_int, [ctypes.POINTER(VideoMAEConfigC), c_int, ctypes.POINTER(c_void_p)]),
     "bvc_videomae_cls_destroy": (None, [c_void_p]),
@@ -188,6 +206,7 @@ SYMBOLS = {
     "bvc_op_attention_fwd_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p]),
     "bvc_op_attention_bwd_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                             ctypes.c_float, c_void_p]),
+    "bvc_op_attention_probs": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p]),
     "bvc_op_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int, c_int, c_float, c_void_p]),
     "bvc_op_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

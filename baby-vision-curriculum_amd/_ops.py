@@ -75,3 +75,18 @@ def cast_bf16(x):
     _lib.check(_lib.lib().bvc_op_cast_bf16(x.float().data_ptr() if x.dtype != torch.float32 else x.data_ptr(), out.data_ptr(),
                                            x.numel(), _lib.current_stream_ptr()), "bvc_op_cast_bf16")
     return out
+
+
+def attention_probs(qkv, lse, B, N, H, head_dim, scale=None):
+    """softmax(q k^T scale) as f32 [B, H, N, N] (row = query, column = key) from a bf16 qkv [B * N, 3 * H * head_dim] and the lse
+    [B * H, N] (f32, log2 units) an attention forward wrote for it (bvc_op_attention_probs); scale None = 1 / sqrt(head_dim)."""
+    if qkv.dtype != torch.bfloat16 or lse.dtype != torch.float32 or not qkv.is_cuda or lse.device != qkv.device:
+        raise ValueError("attention_probs: qkv must be a bf16 and lse an f32 tensor on the same GPU")
+    if qkv.numel() != B * N * 3 * H * head_dim or lse.numel() != B * H * N:
+        raise ValueError(f"attention_probs: qkv / lse hold {qkv.numel()} / {lse.numel()} elements, expected "
+                         f"{B * N * 3 * H * head_dim} / {B * H * N}")
+    qkv, lse = qkv.contiguous(), lse.contiguous()
+    probs = torch.empty((B, H, N, N), dtype=torch.float32, device=qkv.device)
+    _lib.check(_lib.lib().bvc_op_attention_probs(qkv.data_ptr(), lse.data_ptr(), probs.data_ptr(), B, N, H, head_dim,
+                                                 0.0 if scale is None else float(scale), _lib.current_stream_ptr()), "bvc_op_attention_probs")
+    return probs

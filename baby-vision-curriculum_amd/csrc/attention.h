@@ -13,4 +13,7 @@ int launch_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, in
 int launch_attn_bwd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, const float* lse, float* delta,
                     bf16_t* dqkv, int B, int N, int H, int head_dim, hipStream_t stream, float softmax_scale = 0.f, int parts = 3);
 // parts: bit 0 = the dQ kernel (also writes delta = rowsum(dO * O)), bit 1 = the dK / dV kernel (reads delta); 3 = the backward
+// qkv + the lse a forward left -> probs f32 [B][H][N][N] = softmax(q k^T scale), row = query, column = key (attention_probs.hip)
+int launch_attn_probs(const bf16_t* qkv, const float* lse, float* probs, int B, int N, int H, int head_dim, hipStream_t stream,
+                      float softmax_scale = 0.f);
 }  // namespace bvc

@@ -541,10 +541,21 @@ int bvc_videomae_encode(bvc_encoder_ctx* c, const float* pixels, int batch, cons
     return bvc_videomae_encode_px(c, pixels, nullptr, batch, params, fc_norm_w, fc_norm_b, fc_norm_eps, tokens, pooled, stream);
 }
 
+// the softmax scale a stack passes to its attention launches: the true head's when the heads run zero-padded, the default otherwise
+static float stack_sm_scale(const Stack& s) { return s.hdp != s.hd ? 1.0f / sqrtf((float)s.hd) : 0.f; }
+
 int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc_pixel_format* fmt, int batch, const float* params,
                            const float* fc_norm_w, const float* fc_norm_b, float fc_norm_eps, float* tokens, float* pooled,
                            void* stream) {
-    BVC_REQUIRE(c && pixels_any && params && (tokens || pooled), "encode: null argument");
+    return bvc_videomae_encode_ex(c, pixels_any, fmt, batch, params, fc_norm_w, fc_norm_b, fc_norm_eps, tokens, pooled, nullptr, stream);
+}
+
+int bvc_videomae_encode_ex(bvc_encoder_ctx* c, const void* pixels_any, const bvc_pixel_format* fmt, int batch, const float* params,
+                           const float* fc_norm_w, const float* fc_norm_b, float fc_norm_eps, float* tokens, float* pooled,
+                           const bvc_introspect* out, void* stream) {
+    float* const hs = out ? out->hidden_states : nullptr;      // [L + 1][B][N][D]: the residual stream runs through it
+    float* const att = out ? out->attentions : nullptr;        // [L][B][H][N][N]
+    BVC_REQUIRE(c && pixels_any && params && (tokens || pooled || hs || att), "encode: null argument");
     PixelSrc pixels;
     TRY(pixel_src(pixels_any, fmt, c->cfg.num_channels, &pixels));
     BVC_REQUIRE(batch >= 1 && batch <= c->max_batch, "encode: batch %d outside [1, %d]", batch, c->max_batch);
@@ -560,7 +571,8 @@ int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc
     const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
     TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
     TRY(launch_gather_patches(pixels, c->idx_all, c->Ape, B, N, pg, st));
-    float* x = c->xa;
+    const size_t slot = (size_t)M * D;                         // one hidden state
+    float* x = hs ? hs : c->xa;                                // given hidden_states, slot 0 is the embedding output
     float* y = c->xb;
     {
         GemmProblem p = gemm(c->Ape, (size_t)M * P, P, c->wbf + L.pe_w, (size_t)D * P, P, M, D, P, EPI_POS, x, D);
@@ -569,11 +581,16 @@ int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc
     }
     const int nl = (int)L.enc.size();
     for (int i = 0; i < nl; ++i) {
-        float* dst = (i + 1 == nl && tokens) ? tokens : y;     // the last layer writes straight into the caller's buffer
+        // the last layer writes straight into the caller's buffer; with hidden_states, layer i reads slot i and writes slot i + 1
+        float* dst = hs ? hs + (size_t)(i + 1) * slot : (i + 1 == nl && tokens) ? tokens : y;
         c->w.drop_layer = i;     // one LayerAct serves every layer: the gate is keyed by the real layer
         TRY(layer_forward(c->w, c->st, 0, L.enc[i], x, dst, B, N, st));
+        if (att)
+            TRY(launch_attn_probs(c->st.act[0].qkv, c->st.act[0].lse, att + (size_t)i * B * c->st.H * N * N, B, N, c->st.H, c->st.hdp, st,
+                                  stack_sm_scale(c->st)));
         if (dst == y) std::swap(x, y); else x = dst;
     }
+    if (hs && tokens) BVC_CHECK_HIP(hipMemcpyAsync(tokens, x, slot * 4, hipMemcpyDeviceToDevice, st));
     c->drop.active = false;      // forward only: nothing follows that would need the gate
     c->pooled_batch = 0;
     if (pooled) {
@@ -748,6 +765,23 @@ int bvc_videomae_cls_backward(bvc_cls_ctx* c, const float* dpooled, float* G, fl
     return BVC_OK;
 }
 
+int bvc_videomae_cls_introspect(bvc_cls_ctx* c, const bvc_introspect* out, void* stream) {
+    BVC_REQUIRE(c && out, "cls_introspect: null argument");
+    if (!c->have_forward) { set_error("cls_introspect: no forward state (call it between bvc_videomae_cls_forward_px and its backward)"); return BVC_ERR_STATE; }
+    hipStream_t st = (hipStream_t)stream;
+    const int B = c->batch, N = c->L, D = c->cfg.hidden_size, H = c->enc.H, nl = c->enc.nlayers;
+    const size_t slot = (size_t)B * N * D;
+    if (out->hidden_states)
+        for (int i = 0; i <= nl; ++i)
+            BVC_CHECK_HIP(hipMemcpyAsync(out->hidden_states + (size_t)i * slot, i < nl ? c->enc.act[i].x_in : c->enc.x_out, slot * 4,
+                                         hipMemcpyDeviceToDevice, st));
+    if (out->attentions)
+        for (int i = 0; i < nl; ++i)
+            TRY(launch_attn_probs(c->enc.act[i].qkv, c->enc.act[i].lse, out->attentions + (size_t)i * B * H * N * N, B, N, H, c->enc.hdp, st,
+                                  stack_sm_scale(c->enc)));
+    return BVC_OK;
+}
+
 int bvc_videomae_cls_set_drop(bvc_cls_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
     BVC_REQUIRE(c, "cls_set_drop: null context");
     return set_drop(c->drop, drop, samples, "cls_set_drop", (hipStream_t)stream);
@@ -862,6 +896,11 @@ int bvc_op_attention_bwd_scaled(const void* qkv, const void* ctx_in, const void*
     BVC_REQUIRE(qkv && ctx_in && dctx && lse && delta && dqkv && softmax_scale >= 0.f, "op_attention_bwd_scaled: bad argument");
     return launch_attn_bwd((const bf16_t*)qkv, (const bf16_t*)ctx_in, (const bf16_t*)dctx, lse, delta, (bf16_t*)dqkv, B, N, H, head_dim,
                            (hipStream_t)stream, softmax_scale);
+}
+int bvc_op_attention_probs(const void* qkv, const float* lse, float* probs, int B, int N, int H, int head_dim, float softmax_scale,
+                           void* stream) {
+    BVC_REQUIRE(qkv && lse && probs && softmax_scale >= 0.f, "op_attention_probs: bad argument");
+    return launch_attn_probs((const bf16_t*)qkv, lse, probs, B, N, H, head_dim, (hipStream_t)stream, softmax_scale);
 }
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y,
                          float* mean, float* rstd, int M, int D, float eps, void* stream) {

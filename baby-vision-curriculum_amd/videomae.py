@@ -31,14 +31,20 @@ class VideoMAEConfig:
     ``hidden_dropout_prob`` (transformers' field: dropout on the two branch outputs of every encoder layer, HF:270-274, 316-320) and
     the extension ``drop_path_rate`` (stochastic depth, rates ``linspace(0, rate, depth)`` as the published fine-tuning recipes use
     it) take effect in ``VideoMAEForVideoClassification`` in train mode.  ``attention_probs_dropout_prob`` must stay 0.0: dropout on
-    the attention probabilities is not implemented, and a config that asks for it is refused instead of training another model."""
+    the attention probabilities is not implemented, and a config that asks for it is refused instead of training another model.
+
+    ``output_hidden_states`` / ``output_attentions`` (default False) are the defaults of the keywords of the same name of
+    ``VideoMAEForVideoClassification.forward``."""
 
     def __init__(self, image_size=224, patch_size=16, num_channels=3, num_frames=16, tubelet_size=2,
                  hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                  hidden_act="gelu", layer_norm_eps=1e-12, initializer_range=0.02, qkv_bias=True,
                  use_mean_pooling=True, decoder_num_attention_heads=6, decoder_hidden_size=384,
                  decoder_num_hidden_layers=4, decoder_intermediate_size=1536, norm_pix_loss=True,
-                 hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, drop_path_rate=0.0, **kwargs):
+                 hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, drop_path_rate=0.0,
+                 output_hidden_states=False, output_attentions=False, **kwargs):
+        # transformers' PretrainedConfig fields: what VideoMAEForVideoClassification.forward returns when the call leaves them None
+        self.output_hidden_states, self.output_attentions = bool(output_hidden_states), bool(output_attentions)
         if attention_probs_dropout_prob:
             raise ValueError(f"attention_probs_dropout_prob={attention_probs_dropout_prob}: dropout on the attention probabilities is not "
                              "implemented (only 0.0)")
@@ -273,6 +279,11 @@ class VideoMAEForPreTraining(FlatParamModule):
         subset of ``bool_masked_pos`` with the same count ``ndec`` in every clip.  The decoder then runs on ``nvis + ndec`` tokens, the
         loss is the mean over the decoded tokens and ``logits`` is ``[B, ndec, patch_dim]`` in ascending token order.  ``None``: every
         masked token, the step transformers' VideoMAEForPreTraining computes."""
+        for name in ("output_hidden_states", "output_attentions"):
+            if kwargs.get(name):
+                raise NotImplementedError(f"VideoMAEForPreTraining.forward({name}=True) is not implemented: read single activations of the "
+                                          "last forward with tap('embed' / 'enc<i>' / 'x_full' / 'dec<i>'); per-layer outputs exist on "
+                                          "VideoMAEForVideoClassification")
         if bool_masked_pos is None:
             raise ValueError("One must provided a boolean mask ")
         if not pixel_values.is_cuda:
@@ -360,6 +371,46 @@ def classification_loss(config, logits, labels):
     raise ValueError(f"problem_type {config.problem_type!r} unknown")
 
 
+def attentions_nbytes(config, batch):
+    """Bytes of ``output_attentions`` for ``batch`` clips: L * B * H * N * N f32 (base size: 1.42 GB per clip)."""
+    n = config.seq_length
+    return int(config.num_hidden_layers) * int(batch) * int(config.num_attention_heads) * n * n * 4
+
+
+def hidden_states_nbytes(config, batch):
+    """Bytes of ``output_hidden_states`` for ``batch`` clips: (L + 1) * B * N * D f32 (base size: 62.6 MB per clip)."""
+    return (int(config.num_hidden_layers) + 1) * int(batch) * config.seq_length * int(config.hidden_size) * 4
+
+
+def free_device_memory(device):
+    """Bytes an allocation on ``device`` can still get: what the driver reports free plus what torch's allocator holds unused."""
+    free, _total = torch.cuda.mem_get_info(device)
+    return int(free) + int(torch.cuda.memory_reserved(device)) - int(torch.cuda.memory_allocated(device))
+
+
+def alloc_introspection(config, batch, device, want_hidden, want_attentions):
+    """(hidden_states f32 [L + 1, B, N, D] or None, attentions f32 [L, B, H, N, N] or None): one allocation each.  The attention maps
+    are large (``attentions_nbytes``), so their size is checked against the free device memory before anything is allocated."""
+    hs = att = None
+    L, N = int(config.num_hidden_layers), config.seq_length
+    if want_attentions:
+        need, free = attentions_nbytes(config, batch), free_device_memory(device)
+        if need > free:
+            raise ValueError(f"output_attentions needs {need} bytes ({need / 2 ** 30:.2f} GiB = layers {L} x clips {batch} x heads "
+                             f"{config.num_attention_heads} x {N} x {N} tokens x 4) but {free} bytes of device memory are free: pass "
+                             "fewer clips per call")
+        att = torch.empty((L, batch, int(config.num_attention_heads), N, N), dtype=torch.float32, device=device)
+    if want_hidden:
+        hs = torch.empty((L + 1, batch, N, int(config.hidden_size)), dtype=torch.float32, device=device)
+    return hs, att
+
+
+def _mark_detached(ctx, *tensors):
+    live = [t for t in tensors if t is not None]
+    if live:
+        ctx.mark_non_differentiable(*live)
+
+
 class _TrainCtx:
     """The fine-tuning context of one model.  Owned: destroyed with its holder, and a deepcopy starts without one."""
 
@@ -386,34 +437,34 @@ class _ClsTrain(torch.autograd.Function):
     buffer (views as .grad) and returns fc_norm's gradients to autograd."""
 
     @staticmethod
-    def forward(ctx, anchor, fc_w, fc_b, model, pixels, want_tokens):
+    def forward(ctx, anchor, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False):
         ctx.model = model
-        pooled, tokens = model._run_train_forward(pixels, fc_w, fc_b, want_tokens)
+        pooled, tokens, hs, att = model._run_train_forward(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions)
         ctx.stamp = model._stamp_forward()
-        ctx.mark_non_differentiable(tokens) if tokens is not None else None
-        return pooled, tokens
+        _mark_detached(ctx, tokens, hs, att)
+        return pooled, tokens, hs, att
 
     @staticmethod
-    def backward(ctx, dpooled, _dtokens):
+    def backward(ctx, dpooled, _dtokens, _dhs, _datt):
         ctx.model._check_generation(ctx.stamp)
         dw, db = ctx.model._run_train_backward(dpooled)
-        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None
+        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None
 
 
 class _FcNormProbe(torch.autograd.Function):
     """The inference context's encode (today's call, the same bits) with fc_norm under autograd: the linear-probe case."""
 
     @staticmethod
-    def forward(ctx, fc_w, fc_b, model, pixels, want_tokens):
+    def forward(ctx, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False):
         ctx.model = model
-        pooled, tokens = model._run_encode(pixels, fc_w, fc_b, want_tokens)
+        pooled, tokens, hs, att = model._run_encode(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions)
         ctx.stamp = model._stamp_forward()
         ctx.save_for_backward(fc_w)
-        ctx.mark_non_differentiable(tokens) if tokens is not None else None
-        return pooled, tokens
+        _mark_detached(ctx, tokens, hs, att)
+        return pooled, tokens, hs, att
 
     @staticmethod
-    def backward(ctx, dpooled, _dtokens):
+    def backward(ctx, dpooled, _dtokens, _dhs, _datt):
         ctx.model._check_generation(ctx.stamp)
         (fc_w,) = ctx.saved_tensors
         m = ctx.model
@@ -422,7 +473,7 @@ class _FcNormProbe(torch.autograd.Function):
         dw, db = torch.empty_like(w), torch.empty_like(w)
         _lib.check(_lib.lib().bvc_videomae_encoder_fc_norm_backward(m._ctx, g.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                                                     _lib.current_stream_ptr()), "bvc_videomae_encoder_fc_norm_backward")
-        return dw if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None
+        return dw if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None, None, None
 
 
 class VideoMAEForVideoClassification(FlatParamModule):
@@ -556,25 +607,32 @@ class VideoMAEForVideoClassification(FlatParamModule):
     def _fc_norm_args(self, fc_w, fc_b, dev):
         return fc_w.detach().to(device=dev, dtype=torch.float32).contiguous(), fc_b.detach().to(device=dev, dtype=torch.float32).contiguous()
 
-    def _run_encode(self, pixels, fc_w, fc_b, want_tokens):
+    def _run_encode(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False):
         cfg = self.config
         B, dev = pixels.shape[0], pixels.device
         fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
+        hs, att = alloc_introspection(cfg, B, dev, want_hidden, want_attentions)
         h = self._get_ctx(B)
         w, b = self._fc_norm_args(fc_w, fc_b, dev)
         pooled = torch.empty((B, cfg.hidden_size), dtype=torch.float32, device=dev)
-        tokens = torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev) if want_tokens else None
+        tokens = None
+        if want_tokens:     # with hidden states the residual stream already ends in the caller's array: its last slot
+            tokens = hs[-1] if hs is not None else torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev)
         self._arm_gate(_lib.lib().bvc_videomae_encoder_set_drop, h, B, dev)     # train mode on the forward-only path: the same gate
-        _lib.check(_lib.lib().bvc_videomae_encode_px(
-            h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
-            float(self.fc_norm.eps),
-            tokens.data_ptr() if tokens is not None else None, pooled.data_ptr(), _lib.current_stream_ptr()), "bvc_videomae_encode")
-        return pooled, tokens
+        args = (h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
+                float(self.fc_norm.eps), tokens.data_ptr() if tokens is not None and hs is None else None, pooled.data_ptr())
+        out = _lib.introspect(hs, att)
+        if out is None:
+            _lib.check(_lib.lib().bvc_videomae_encode_px(*args, _lib.current_stream_ptr()), "bvc_videomae_encode")
+        else:
+            _lib.check(_lib.lib().bvc_videomae_encode_ex(*args, ctypes.byref(out), _lib.current_stream_ptr()), "bvc_videomae_encode_ex")
+        return pooled, tokens, hs, att
 
-    def _run_train_forward(self, pixels, fc_w, fc_b, want_tokens):
+    def _run_train_forward(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False):
         cfg = self.config
         B, dev = pixels.shape[0], pixels.device
         fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
+        hs, att = alloc_introspection(cfg, B, dev, want_hidden, want_attentions)
         h = self._get_train_ctx(B)
         w, b = self._fc_norm_args(fc_w, fc_b, dev)
         pooled = torch.empty((B, cfg.hidden_size), dtype=torch.float32, device=dev)
@@ -587,7 +645,10 @@ class VideoMAEForVideoClassification(FlatParamModule):
             "bvc_videomae_cls_forward")
         self._shadow_established(h)
         self._live = pixels       # keep the borrowed input alive until backward
-        return pooled, tokens
+        out = _lib.introspect(hs, att)
+        if out is not None:       # what every layer kept for the backward: its input, and the qkv / lse its attention ran on
+            _lib.check(_lib.lib().bvc_videomae_cls_introspect(h, ctypes.byref(out), _lib.current_stream_ptr()), "bvc_videomae_cls_introspect")
+        return pooled, tokens, hs, att
 
     def _run_train_backward(self, dpooled):
         target, accumulate = self._grad_target()
@@ -601,10 +662,20 @@ class VideoMAEForVideoClassification(FlatParamModule):
         self._live = None
         return dw.to(self.fc_norm.weight.dtype), db.to(self.fc_norm.bias.dtype)
 
-    def forward(self, pixel_values=None, labels=None, output_last_hidden_state=False, **kwargs):
+    def forward(self, pixel_values=None, labels=None, output_last_hidden_state=False, output_hidden_states=None, output_attentions=None,
+                **kwargs):
+        """``output_hidden_states`` / ``output_attentions`` (None = ``config.output_hidden_states`` / ``config.output_attentions``, as in
+        transformers): ``hidden_states`` is a tuple of L + 1 tensors (B, N, D) - the embedding output, then every layer's output -
+        and ``attentions`` a tuple of L tensors (B, H, N, N) of softmax probabilities (row = query).  Each tuple is f32 views of one
+        allocation; ``attentions`` takes ``attentions_nbytes(config, B)`` bytes and the call raises ValueError before allocating when
+        that exceeds the free device memory.  Unlike transformers', both are detached (no gradient flows through them, as through
+        ``last_hidden_state``).  They are those of the forward that ran: in train mode they include the drop-path / dropout gates.
+        The logits are the same bits with or without them."""
         if pixel_values is None or not pixel_values.is_cuda:
             raise _lib.BvcError("VideoMAEForVideoClassification runs on a GPU only (libbvc_hip.so has no CPU path)")
         cfg = self.config
+        want_hs = bool(getattr(cfg, "output_hidden_states", False) if output_hidden_states is None else output_hidden_states)
+        want_att = bool(getattr(cfg, "output_attentions", False) if output_attentions is None else output_attentions)
         B, T, C, H, W = pixel_values.shape
         if C != cfg.num_channels or H != cfg.image_size or W != cfg.image_size or T != cfg.num_frames:
             raise ValueError(f"Input size ({T}x{C}x{H}*{W}) doesn't match model ({cfg.num_frames}x{cfg.num_channels}x{cfg.image_size}*{cfg.image_size}).")
@@ -617,21 +688,23 @@ class VideoMAEForVideoClassification(FlatParamModule):
         fc_w, fc_b = self.fc_norm.weight, self.fc_norm.bias
         if classification_path(self.training, grad, trainable) == "train":
             anchor = next(self._param(n) for n in self._names if self._param(n).requires_grad)
-            pooled, tokens = _ClsTrain.apply(anchor, fc_w, fc_b, self, pixels, output_last_hidden_state)
+            pooled, tokens, hs, att = _ClsTrain.apply(anchor, fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att)
         else:
             if grad and trainable and not self._warned_eval_grad:
                 self._warned_eval_grad = True
                 warnings.warn("VideoMAEForVideoClassification in eval mode: the encoder receives no gradient (call .train() to "
                               "fine-tune it); fc_norm and the classifier still do", stacklevel=2)
             if grad and (fc_w.requires_grad or fc_b.requires_grad):
-                pooled, tokens = _FcNormProbe.apply(fc_w, fc_b, self, pixels, output_last_hidden_state)
+                pooled, tokens, hs, att = _FcNormProbe.apply(fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att)
             else:
                 with torch.no_grad():
-                    pooled, tokens = self._run_encode(pixels, fc_w, fc_b, output_last_hidden_state)
+                    pooled, tokens, hs, att = self._run_encode(pixels, fc_w, fc_b, output_last_hidden_state, want_hs, want_att)
                 self._stamp_forward()     # a pending backward of an earlier forward must not run on overwritten state
         logits = self.classifier(pooled)
         loss = classification_loss(cfg, logits, labels) if labels is not None else None
-        return ImageClassifierOutput(loss=loss, logits=logits, last_hidden_state=tokens)
+        return ImageClassifierOutput(loss=loss, logits=logits, last_hidden_state=tokens,
+                                     hidden_states=tuple(hs.unbind(0)) if hs is not None else None,
+                                     attentions=tuple(att.unbind(0)) if att is not None else None)
 
 
 # The VideoMAE (v1) pre-training shapes: (hidden, layers, heads, decoder hidden, decoder heads).  All use patch 16, tubelet 2,

@@ -208,6 +208,30 @@ int bvc_videomae_cls_backward(bvc_cls_ctx* ctx, const float* dpooled_dev, float*
 /* as bvc_videomae_shadow (the copy covers the encoder's parameters) */
 int bvc_videomae_cls_shadow(bvc_cls_ctx* ctx, int valid, void** shadow_bf16, int64_t* numel);
 
+/* Per-layer outputs of the two classification contexts: output_hidden_states / output_attentions of
+ * VideoMAEForVideoClassification.forward (HF VideoMAEEncoder.forward collects them layer by layer).  L = num_hidden_layers,
+ * N = seq_len, D = hidden_size, H = num_attention_heads; either pointer may be NULL (NULL struct = neither):
+ *   hidden_states f32 [L + 1][batch][N][D]   slot 0 = the embedding output (patch embedding + position table), slot i + 1 = the
+ *                                            output of layer i - of the forward that ran, gates of a set_drop included
+ *   attentions    f32 [L][batch][H][N][N]    softmax(q k^T / sqrt(D / H)) of layer i, row = query, column = key (bvc_op_attention_probs
+ *                                            on the layer's qkv and lse, at the stack's attention width with the true head's scale)
+ * bvc_videomae_encode_ex is bvc_videomae_encode_px with these outputs: given hidden_states, the embedding product writes slot 0 and
+ * layer i reads slot i and writes slot i + 1 - the same launches as without it, on other pointers, and no copy for the hidden states
+ * themselves.  last_hidden_state then IS slot L: a caller that wants both should read it there and pass tokens_dev = NULL (the Python
+ * shim does); a non-NULL tokens_dev is still served, by one device-to-device copy of slot L.  Given attentions, one attn_probs_kernel
+ * launch follows each layer.  out == NULL or both members NULL: exactly
+ * bvc_videomae_encode_px.  bvc_videomae_cls_introspect is valid between a bvc_videomae_cls_forward_px of the same context and
+ * its backward (BVC_ERR_STATE otherwise): it copies each layer's kept residual stream and recomputes the probabilities from each
+ * layer's kept qkv and lse; the forward and the backward themselves are unchanged. */
+typedef struct bvc_introspect {
+    float* hidden_states;
+    float* attentions;
+} bvc_introspect;
+int bvc_videomae_encode_ex(bvc_encoder_ctx* ctx, const void* pixels_dev, const bvc_pixel_format* fmt, int batch,
+                           const float* params_dev, const float* fc_norm_w, const float* fc_norm_b, float fc_norm_eps,
+                           float* tokens_dev, float* pooled_dev, const bvc_introspect* out, void* stream);
+int bvc_videomae_cls_introspect(bvc_cls_ctx* ctx, const bvc_introspect* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Stochastic depth and hidden dropout: a gate on the two residual branches of every pre-LN layer of a context,
  *     h     = x_in + g1 .* (proj(ctx) + b_o)        g(row, col) = path_scale[layer][branch][row / rows_per_sample]
@@ -398,6 +422,13 @@ int bvc_op_attention_fwd_scaled(const void* qkv, void* ctx_out, float* lse, int 
                                 void* stream);
 int bvc_op_attention_bwd_scaled(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta_scratch,
                                 void* dqkv, int B, int N, int H, int head_dim, float softmax_scale, void* stream);
+/* The attention probabilities the forward never stores (HF:181-206 eager attention_probs, before dropout): probs f32 [B][H][N][N],
+ * row = query, column = key, = exp2(q.k * scale * log2 e - lse[query]) from the same qkv and the lse (log2 units) that
+ * bvc_op_attention_fwd / _fwd_scaled wrote for it; softmax_scale as for the _scaled entry points (0 = 1/sqrt(head_dim)).  Every one of
+ * the B * H * N * N elements is written (64-bit addressing: the output may exceed 4 GiB; qkv may not), nothing else is.  No atomics:
+ * the same bits on every run. */
+int bvc_op_attention_probs(const void* qkv, const float* lse, float* probs, int B, int N, int H, int head_dim, float softmax_scale,
+                           void* stream);
 /* nn.LayerNorm forward/backward (HF:336-337,484); rows may be strided by (rin, rout, roff), rin<=0 = dense */
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y_bf16,
                          float* mean, float* rstd, int M, int D, float eps, void* stream);

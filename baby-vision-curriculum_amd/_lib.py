@@ -77,12 +77,12 @@ class GemmDesc(ctypes.Structure):
         ("a_bytes", ctypes.c_uint32), ("b_bytes", ctypes.c_uint32),
         ("alpha", c_float), ("alpha_dev", c_void_p),
         ("epi", c_int), ("split_k", c_int),
-        ("C", c_void_p), ("ldc", c_int), ("C2", c_void_p),
-        ("bias", c_void_p), ("resid", c_void_p), ("aux", c_void_p), ("ldaux", c_int),
+        ("C", c_void_p), ("ldc", c_int), ("seg_rows", c_int), ("C2", c_void_p),
+        ("bias", c_void_p), ("resid", c_void_p), ("aux", c_void_p), ("ldaux", c_int), ("seg_stride", c_int),
         ("rowtok", c_void_p), ("pos", c_void_p), ("labels", c_void_p), ("partial", c_void_p),
         ("rin", c_int), ("rout", c_int),
         ("rowsum", c_void_p),
-        ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_mean", c_void_p), ("ln_rstd", c_void_p), ("ln_eps", c_float),
+        ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_mean", c_void_p), ("ln_rstd", c_void_p), ("ln_eps", c_float), ("seg_off", c_int),
         ("ln_x", c_void_p), ("ln_part", c_void_p), ("ln_dgamma", c_void_p), ("ln_dbeta", c_void_p),
     ]
 
@@ -310,7 +310,7 @@ def check(rc, what=""):
 
 
 def set_option(name, value):
-    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1, "head_pad" 0 / 1, "deterministic" 0 / 1 (what
+    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1, "head_pad" 0 / 1, "dec_tail" 0 / 1, "deterministic" 0 / 1 (what
     bvc.use_deterministic_algorithms and torch.use_deterministic_algorithms switch; the library's raw flag - the next library call
     after either of those changes resets it to their OR).  Returns the previous value."""
     old = lib().bvc_get_option(name.encode())

@@ -16,4 +16,12 @@ int launch_attn_bwd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, co
 // qkv + the lse a forward left -> probs f32 [B][H][N][N] = softmax(q k^T scale), row = query, column = key (attention_probs.hip)
 int launch_attn_probs(const bf16_t* qkv, const float* lse, float* probs, int B, int N, int H, int head_dim, hipStream_t stream,
                       float softmax_scale = 0.f);
+// Query window: the queries are rows q_off .. q_off + Nq - 1 of every clip, the keys all N rows.  Q is read (dQ written) at the physical
+// rows of the full qkv / dqkv; ctx, dctx, lse and delta are compact - [B*Nq][D] and [B*H][Nq].  The backward takes a window that ends
+// with the clip (q_off + Nq == N) and writes exact zeros into the q columns of the rows in front of it; dK / dV cover all N rows.
+bool attn_window_ok(int head_dim);
+int launch_attn_fwd_win(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, int H, int head_dim, int q_off, int Nq, hipStream_t stream,
+                        float softmax_scale = 0.f);
+int launch_attn_bwd_win(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, const float* lse, float* delta, bf16_t* dqkv, int B, int N,
+                        int H, int head_dim, int q_off, int Nq, hipStream_t stream, float softmax_scale = 0.f);
 }  // namespace bvc

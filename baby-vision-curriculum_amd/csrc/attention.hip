@@ -345,107 +345,29 @@ __device__ __forceinline__ void tail_reduce(char* buf, const TailSplit& ts, int 
     }
 }
 
+// Query window (WIN): the queries are rows q_off .. q_off + Nq - 1 of every clip's N rows (the last decoder layer of the VideoMAE
+// pre-training step needs the decoded rows only, stack.h LayerTail), the keys stay all N rows.  Q (and, in the backward, dQ) sit at the
+// physical rows b N + q_off + i of the full qkv / dqkv; everything else that is indexed by the query - ctx, lse, dctx, delta - is
+// COMPACT: [B Nq][D] and [B H][Nq].  WIN = false is the identity window (0, N) at compile time: those instantiations are the kernels
+// they were.
 // grid ceil(N/128) * B*H (1-D, see attn_block); 256 threads; wave w owns queries q0 + 32 w .. + 31
+
 template <int HD, int NW = 4>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                           float* __restrict__ lse, int N, int H, int D,
                                                           uint32_t qkv_bytes, float scale_log2, int remap) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages x (K image + V image)
-    constexpr int HI = img_hd(HD);   // the image width (96 for 80 / 88)
-    constexpr int IMG = 64 * HI * 2, STG = 2 * IMG, SUB = 32 * HI * 2;
-    const AS3 char* lds = (const AS3 char*)smem;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int tile_, bh;
-    attn_block((N + 32 * NW - 1) / (32 * NW), remap, tile_, bh);
-    const int b = bh / H, head = bh % H;
-    const int ld = 3 * D;
-    const TailSplit ts = tail_split<NW>(N, tile_, wave);
-    const int qi = tile_ * (32 * NW) + ts.own * 32 + (lane & 31);   // this lane's query
-    const int h = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(qkv, qkv_bytes);
-    const FragAddr<HI> fa = make_frag_addr<HI>(lane);
-    const int gm = ts.gs - 1;
-    auto mine = [&](int sub) { return (sub & gm) == ts.part; };      // does this wave take 32-key sub-tile `sub`?
-
-    bf16x8 qf[HI / 16];   // Q^T fragments (B operand of S^T = K Q^T): Q[qi][16 step + 8 h + 0..7]
-    {
-        const bf16_t* qrow = qkv + (size_t)(b * N + min(qi, N - 1)) * ld + head * HD + 8 * h;
-#pragma unroll
-        for (int st = 0; st < HI / 16; ++st) qf[st] = load8_head<HD, HI>(qrow + 16 * st, 16 * st + 8 * h);
-    }
-    FwdState<HI> st;
-#pragma unroll
-    for (int t = 0; t < HI / 32; ++t) st.o[t] = zero16();
-    st.m_run = -INFINITY; st.l_run = 0.f;
-
-    const int nkt = (N + 63) >> 6;
-    const int krow0 = b * N;
-    auto issue = [&](int kt, int stage) {
-        stage64<HI, NW, HD>(rs, krow0 + kt * 64, ld, D + head * HD, smem + stage * STG, wave, lane);
-        stage64<HI, NW, HD>(rs, krow0 + kt * 64, ld, 2 * D + head * HD, smem + stage * STG + IMG, wave, lane);
-    };
-#pragma unroll
-    for (int stq = 0; stq < HI / 16; ++stq) settle(qf[stq]);
-    issue(0, 0);
-    for (int kt = 0; kt < nkt; kt += 2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (kt + 1 < nkt) issue(kt + 1, 1);
-        if (mine(2 * kt)) fwd_subtile<HI, 0, IMG>(lds, fa, qf, st, kt * 64, N, h, scale_log2);
-        if (kt * 64 + 32 < N && mine(2 * kt + 1)) fwd_subtile<HI, SUB, IMG + SUB>(lds, fa, qf, st, kt * 64 + 32, N, h, scale_log2);
-        if (kt + 1 >= nkt) break;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (kt + 2 < nkt) issue(kt + 2, 0);
-        if (mine(2 * kt + 2)) fwd_subtile<HI, STG, STG + IMG>(lds, fa, qf, st, kt * 64 + 64, N, h, scale_log2);
-        if (kt * 64 + 96 < N && mine(2 * kt + 3)) fwd_subtile<HI, STG + SUB, STG + IMG + SUB>(lds, fa, qf, st, kt * 64 + 96, N, h, scale_log2);
-    }
-    if (ts.gs > 1) {      // workgroup-uniform: merge the parts of a query tile (flash-decoding style: common maximum, rescaled sums)
-        AS3 float* cl = (AS3 float*)smem;
-        constexpr int NO = HI / 32 * 16, SLOT = (NO + 2) * 64;
-        __syncthreads();
-        if (ts.part > 0) {
-            AS3 float* w = cl + ((ts.part - 1) * ts.valid + ts.own) * SLOT + lane;
-#pragma unroll
-            for (int t = 0; t < HI / 32; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) w[(t * 16 + r) * 64] = st.o[t][r];
-            w[NO * 64] = st.m_run;
-            w[(NO + 1) * 64] = st.l_run;
-        }
-        __syncthreads();
-        if (ts.part == 0) {
-            for (int p = 1; p < ts.gs; ++p) {
-                const AS3 float* w = cl + ((p - 1) * ts.valid + ts.own) * SLOT + lane;
-                const float m_p = w[NO * 64], l_p = w[(NO + 1) * 64];
-                const float m_new = fmaxf(st.m_run, m_p);
-                const float a = st.m_run == -INFINITY ? 0.f : fast_exp2(st.m_run - m_new);     // (a part that saw no key: -inf, weight 0)
-                const float c = m_p == -INFINITY ? 0.f : fast_exp2(m_p - m_new);
-                st.m_run = m_new;
-                st.l_run = st.l_run * a + l_p * c;
-#pragma unroll
-                for (int t = 0; t < HI / 32; ++t)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) st.o[t][r] = st.o[t][r] * a + w[(t * 16 + r) * 64] * c;
-            }
-        }
-    }
-    const float l_tot = xhalf_sum(st.l_run);
-    const float inv = 1.f / l_tot;
-    if (qi < N && ts.part == 0) {
-        bf16_t* orow = ctx + (size_t)(b * N + qi) * D + head * HD;
-#pragma unroll
-        for (int t = 0; t < HI / 32; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * t + 8 * g + 4 * h;
-                if (HD != HI && d >= HD) continue;     // past a narrower head
-                uint2 a = {pack2bf(st.o[t][4 * g] * inv, st.o[t][4 * g + 1] * inv), pack2bf(st.o[t][4 * g + 2] * inv, st.o[t][4 * g + 3] * inv)};
-                *reinterpret_cast<uint2*>(orow + d) = a;
-            }
-        if (h == 0) lse[(size_t)bh * N + qi] = st.m_run + log2f(l_tot);
-    }
+    constexpr bool WIN = false;
+    const int q_off_ = 0, Nq_ = N;
+#include "attention_fwd_body.inc"
+}
+// grid ceil(Nq/128) * B*H
+template <int HD>
+__global__ __launch_bounds__(256, 2) void attn_fwd_win_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
+                                                              float* __restrict__ lse, int N, int H, int D,
+                                                              uint32_t qkv_bytes, float scale_log2, int remap, int q_off_, int Nq_) {
+    constexpr bool WIN = true;
+    constexpr int NW = 4;
+#include "attention_fwd_body.inc"
 }
 
 // ============================================================================ dQ
@@ -478,94 +400,26 @@ __device__ __forceinline__ void dq_subtile(const AS3 char* lds, const FragAddr<H
 }
 
 // grid (ceil(N/128), B*H); wave w owns 32 queries; loops over key tiles (K and V staged)
+// WIN (the window ends with the clip: q_off + Nq == N): the first ceil(q_off / 128) blocks of a (clip, head) own the rows in front of the
+// window, whose dQ is exactly zero - they store the zeros and leave; the others tile the window.
+
 template <int HD>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                              const bf16_t* __restrict__ ctx, const float* __restrict__ lse,
                                                              float* __restrict__ delta, bf16_t* __restrict__ dqkv, int N, int H, int D,
                                                              uint32_t qkv_bytes, float scale, float scale_log2, int remap) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int HI = img_hd(HD);
-    constexpr int IMG = 64 * HI * 2, STG = 2 * IMG, SUB = 32 * HI * 2;
-    const AS3 char* lds = (const AS3 char*)smem;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int tile_, bh;
-    attn_block((N + 127) >> 7, remap, tile_, bh);
-    const int b = bh / H, head = bh % H;
-    const int ld = 3 * D;
-    const TailSplit ts = tail_split(N, tile_, wave);      // the ragged last block: idle waves share the key loop of the owners
-    const int qi = tile_ * 128 + ts.own * 32 + (lane & 31);
-    const int qc = min(qi, N - 1);
-    const int h = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(qkv, qkv_bytes);
-    const FragAddr<HI> fa = make_frag_addr<HI>(lane);
-    const int gm = ts.gs - 1;
-    auto mine = [&](int sub) { return (sub & gm) == ts.part; };
-
-    bf16x8 qf[HI / 16], dof[HI / 16];
-    float del_q = 0.f;
-    {
-        const bf16_t* qrow = qkv + (size_t)(b * N + qc) * ld + head * HD + 8 * h;
-        const bf16_t* drow = dctx + (size_t)(b * N + qc) * D + head * HD + 8 * h;
-        const bf16_t* orow_in = ctx + (size_t)(b * N + qc) * D + head * HD + 8 * h;
-#pragma unroll
-        for (int st = 0; st < HI / 16; ++st) {
-            qf[st] = load8_head<HD, HI>(qrow + 16 * st, 16 * st + 8 * h);
-            dof[st] = load8_head<HD, HI>(drow + 16 * st, 16 * st + 8 * h);
-            // delta = rowsum(dO * O) of this query (the softmax-gradient correction): the two half-waves hold disjoint halves
-            // of the row, so it costs one more 16-B load per step here instead of a pass of its own over dO and O
-            const bf16x8 of = load8_head<HD, HI>(orow_in + 16 * st, 16 * st + 8 * h);     // (past the head: 0 * 0 terms)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) del_q += bf2f((bf16_t)dof[st][j]) * bf2f((bf16_t)of[j]);
-        }
-    }
-    del_q += __shfl_xor(del_q, 32, 64);
-    if (h == 0 && qi < N && ts.part == 0) delta[(size_t)bh * N + qi] = -del_q;     // NEGATED: the dK/dV kernel, launched after this one, starts its dP chain from it
-    float nlse = -lse[(size_t)bh * N + qc];
-#pragma unroll
-    for (int stq = 0; stq < HI / 16; ++stq) { settle(qf[stq]); settle(dof[stq]); }
-    settle(nlse); settle(del_q);
-    f32x16 ndel;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ndel[r] = -del_q;
-    f32x16 dq[HI / 32];
-#pragma unroll
-    for (int t = 0; t < HI / 32; ++t) dq[t] = zero16();
-
-    const int nkt = (N + 63) >> 6;
-    const int krow0 = b * N;
-    auto issue = [&](int kt, int stage) {
-        stage64<HI, 4, HD>(rs, krow0 + kt * 64, ld, D + head * HD, smem + stage * STG, wave, lane);
-        stage64<HI, 4, HD>(rs, krow0 + kt * 64, ld, 2 * D + head * HD, smem + stage * STG + IMG, wave, lane);
-    };
-    issue(0, 0);
-    for (int kt = 0; kt < nkt; kt += 2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (kt + 1 < nkt) issue(kt + 1, 1);
-        if (mine(2 * kt)) dq_subtile<HI, 0, IMG>(lds, fa, qf, dof, dq, kt * 64, N, h, scale_log2, nlse, ndel);
-        if (kt * 64 + 32 < N && mine(2 * kt + 1)) dq_subtile<HI, SUB, IMG + SUB>(lds, fa, qf, dof, dq, kt * 64 + 32, N, h, scale_log2, nlse, ndel);
-        if (kt + 1 >= nkt) break;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (kt + 2 < nkt) issue(kt + 2, 0);
-        if (mine(2 * kt + 2)) dq_subtile<HI, STG, STG + IMG>(lds, fa, qf, dof, dq, kt * 64 + 64, N, h, scale_log2, nlse, ndel);
-        if (kt * 64 + 96 < N && mine(2 * kt + 3))
-            dq_subtile<HI, STG + SUB, STG + IMG + SUB>(lds, fa, qf, dof, dq, kt * 64 + 96, N, h, scale_log2, nlse, ndel);
-    }
-    if (ts.gs > 1) tail_reduce<HI / 32>(smem, ts, lane, dq);
-    if (qi < N && ts.part == 0) {
-        bf16_t* orow = dqkv + (size_t)(b * N + qi) * ld + head * HD;
-#pragma unroll
-        for (int t = 0; t < HI / 32; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * t + 8 * g + 4 * h;
-                if (HD != HI && d >= HD) continue;
-                uint2 a = {pack2bf(dq[t][4 * g] * scale, dq[t][4 * g + 1] * scale), pack2bf(dq[t][4 * g + 2] * scale, dq[t][4 * g + 3] * scale)};
-                *reinterpret_cast<uint2*>(orow + d) = a;
-            }
-    }
+    constexpr bool WIN = false;
+    const int q_off_ = 0, Nq_ = N;
+#include "attention_dq_body.inc"
+}
+// grid (ceil(q_off/128) + ceil(Nq/128)) * B*H
+template <int HD>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_win_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+                                                                 const bf16_t* __restrict__ ctx, const float* __restrict__ lse,
+                                                                 float* __restrict__ delta, bf16_t* __restrict__ dqkv, int N, int H, int D,
+                                                                 uint32_t qkv_bytes, float scale, float scale_log2, int remap, int q_off_, int Nq_) {
+    constexpr bool WIN = true;
+#include "attention_dq_body.inc"
 }
 
 // (the single-wave 96-query dQ experiment of round 2 - 3-4 % at the decoder shape, not adopted, profiles/r02_h_attention_single_wave.txt -
@@ -670,93 +524,27 @@ __device__ __forceinline__ void dkdv_subtile(const AS3 char* lds, const FragAddr
 // grid (ceil(N/128), B*H); wave w owns 32 keys; loops over query tiles (Q, dO, lse, delta staged)
 // HD = 128 (ViT-Ti predictor only): K, V fragments and the dK^T / dV^T accumulators do not fit 256 registers (it spilled 128 B per
 // lane), so that instantiation runs one workgroup per CU with the whole register file
+// WIN: the query loop covers the window only - the Q image comes from the physical rows b N + q_off + ..., the dO image, lse and
+// -delta from the compact rows (dctx_bytes / stat_bytes are the compact extents)
+
 template <int HD>
 __global__ __launch_bounds__(256, img_hd(HD) > 96 ? 1 : 2) void attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                bf16_t* __restrict__ dqkv, int N, int H, int D,
                                                                uint32_t qkv_bytes, uint32_t dctx_bytes, uint32_t stat_bytes,
                                                                float scale, float scale_log2, int remap) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int HI = img_hd(HD);
-    constexpr int IMG = 64 * HI * 2, SUB = 32 * HI * 2, STG = 2 * IMG + 512;
-    const AS3 char* lds = (const AS3 char*)smem;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int tile_, bh;
-    attn_block((N + 127) >> 7, remap, tile_, bh);
-    const int b = bh / H, head = bh % H;
-    const int ld = 3 * D;
-    const TailSplit ts = tail_split(N, tile_, wave);      // the ragged last key block: idle waves share the query loop of the owners
-    const int ki = tile_ * 128 + ts.own * 32 + (lane & 31);   // this lane's key
-    const int kc = min(ki, N - 1);
-    const int h = lane >> 5;
-    const int gm = ts.gs - 1;
-    auto mine = [&](int sub) { return (sub & gm) == ts.part; };
-    const __amdgpu_buffer_rsrc_t rq = make_rsrc(qkv, qkv_bytes);
-    const __amdgpu_buffer_rsrc_t rd = make_rsrc(dctx, dctx_bytes);
-    const __amdgpu_buffer_rsrc_t rl = make_rsrc(lse, stat_bytes);
-    const __amdgpu_buffer_rsrc_t re = make_rsrc(delta, stat_bytes);
-    const FragAddr<HI> fa = make_frag_addr<HI>(lane);
-
-    bf16x8 kf[HI / 16], vf[HI / 16];   // B operands of S = Q K^T and dP = dO V^T
-    {
-        const bf16_t* krow = qkv + (size_t)(b * N + kc) * ld + D + head * HD + 8 * h;
-#pragma unroll
-        for (int st = 0; st < HI / 16; ++st) {
-            kf[st] = load8_head<HD, HI>(krow + 16 * st, 16 * st + 8 * h);
-            vf[st] = load8_head<HD, HI>(krow + D + 16 * st, 16 * st + 8 * h);
-        }
-    }
-#pragma unroll
-    for (int stq = 0; stq < HI / 16; ++stq) { settle(kf[stq]); settle(vf[stq]); }
-    f32x16 dk[HI / 32], dv[HI / 32];
-#pragma unroll
-    for (int t = 0; t < HI / 32; ++t) { dk[t] = zero16(); dv[t] = zero16(); }
-
-    const int nqt = (N + 63) >> 6;
-    const int qrow0 = b * N;
-    auto issue = [&](int qt, int stage) {
-        char* dst = smem + stage * STG;
-        stage64<HI, 4, HD>(rq, qrow0 + qt * 64, ld, head * HD, dst, wave, lane);
-        stage64<HI, 4, HD>(rd, qrow0 + qt * 64, D, head * HD, dst + IMG, wave, lane);
-        if (wave == 0)
-            glds4(rl, (uint32_t)(((size_t)bh * N + qt * 64 + lane) * 4), (uint32_t)(size_t)((AS3 char*)dst) + 2 * IMG);
-        if (wave == 1)
-            glds4(re, (uint32_t)(((size_t)bh * N + qt * 64 + lane) * 4), (uint32_t)(size_t)((AS3 char*)dst) + 2 * IMG + 256);
-    };
-    issue(0, 0);
-    for (int qt = 0; qt < nqt; qt += 2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (qt + 1 < nqt) issue(qt + 1, 1);
-        if (mine(2 * qt)) dkdv_subtile<HI, 0, 2 * IMG>(lds, fa, kf, vf, dk, dv, qt * 64, N, h, scale_log2);
-        if (qt * 64 + 32 < N && mine(2 * qt + 1)) dkdv_subtile<HI, SUB, 2 * IMG + 128>(lds, fa, kf, vf, dk, dv, qt * 64 + 32, N, h, scale_log2);
-        if (qt + 1 >= nqt) break;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (qt + 2 < nqt) issue(qt + 2, 0);
-        if (mine(2 * qt + 2)) dkdv_subtile<HI, STG, STG + 2 * IMG>(lds, fa, kf, vf, dk, dv, qt * 64 + 64, N, h, scale_log2);
-        if (qt * 64 + 96 < N && mine(2 * qt + 3)) dkdv_subtile<HI, STG + SUB, STG + 2 * IMG + 128>(lds, fa, kf, vf, dk, dv, qt * 64 + 96, N, h, scale_log2);
-    }
-    if (ts.gs > 1) {      // (one accumulator set at a time: three partial sets of 8 KiB fit the 33 KiB ring, six do not)
-        tail_reduce<HI / 32>(smem, ts, lane, dk);
-        tail_reduce<HI / 32>(smem, ts, lane, dv);
-    }
-    if (ki < N && ts.part == 0) {
-        bf16_t* krow = dqkv + (size_t)(b * N + ki) * ld + D + head * HD;
-        bf16_t* vrow = krow + D;
-#pragma unroll
-        for (int t = 0; t < HI / 32; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * t + 8 * g + 4 * h;
-                if (HD != HI && d >= HD) continue;
-                uint2 a = {pack2bf(dk[t][4 * g] * scale, dk[t][4 * g + 1] * scale), pack2bf(dk[t][4 * g + 2] * scale, dk[t][4 * g + 3] * scale)};
-                *reinterpret_cast<uint2*>(krow + d) = a;
-                uint2 e = {pack2bf(dv[t][4 * g], dv[t][4 * g + 1]), pack2bf(dv[t][4 * g + 2], dv[t][4 * g + 3])};
-                *reinterpret_cast<uint2*>(vrow + d) = e;
-            }
-    }
+    constexpr bool WIN = false;
+    const int q_off_ = 0, Nq_ = N;
+#include "attention_dkdv_body.inc"
+}
+template <int HD>
+__global__ __launch_bounds__(256, img_hd(HD) > 96 ? 1 : 2) void attn_bwd_dkdv_win_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+                                                               const float* __restrict__ lse, const float* __restrict__ delta,
+                                                               bf16_t* __restrict__ dqkv, int N, int H, int D,
+                                                               uint32_t qkv_bytes, uint32_t dctx_bytes, uint32_t stat_bytes,
+                                                               float scale, float scale_log2, int remap, int q_off_, int Nq_) {
+    constexpr bool WIN = true;
+#include "attention_dkdv_body.inc"
 }
 
 // ============================================================================ whole-head backward for short sequences (round 4)
@@ -1131,6 +919,47 @@ int launch_attn_bwd(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, co
         case 128: return bwd_hd<128>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
         default: return bwd_hd<64>(qkv, ctx, dctx, lse, delta, dqkv, B, N, H, stream, sm_scale, parts);
     }
+}
+
+// ---- query-window launches (head_dim 64: the width the 384-wide decoder of every shipped VideoMAE configuration runs at)
+bool attn_window_ok(int head_dim) { return head_dim == 64; }
+
+int launch_attn_fwd_win(const bf16_t* qkv, bf16_t* ctx, float* lse, int B, int N, int H, int head_dim, int q_off, int Nq, hipStream_t stream,
+                        float sm_scale) {
+    BVC_REQUIRE(B > 0 && N > 0 && H > 0, "attn_fwd_win: empty shape");
+    BVC_REQUIRE(attn_window_ok(head_dim), "attn_fwd_win: head_dim %d has no query-window kernel (64)", head_dim);
+    BVC_REQUIRE(q_off >= 0 && Nq > 0 && q_off + Nq <= N, "attn_fwd_win: window (%d, %d) outside the %d rows", q_off, Nq, N);
+    BVC_REQUIRE((size_t)B * N * 3 * H * head_dim * 2 < 0xffffffffull, "attn_fwd_win: qkv larger than 4 GiB");
+    constexpr int HD = 64;
+    const int D = H * HD;
+    const float scale_log2 = (sm_scale > 0.f ? sm_scale : 1.0f / sqrtf((float)HD)) * 1.4426950408889634f;
+    const dim3 grid((unsigned)(((Nq + 127) / 128) * B * H));
+    hipLaunchKernelGGL(attn_fwd_win_kernel<HD>, grid, dim3(256), 4 * 64 * HD * 2, stream, qkv, ctx, lse, N, H, D,
+                       (uint32_t)((size_t)B * N * 3 * D * 2), scale_log2, xcd_remap(), q_off, Nq);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_attn_bwd_win(const bf16_t* qkv, const bf16_t* ctx, const bf16_t* dctx, const float* lse, float* delta, bf16_t* dqkv, int B, int N,
+                        int H, int head_dim, int q_off, int Nq, hipStream_t stream, float sm_scale) {
+    BVC_REQUIRE(B > 0 && N > 0 && H > 0, "attn_bwd_win: empty shape");
+    BVC_REQUIRE(attn_window_ok(head_dim), "attn_bwd_win: head_dim %d has no query-window kernel (64)", head_dim);
+    BVC_REQUIRE(q_off >= 0 && Nq > 0 && q_off + Nq == N, "attn_bwd_win: the window (%d, %d) must end with the %d rows", q_off, Nq, N);
+    BVC_REQUIRE((size_t)B * N * 3 * H * head_dim * 2 < 0xffffffffull, "attn_bwd_win: qkv larger than 4 GiB");
+    constexpr int HD = 64;
+    const int D = H * HD;
+    const uint32_t bytes = (uint32_t)((size_t)B * N * 3 * D * 2);
+    const float scale = sm_scale > 0.f ? sm_scale : 1.0f / sqrtf((float)HD), scale_log2 = scale * 1.4426950408889634f;
+    const int remap = xcd_remap();
+    // dQ first (it leaves -delta for the dK/dV kernel), with the zero blocks of the rows in front of the window
+    const dim3 gq((unsigned)((((q_off + 127) / 128) + ((Nq + 127) / 128)) * B * H));
+    hipLaunchKernelGGL(attn_bwd_dq_win_kernel<HD>, gq, dim3(256), 4 * 64 * HD * 2, stream, qkv, dctx, ctx, lse, delta, dqkv, N, H, D, bytes,
+                       scale, scale_log2, remap, q_off, Nq);
+    const dim3 gk((unsigned)(((N + 127) / 128) * B * H));
+    hipLaunchKernelGGL(attn_bwd_dkdv_win_kernel<HD>, gk, dim3(256), 2 * (2 * 64 * HD * 2 + 512), stream, qkv, dctx, lse, delta, dqkv, N, H, D, bytes,
+                       (uint32_t)((size_t)B * Nq * D * 2), (uint32_t)((size_t)B * H * Nq * 4), scale, scale_log2, remap, q_off, Nq);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
 }
 
 }  // namespace bvc

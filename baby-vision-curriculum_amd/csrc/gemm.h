@@ -50,7 +50,9 @@ constexpr int kMaxGroup = 4;
 //               go to a workspace slab with plain stores, a separate pass adds them in index order (launch_gemm, rowops.hip)
 //   head_pad:   1 = heads of 80 / 88 dims run zero-padded to 96 in HBM (padded weight copies, pad / unpad launches per layer call), as
 //               before the in-place attention instantiations; 0 (default) = in place.  Read when a stack is allocated (A/B only)
-struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; int deterministic = 0; int head_pad = 0; };
+//   dec_tail:   1 (default) = the last decoder layer of the VideoMAE pre-training step runs everything behind its qkv product on the decoded
+//               rows only (stack.h LayerTail) when the shapes allow; 0 = on all rows, as before that mode existed (A/B)
+struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; int deterministic = 0; int head_pad = 0; int dec_tail = 1; };
 Options& options();
 
 // Workspace of the deterministic mode: library-owned, grow-only, one buffer per (device, stream) - kernels on one stream use it in

@@ -445,7 +445,16 @@ int launch_gemm(const GemmProblem* probs, int nprob, GemmLayout layout, int tile
         BVC_REQUIRE(p.C && p.C2 && p.ln_mean && p.ln_rstd && p.ln_gamma, "launch_gemm: LayerNorm epilogue with a null output / statistic / scale");
         if (p.epi == EPI_RESID_LN) BVC_REQUIRE(layout == GEMM_NT && p.resid && p.ln_beta, "launch_gemm: RESID_LN is an NT product with a residual and a LayerNorm bias");
         if (p.epi == EPI_DLN) BVC_REQUIRE(layout == GEMM_NN && p.ln_x && p.ln_part && p.ln_dgamma && p.ln_dbeta, "launch_gemm: DLN is an NN product with the LayerNorm input, partial scratch and parameter gradients");
+        // the segment map shifts the base of the mapped side array's buffer descriptor (gemm8.hip): a bad map would defeat its range check
+        if (p.seg_rows != 0)
+            BVC_REQUIRE(p.seg_rows > 0 && p.seg_rows % 128 == 0 && p.M % p.seg_rows == 0 && p.seg_off >= 0 && p.seg_stride > 0 &&
+                            (long long)p.seg_off + p.seg_rows <= (long long)p.seg_stride,
+                        "launch_gemm: bad segment map (seg_rows %d: a multiple of 128 that divides M = %d; seg_off %d + seg_rows <= seg_stride %d)",
+                        p.seg_rows, p.M, p.seg_off, p.seg_stride);
         tile_cfg = 12;
+    } else {
+        for (int i = 0; i < nprob; ++i)
+            BVC_REQUIRE(probs[i].seg_rows == 0, "launch_gemm: a segment map (seg_rows %d) exists for BVC_EPI_RESID_LN / BVC_EPI_DLN only", probs[i].seg_rows);
     }
     // K = 384 products with a plain bf16 output (decoder / predictor qkv): the A-stationary kernel (gemm_as.hip), whose epilogue runs under
     // the next N tile's MFMAs.  Same-process A/B against the kernels picked below (profiles/r05_l_as_ab_batches.txt, r05_i_as_ab_b256.txt):

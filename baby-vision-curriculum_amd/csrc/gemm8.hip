@@ -560,6 +560,15 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
         // trip per chunk, ~14 us per 256 x 256 tile.)
         const int m0 = cu.m0, n0 = cu.n0;
         const int epi = p.epi, Mrows = p.M, Ncols = p.N, ldc = p.ldc;
+        // segment map of the row epilogues (bvc_gemm_desc::seg_*): how far, in rows, the mapped side array's copy of this tile lies
+        // past row m0 - a scalar per unit (a 128-row tile never straddles a segment), folded into that array's descriptor base
+        int seg_shift = 0;
+        if constexpr (EC == 4 || EC == 5) {
+            if (p.seg_rows > 0) {
+                const int upc = p.seg_rows >> 7, u = m0 >> 7, c = u / upc;
+                seg_shift = __builtin_amdgcn_readfirstlane(c * p.seg_stride + p.seg_off + ((u - c * upc) << 7) - m0);
+            }
+        }
         const float alpha = p.alpha_dev ? p.alpha * p.alpha_dev[0] : p.alpha;
         constexpr int UNITS = WN / 4;                 // 16-B units per parked row
         constexpr int RPU = 64 / CPR;                 // rows covered by the 64 lanes in one pass
@@ -647,7 +656,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
             // Row tile by row tile, the residual rows of tile i + 1 in flight while tile i is finished (24 registers each: all four at
             // once next to the accumulators made hipcc spill lane constants of the K loop into scratch).
             const uint32_t ext = (uint32_t)Mrows * (uint32_t)(BN * 4);
-            const __amdgpu_buffer_rsrc_t rres = make_rsrc(p.resid, ext), rc = make_rsrc(p.C, ext), rc2 = make_rsrc(p.C2, ext / 2);
+            const __amdgpu_buffer_rsrc_t rres = make_rsrc(p.resid + (size_t)seg_shift * BN, ext), rc = make_rsrc(p.C, ext), rc2 = make_rsrc(p.C2, ext / 2);
             const __amdgpu_buffer_rsrc_t rmu = make_rsrc(p.ln_mean, (uint32_t)Mrows * 4u), rrs = make_rsrc(p.ln_rstd, (uint32_t)Mrows * 4u);
             const AS3 float* lpar = (const AS3 float*)((AS3 char*)smem + 2 * TILE);
             AS3 float* lstat = (AS3 float*)((AS3 char*)smem + 2 * TILE + STAT_OFF);
@@ -728,7 +737,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const GemmGroup g, const 
             // ---- LayerNorm backward on complete rows: acc = g = d/d(LayerNorm output).  Row tile by row tile; the LayerNorm input rows and
             // the incoming residual gradient of tile i + 1 are in flight while tile i is reduced, exchanged and written.
             const uint32_t ext = (uint32_t)Mrows * (uint32_t)(BN * 4);
-            const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.ln_x, ext), rd = make_rsrc(p.C, ext), rc2 = make_rsrc(p.C2, ext / 2);
+            const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.ln_x, ext), rd = make_rsrc(reinterpret_cast<float*>(p.C) + (size_t)seg_shift * BN, ext), rc2 = make_rsrc(p.C2, ext / 2);
             const __amdgpu_buffer_rsrc_t rmu = make_rsrc(p.ln_mean, (uint32_t)Mrows * 4u), rrs = make_rsrc(p.ln_rstd, (uint32_t)Mrows * 4u);
             const AS3 float* lpar = (const AS3 float*)((AS3 char*)smem + 2 * TILE);
             AS3 float* lstat = (AS3 float*)((AS3 char*)smem + 2 * TILE + STAT_OFF);

@@ -31,7 +31,8 @@ size_t ln_bwd_workspace_floats(int M, int D);
 size_t ln_bwd_workspace_floats_upto(int Mmax, int D);
 int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean, const float* rstd, const float* gamma,
                   float* dres, int accumulate, bf16_t* dres_bf, float* dgamma, float* dbeta, float* part, int M, int D, hipStream_t s,
-                  const Gate* gate = nullptr);     // gate: dres_bf = bf16(gate .* dres) (ln_bwd_gate_kernel), dres itself ungated
+                  const Gate* gate = nullptr,      // gate: dres_bf = bf16(gate .* dres) (ln_bwd_gate_kernel), dres itself ungated
+                  bool compact_x = false);         // x and dres_bf are stored by logical row ([M][D]), only dres goes through rm
 // dgamma[c] += sum_b part[b][0][c], dbeta[c] += sum_b part[b][1][c] over nblk partial rows of [2][D] floats (what ln_bwd and the fused
 // LayerNorm-backward epilogue of gemm8.hip leave behind)
 int launch_ln_param_reduce(const float* part, int nblk, int D, float* dgamma, float* dbeta, hipStream_t s);

@@ -88,7 +88,7 @@ __device__ __forceinline__ void ln_bwd_body(const bf16_t* __restrict__ dy, const
                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                             const float* __restrict__ gamma, float* __restrict__ dres,
                                             int accumulate, bf16_t* __restrict__ dres_bf, float* __restrict__ part,
-                                            int M, int D, const Gate& gate) {
+                                            int M, int D, const Gate& gate, int compact) {
     // per-wave (per half-wave for LPR = 32) column partials, [4 RPW][dgamma | dbeta][D]: sized by D at launch (a static 32 KiB array
     // capped the kernel at 5 workgroups per CU; at D = 384 this is 24 KiB and the register budget decides: 6-7)
     extern __shared__ __attribute__((aligned(16))) float red[];
@@ -116,8 +116,9 @@ __device__ __forceinline__ void ln_bwd_body(const bf16_t* __restrict__ dy, const
         const int m = mw + rsel;
         const bool live = m < M;
         const int mc = live ? m : M - 1;
-        const size_t xrow = (size_t)map_row(mc, rm) * D;
-        const f32x4* xr = reinterpret_cast<const f32x4*>(x + xrow);
+        const size_t xrow = (size_t)map_row(mc, rm) * D;       // the row of dres; with `compact`, x and the bf16 copy are stored by logical row
+        const size_t crow = compact ? (size_t)mc * D : xrow;
+        const f32x4* xr = reinterpret_cast<const f32x4*>(x + crow);
         const uint2* dyr = reinterpret_cast<const uint2*>(dy + (size_t)mc * D);
         const float mu = mean[mc], rs = rstd[mc];
         f32x4 xh[NC], g[NC];
@@ -142,7 +143,7 @@ __device__ __forceinline__ void ln_bwd_body(const bf16_t* __restrict__ dy, const
         s2 = row_sum<LPR>(s2) * invD;
         if (!live) continue;
         f32x4* dr = reinterpret_cast<f32x4*>(dres + xrow);
-        uint2* db16 = dres_bf ? reinterpret_cast<uint2*>(dres_bf + xrow) : nullptr;
+        uint2* db16 = dres_bf ? reinterpret_cast<uint2*>(dres_bf + crow) : nullptr;
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
             const int c = sub + LPR * i;
@@ -188,8 +189,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, float* __restrict__ dres,
                                                      int accumulate, bf16_t* __restrict__ dres_bf, float* __restrict__ part,
-                                                     int M, int D) {
-    ln_bwd_body<RPB, LPR, NC, false>(dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, Gate{});
+                                                     int M, int D, int compact) {
+    ln_bwd_body<RPB, LPR, NC, false>(dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, Gate{}, compact);
 }
 template <int RPB, int LPR, int NC>
 __global__ __launch_bounds__(256) void ln_bwd_gate_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x, RowMap rm,
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(256) void ln_bwd_gate_kernel(const bf16_t* __restri
                                                           const float* __restrict__ gamma, float* __restrict__ dres,
                                                           int accumulate, bf16_t* __restrict__ dres_bf, float* __restrict__ part,
                                                           int M, int D, const Gate gate) {
-    ln_bwd_body<RPB, LPR, NC, true>(dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, gate);
+    ln_bwd_body<RPB, LPR, NC, true>(dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, gate, 0);
 }
 
 // dgamma[c] += sum_b part[b][0][c], dbeta[c] += sum_b part[b][1][c]; grid (ceil(2D/256), ceil(nblk/16))
@@ -1379,8 +1380,10 @@ size_t ln_bwd_workspace_floats_upto(int Mmax, int D) {
 
 int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean, const float* rstd, const float* gamma,
                   float* dres, int accumulate, bf16_t* dres_bf, float* dgamma, float* dbeta, float* part, int M, int D, hipStream_t s,
-                  const Gate* gate) {
+                  const Gate* gate, bool compact_x) {
     BVC_REQUIRE(D % 4 == 0 && D <= kWideChunks * 256, "ln_bwd: D=%d unsupported", D);
+    BVC_REQUIRE(!(gate && compact_x), "ln_bwd: the gated form has no compact operands");
+    const int compact = compact_x ? 1 : 0;
     BVC_REQUIRE(part != nullptr, "ln_bwd: workspace missing");
     // rows per workgroup: enough workgroups to keep >= 16 waves per CU streaming (the kernel is HBM-bound and
     // each wave walks its rows serially), few enough that the per-column atomics stay negligible
@@ -1389,7 +1392,7 @@ int launch_ln_bwd(const bf16_t* dy, const float* x, RowMap rm, const float* mean
     const int nblk = balanced_grid((M + rpg - 1) / rpg, kLnBwdMaxBlocks);
     const bool half = ln_half_wave_rows(D);
     const size_t lds = (size_t)(half ? 16 : 8) * D * sizeof(float);
-#define BVC_LN_BWD(RPB_, LPR_, NC_) hipLaunchKernelGGL((ln_bwd_kernel<RPB_, LPR_, NC_>), dim3(nblk), dim3(256), lds, s, dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D)
+#define BVC_LN_BWD(RPB_, LPR_, NC_) hipLaunchKernelGGL((ln_bwd_kernel<RPB_, LPR_, NC_>), dim3(nblk), dim3(256), lds, s, dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, compact)
 #define BVC_LN_BWD_G(RPB_, LPR_, NC_) hipLaunchKernelGGL((ln_bwd_gate_kernel<RPB_, LPR_, NC_>), dim3(nblk), dim3(256), lds, s, dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, *gate)
     if (gate) {      // the same grid and instantiation choice, the bf16 copy gated
         BVC_REQUIRE(dres_bf && gate->rows >= 1 && (double)M * D < 4398046511104.0, "ln_bwd: a gate needs the bf16 copy and rows per sample >= 1");

@@ -109,6 +109,15 @@ inline int attn_width(int hd) {
     return hd <= 32 ? 32 : hd <= 64 ? 64 : hd <= 96 ? 96 : 128;
 }
 
+// Tail mode of a LAST layer whose consumer reads only the trailing `ndec` rows of every clip's N = nvis + ndec rows (the VideoMAE decoder:
+// head, loss and final LayerNorm see the decoded tokens only).  The leading nvis rows are needed as keys and values, so the first
+// LayerNorm and the qkv product cover them; behind that nothing reads what the layer would compute for them, and in the backward their
+// incoming gradient is exactly zero.  With a LayerTail, layer_forward / layer_backward run the attention queries, proj, LayerNorm 2,
+// fc1, fc2 and their input- and weight-gradient products on the B * ndec decoded rows, stored compact.
+struct LayerTail { int nvis, ndec; };
+// may this stack's last layer run in tail mode for B clips of nvis + ndec rows (options, shapes, gate)?
+bool layer_tail_ok(const Work& w, const Stack& s, int B, int nvis, int ndec);
+
 LayerOff add_layer_params(ParamTable& t, const std::string& prefix, int64_t d, int64_t inter, bool hf_names);
 int alloc_stack(Arena& a, Stack& s, int D, int I, int H, int nlayers, float eps, size_t M, size_t BHN);
 // MD = max tokens x width, MI = max tokens x intermediate, over every stack that will use this scratch
@@ -122,8 +131,10 @@ int join_side(Work& w, int parity, hipStream_t st, bvc_bucket_fn on_bucket, void
 void begin_backward(Work& w);
 // next: the parameters of layer li + 1 when its activations are s.act[li + 1] (its first LayerNorm may then be produced by this
 // layer's fc2 epilogue), nullptr for the last layer or when the caller reuses one set of activations
+// tail: see LayerTail (the caller asks layer_tail_ok first and passes the same descriptor to the layer's backward); x_out then holds
+// the B * ndec decoded rows only
 int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* x_out, int B, int N, hipStream_t st,
-                  const LayerOff* next = nullptr);
+                  const LayerOff* next = nullptr, const LayerTail* tail = nullptr);
 // Do the LayerNorms of this stack run inside the epilogues of the 384-wide products next to them (gemm8.hip, EPI_RESID_LN / EPI_DLN)?
 bool fuse_row_ln(const Stack& s, int M);
 // bvc_*_set_drop: validates the public description and copies path_scale ([nlayers][2][samples], device) into the context's buffer
@@ -138,6 +149,6 @@ inline const Gate* top_gate(const DropState& d, Gate& store) {
     return &store;
 }
 int layer_backward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* dres, float* G, int B, int N,
-                   hipStream_t st, bvc_bucket_fn on_bucket, void* user);
+                   hipStream_t st, bvc_bucket_fn on_bucket, void* user, const LayerTail* tail = nullptr);
 
 }  // namespace bvc

@@ -250,6 +250,17 @@ bool fuse_row_ln(const Stack& s, int M) {
     return M >= 128 * 128;     // (16 clips of 1568 tokens = 196 units: -0.5 %; 32: -1.3 %; 64: -1.3 %; 128: -2.0 %; 256: -2.2 % of the step)
 }
 
+// Tail mode (stack.h LayerTail): on by default, bvc_set_option("dec_tail", 0) switches it off.  It needs the row-LayerNorm epilogues (their
+// segment map carries the one full-layout side array of proj and of dX fc1), decoded rows in whole 128-row units per clip (a unit then
+// never straddles a clip), no gate on the branches, and heads the attention kernels have a query window for, in place (no padded copies).
+bool layer_tail_ok(const Work& w, const Stack& s, int B, int nvis, int ndec) {
+    if (!options().dec_tail || nvis < 1 || ndec < 128 || ndec % 128 != 0) return false;
+    if (w.drop != nullptr && w.drop->active) return false;
+    if (s.hdp != s.hd || !attn_window_ok(s.hd)) return false;
+    if (nvis + ndec <= 160) return false;      // the whole-head attention backward's range: the window form (two kernels) was not measured against it
+    return fuse_row_ln(s, B * (nvis + ndec)) && gemm_row_ln_ok(B * ndec, s.D, s.D);
+}
+
 int alloc_drop(Arena& a, DropState& d, int nlayers, int max_samples) {
     d.nlayers = nlayers;
     d.max_samples = max_samples;
@@ -287,9 +298,13 @@ int take_drop(DropState& d, int samples, int rows, const char* who) {
 }
 
 int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* x_out, int B, int N, hipStream_t st,
-                  const LayerOff* next) {
+                  const LayerOff* next, const LayerTail* tail) {
     LayerAct& a = s.act[li];
     const int D = s.D, I = s.I, M = B * N;
+    // tail mode: everything behind the qkv product runs on the Mq = B * ndec decoded rows, stored compact (ctx, lse, h, ln2o, mean2, rstd2,
+    // pre, act and x_out hold Mq rows); only the residual input of proj is read in the full layout, through the epilogue's segment map
+    const int Mq = tail ? B * tail->ndec : M;
+    if (tail) BVC_REQUIRE(next == nullptr && tail->nvis + tail->ndec == N && layer_tail_ok(w, s, B, tail->nvis, tail->ndec), "layer_forward: tail mode is not available for this layer");
     const float* P = w.params;
     const bf16_t* W = w.wbf;
     const float eps = s.eps;
@@ -315,23 +330,25 @@ int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_i
         p.bias = bqkv;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
-    TRY(launch_attn_fwd(a.qkv, a.ctx, a.lse, B, N, s.H, s.hdp, st, sm_scale));
+    if (tail) TRY(launch_attn_fwd_win(a.qkv, a.ctx, a.lse, B, N, s.H, s.hdp, tail->nvis, tail->ndec, st, sm_scale));
+    else TRY(launch_attn_fwd(a.qkv, a.ctx, a.lse, B, N, s.H, s.hdp, st, sm_scale));
     {
-        GemmProblem p = gemm(a.ctx, (size_t)M * Da, Da, Wo, (size_t)D * Da, Da, M, D, Da, fuse ? EPI_RESID_LN : EPI_RESID, a.h, D);
+        GemmProblem p = gemm(a.ctx, (size_t)Mq * Da, Da, Wo, (size_t)D * Da, Da, Mq, D, Da, fuse ? EPI_RESID_LN : EPI_RESID, a.h, D);
         p.bias = P + o.bo; p.resid = x_in;
         if (fuse) { p.C2 = a.ln2o; p.ln_gamma = P + o.ln2w; p.ln_beta = P + o.ln2b; p.ln_mean = a.mean2; p.ln_rstd = a.rstd2; p.ln_eps = eps; }
+        if (tail) { p.seg_rows = tail->ndec; p.seg_stride = N; p.seg_off = tail->nvis; }
         if (gated) TRY(launch_gemm_gate(p, w.drop->gate(gl, 0), -1, st));
         else TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
     if (!fuse) TRY(launch_ln_fwd(a.h, identity_rows(), P + o.ln2w, P + o.ln2b, a.ln2o, a.mean2, a.rstd2, M, D, eps, st));
     {
-        GemmProblem p = gemm(a.ln2o, (size_t)M * D, D, W + o.w1, (size_t)I * D, D, M, I, D, EPI_GELU, a.pre, I);
+        GemmProblem p = gemm(a.ln2o, (size_t)Mq * D, D, W + o.w1, (size_t)I * D, D, Mq, I, D, EPI_GELU, a.pre, I);
         p.bias = P + o.b1; p.C2 = a.act;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
     {
         const bool fuse_next = fuse && next != nullptr && li + 1 < (int)s.act.size();
-        GemmProblem p = gemm(a.act, (size_t)M * I, I, W + o.w2, (size_t)D * I, I, M, D, I, fuse_next ? EPI_RESID_LN : EPI_RESID, x_out, D);
+        GemmProblem p = gemm(a.act, (size_t)Mq * I, I, W + o.w2, (size_t)D * I, I, Mq, D, I, fuse_next ? EPI_RESID_LN : EPI_RESID, x_out, D);
         p.bias = P + o.b2; p.resid = a.h;
         if (fuse_next) {      // the next layer's first LayerNorm, out of this epilogue's complete rows
             LayerAct& an = s.act[li + 1];
@@ -356,10 +373,14 @@ int join_side(Work& c_, int parity, hipStream_t st, bvc_bucket_fn on_bucket, voi
 // dres (f32 [M][D]) holds d/d(layer output) on entry and d/d(layer input) on exit; dyb[seq % 3] is its bf16 copy.
 // The four weight gradients (+ bias gradients) of the layer are one grouped launch on the side stream, overlapping the
 // next layer's dX chain; its gradient range [o.ln1w, o.end) is reported when that launch has been fenced (two steps later).
+// Tail mode (the layer's forward ran with the same LayerTail): dyb, dh, dhb and dctx hold the Mq decoded rows, compact; dres keeps the full
+// layout - the dX fc1 epilogue adds into its decoded rows through the segment map, the visible rows (zero on entry: the head sends them no
+// gradient) reach the dX qkv product untouched.
 int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x_in, float* dres, float* G, int B, int N,
-                   hipStream_t st, bvc_bucket_fn on_bucket, void* user) {
+                   hipStream_t st, bvc_bucket_fn on_bucket, void* user, const LayerTail* tail) {
     LayerAct& a = s.act[li];
     const int D = s.D, I = s.I, M = B * N;
+    const int Mq = tail ? B * tail->ndec : M;
     const float* P = c_.params;
     const bf16_t* W = c_.wbf;
     const int q = c_.seq, par = q & 1;
@@ -370,7 +391,7 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
     TRY(join_side(c_, par, st, on_bucket, user));
     // MLP
     {
-        GemmProblem p = gemm(dyb, (size_t)M * D, D, W + o.w2, (size_t)D * I, I, M, I, D, EPI_DGELU, dh, I);
+        GemmProblem p = gemm(dyb, (size_t)Mq * D, D, W + o.w2, (size_t)D * I, I, Mq, I, D, EPI_DGELU, dh, I);
         p.aux = a.pre; p.ldaux = I;
         TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
     }
@@ -381,10 +402,12 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
     Gate g_attn, g_below;
     if (gated) { g_attn = c_.drop->gate(li, 0); if (li > 0) g_below = c_.drop->gate(li - 1, 1); }
     const bool fuse = !gated && fuse_row_ln(s, M);
+    if (tail) BVC_REQUIRE(fuse && tail->nvis + tail->ndec == N, "layer_backward: tail mode needs the row-LayerNorm epilogues");
     if (fuse) {      // dX of fc1 with the second LayerNorm's backward in its epilogue: dres += ..., dhb = bf16(dres), dgamma / dbeta
-        GemmProblem p = gemm(dh, (size_t)M * I, I, W + o.w1, (size_t)I * D, D, M, D, I, EPI_DLN, dres, D);
+        GemmProblem p = gemm(dh, (size_t)Mq * I, I, W + o.w1, (size_t)I * D, D, Mq, D, I, EPI_DLN, dres, D);
         p.C2 = dhb; p.ln_x = a.h; p.ln_mean = a.mean2; p.ln_rstd = a.rstd2; p.ln_gamma = P + o.ln2w;
         p.ln_part = c_.ln_part; p.ln_dgamma = G + o.ln2w; p.ln_dbeta = G + o.ln2b;
+        if (tail) { p.seg_rows = tail->ndec; p.seg_stride = N; p.seg_off = tail->nvis; }
         TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
     } else {
         GemmProblem p = gemm(dh, (size_t)M * I, I, W + o.w1, (size_t)I * D, D, M, D, I, EPI_BF16, c_.dln, D);
@@ -402,10 +425,11 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
         Wqkv = s.wqkv_pad; Wo = s.wo_pad;
     }
     {
-        GemmProblem p = gemm(dhb, (size_t)M * D, D, Wo, (size_t)D * Da, Da, M, Da, D, EPI_BF16, c_.dctx, Da);
+        GemmProblem p = gemm(dhb, (size_t)Mq * D, D, Wo, (size_t)D * Da, Da, Mq, Da, D, EPI_BF16, c_.dctx, Da);
         TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
     }
-    TRY(launch_attn_bwd(a.qkv, a.ctx, c_.dctx, a.lse, c_.delta, dqkv, B, N, s.H, s.hdp, st, sm_scale));
+    if (tail) TRY(launch_attn_bwd_win(a.qkv, a.ctx, c_.dctx, a.lse, c_.delta, dqkv, B, N, s.H, s.hdp, tail->nvis, tail->ndec, st, sm_scale));
+    else TRY(launch_attn_bwd(a.qkv, a.ctx, c_.dctx, a.lse, c_.delta, dqkv, B, N, s.H, s.hdp, st, sm_scale));
     if (fuse) {      // dX of qkv with the first LayerNorm's backward in its epilogue: dres becomes d/d(layer input), dyb_next its bf16 copy
         GemmProblem p = gemm(dqkv, (size_t)M * 3 * Da, 3 * Da, Wqkv, (size_t)3 * Da * D, D, M, D, 3 * Da, EPI_DLN, dres, D);
         p.C2 = dyb_next; p.ln_x = x_in; p.ln_mean = a.mean1; p.ln_rstd = a.rstd1; p.ln_gamma = P + o.ln1w;
@@ -424,9 +448,10 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
     }
     {
         GemmProblem g[4];
-        g[0] = gemm(dyb, (size_t)M * D, D, a.act, (size_t)M * I, I, D, I, M, EPI_F32, G + o.w2, I);
-        g[1] = gemm(dh, (size_t)M * I, I, a.ln2o, (size_t)M * D, D, I, D, M, EPI_F32, G + o.w1, D);
-        g[2] = gemm(dhb, (size_t)M * D, D, a.ctx, (size_t)M * Da, Da, D, Da, M, EPI_F32, pad ? s.gwo_pad : G + o.wo, Da);
+        // (tail mode: the fc2 / fc1 / proj members contract over the Mq compact rows, the qkv member over all M)
+        g[0] = gemm(dyb, (size_t)Mq * D, D, a.act, (size_t)Mq * I, I, D, I, Mq, EPI_F32, G + o.w2, I);
+        g[1] = gemm(dh, (size_t)Mq * I, I, a.ln2o, (size_t)Mq * D, D, I, D, Mq, EPI_F32, G + o.w1, D);
+        g[2] = gemm(dhb, (size_t)Mq * D, D, a.ctx, (size_t)Mq * Da, Da, D, Da, Mq, EPI_F32, pad ? s.gwo_pad : G + o.wo, Da);
         g[3] = gemm(dqkv, (size_t)M * 3 * Da, 3 * Da, a.ln1o, (size_t)M * D, D, 3 * Da, D, M, EPI_F32, pad ? s.gwqkv_pad : G + o.wqkv, D);
         g[0].rowsum = G + o.b2;     // bias gradients ride along as one extra MFMA column each
         g[1].rowsum = G + o.b1;

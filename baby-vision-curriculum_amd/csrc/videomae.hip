@@ -118,6 +118,9 @@ struct bvc_ctx {
     int npartial = 0;
     float *dres_enc, *dres_dec;
     bf16_t* de2d;
+    // the last forward ran the last decoder layer in tail mode (stack.h LayerTail): dec.x_out and that layer's activations behind qkv
+    // hold the B * ndec decoded rows, compact; its backward and the "dec<last>" tap follow suit
+    bool tail_on = false;
 };
 
 namespace {
@@ -165,6 +168,7 @@ int bvc_set_option(const char* name, int value) {
     else if (!strcmp(name, "row_ln")) { BVC_REQUIRE(value >= -1 && value <= 1, "set_option: row_ln takes -1 / 0 / 1"); options().row_ln = value; }
     else if (!strcmp(name, "deterministic")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: deterministic takes 0 / 1"); options().deterministic = value; }
     else if (!strcmp(name, "head_pad")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: head_pad takes 0 / 1"); options().head_pad = value; }
+    else if (!strcmp(name, "dec_tail")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: dec_tail takes 0 / 1"); options().dec_tail = value; }
     else BVC_REQUIRE(false, "set_option: unknown option '%s'", name);
     return BVC_OK;
 }
@@ -175,6 +179,7 @@ int bvc_get_option(const char* name) {
     if (name && !strcmp(name, "row_stagger")) return options().row_stagger;
     if (name && !strcmp(name, "deterministic")) return options().deterministic;
     if (name && !strcmp(name, "head_pad")) return options().head_pad;
+    if (name && !strcmp(name, "dec_tail")) return options().dec_tail;
     bvc::set_error("get_option: unknown option '%s'", name ? name : "(null)");
     return BVC_ERR_INVALID;
 }
@@ -355,12 +360,16 @@ int bvc_videomae_forward_dual(bvc_ctx* c, const void* pixels_any, const bvc_pixe
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
     TRY(launch_fill_masked(c->dec.act[0].x_in, params + L.mask_token, c->pos_dec, c->dec_idx, B, Ld, nvis, ndec, Dd, st));
+    // the head reads the decoded rows only: the last layer computes nothing else behind its qkv product when the shapes allow (tail mode)
+    const LayerTail lt{nvis, ndec};
+    c->tail_on = layer_tail_ok(c->w, c->dec, B, nvis, ndec);
     for (int i = 0; i < c->dec.nlayers; ++i) {
-        float* xo = i + 1 < c->dec.nlayers ? c->dec.act[i + 1].x_in : c->dec.x_out;
-        TRY(layer_forward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, xo, B, Ld, st, i + 1 < c->dec.nlayers ? &L.dec[i + 1] : nullptr));
+        const bool last = i + 1 == c->dec.nlayers;
+        float* xo = !last ? c->dec.act[i + 1].x_in : c->dec.x_out;
+        TRY(layer_forward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, xo, B, Ld, st, !last ? &L.dec[i + 1] : nullptr, last && c->tail_on ? &lt : nullptr));
     }
-    // last ndec tokens -> LayerNorm -> head, fused with the pixel-target MSE (HF:497-501,588-664)
-    const RowMap tail{ndec, Ld, nvis};
+    // last ndec tokens -> LayerNorm -> head, fused with the pixel-target MSE (HF:497-501,588-664); in tail mode x_out holds just those rows
+    const RowMap tail = c->tail_on ? identity_rows() : RowMap{ndec, Ld, nvis};
     TRY(launch_ln_fwd(c->dec.x_out, tail, params + L.norm_w, params + L.norm_b, c->lnf, c->meanf, c->rstdf, Mm, Dd, cf.decoder_norm_eps, st));
     TRY(launch_labels(pixels, c->dec_idx, c->labels, B, ndec, pg, cf.norm_pix_loss, st));
     {
@@ -405,14 +414,24 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
         TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
     }
     // visible rows of the decoder stream receive no gradient from the head
-    BVC_CHECK_HIP(hipMemsetAsync(c->dres_dec, 0, (size_t)Md * Dd * 4, st));
-    BVC_CHECK_HIP(hipMemsetAsync(c->w.dyb[0], 0, (size_t)Md * Dd * 2, st));
     const RowMap tail{ndec, Ld, nvis};
-    TRY(launch_ln_bwd(c->w.dln, c->dec.x_out, tail, c->meanf, c->rstdf, params + L.norm_w, c->dres_dec, 0, c->w.dyb[0],
-                      G + L.norm_w, G + L.norm_b, c->w.ln_part, Mm, Dd, st));
+    const LayerTail lt{nvis, ndec};
+    if (c->tail_on) {
+        // tail mode: the LayerNorm backward writes every decoded row of dres_dec, so only the visible rows are zeroed (one strided fill);
+        // x_out and the bf16 copy hold the decoded rows compact - nothing of dyb[0] is left unwritten, its fill is gone
+        BVC_CHECK_HIP(hipMemset2DAsync(c->dres_dec, (size_t)Ld * Dd * 4, 0, (size_t)nvis * Dd * 4, (size_t)B, st));
+        TRY(launch_ln_bwd(c->w.dln, c->dec.x_out, tail, c->meanf, c->rstdf, params + L.norm_w, c->dres_dec, 0, c->w.dyb[0],
+                          G + L.norm_w, G + L.norm_b, c->w.ln_part, Mm, Dd, st, nullptr, true));
+    } else {
+        BVC_CHECK_HIP(hipMemsetAsync(c->dres_dec, 0, (size_t)Md * Dd * 4, st));
+        BVC_CHECK_HIP(hipMemsetAsync(c->w.dyb[0], 0, (size_t)Md * Dd * 2, st));
+        TRY(launch_ln_bwd(c->w.dln, c->dec.x_out, tail, c->meanf, c->rstdf, params + L.norm_w, c->dres_dec, 0, c->w.dyb[0],
+                          G + L.norm_w, G + L.norm_b, c->w.ln_part, Mm, Dd, st));
+    }
     bucket(L.norm_w, L.total);
     for (int i = c->dec.nlayers - 1; i >= 0; --i) {
-        TRY(layer_backward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, c->dres_dec, G, B, Ld, st, on_bucket, user));
+        TRY(layer_backward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, c->dres_dec, G, B, Ld, st, on_bucket, user,
+                           i + 1 == c->dec.nlayers && c->tail_on ? &lt : nullptr));
     }
     // decoder input: mask token, encoder_to_decoder
     TRY(launch_colsum_f32(c->dres_dec, tail, Mm, Dd, G + L.mask_token, st));
@@ -446,6 +465,47 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
     return BVC_OK;
 }
 
+// "dec<last>" after a forward in tail mode: the layer's output exists for the decoded rows only (dec.x_out, compact).  The visible rows
+// are completed here, off the training path: attention with the query window (0, nvis), then proj + residual, LayerNorm 2, fc1 + GELU
+// and fc2 + residual on the B * nvis gathered rows with the ordinary kernels.  Scratch: the layer's own activation buffers, allocated
+// for B * Ld rows, hold B * ndec in tail mode - the completion lives in the B * nvis rows behind them, so neither a later backward
+// nor a second tap finds anything changed.  It uses the parameters of the forward (the caller's `params` and the bf16 copy): ask for the
+// tap before an optimiser step rewrites them.
+static int tail_tap(bvc_ctx* c, float* dst, hipStream_t st) {
+    const Layout& L = c->lay;
+    Stack& s = c->dec;
+    LayerAct& a = s.act.back();
+    const LayerOff& o = L.dec.back();
+    const int B = c->batch, nvis = c->nvis, ndec = c->ndec, Ld = c->Ld, D = s.D, I = s.I, Da = s.Da;
+    const size_t Mq = (size_t)B * ndec, Mv = (size_t)B * nvis;
+    const float* P = c->params;
+    const bf16_t* W = c->wbf;
+    bf16_t *ctx_v = a.ctx + Mq * Da, *ln2o_v = a.ln2o + Mq * D, *pre_v = a.pre + Mq * I, *act_v = a.act + Mq * I;
+    float *lse_v = a.lse + (size_t)B * s.H * ndec, *h_v = a.h + Mq * D, *mean_v = a.mean2 + Mq, *rstd_v = a.rstd2 + Mq, *out_v = s.x_out + Mq * D;
+    const size_t full = (size_t)Ld * D * 4, vis = (size_t)nvis * D * 4, dec = (size_t)ndec * D * 4;
+    TRY(launch_attn_fwd_win(a.qkv, ctx_v, lse_v, B, Ld, s.H, s.hdp, 0, nvis, st));
+    BVC_CHECK_HIP(hipMemcpy2DAsync(h_v, vis, a.x_in, full, vis, (size_t)B, hipMemcpyDeviceToDevice, st));     // the residual input of the visible rows
+    {
+        GemmProblem p = gemm(ctx_v, Mv * Da, Da, W + o.wo, (size_t)D * Da, Da, (int)Mv, D, Da, EPI_RESID, h_v, D);
+        p.bias = P + o.bo; p.resid = h_v;
+        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
+    }
+    TRY(launch_ln_fwd(h_v, identity_rows(), P + o.ln2w, P + o.ln2b, ln2o_v, mean_v, rstd_v, (int)Mv, D, s.eps, st));
+    {
+        GemmProblem p = gemm(ln2o_v, Mv * D, D, W + o.w1, (size_t)I * D, D, (int)Mv, I, D, EPI_GELU, pre_v, I);
+        p.bias = P + o.b1; p.C2 = act_v;
+        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
+    }
+    {
+        GemmProblem p = gemm(act_v, Mv * I, I, W + o.w2, (size_t)D * I, I, (int)Mv, D, I, EPI_RESID, out_v, D);
+        p.bias = P + o.b2; p.resid = h_v;
+        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
+    }
+    BVC_CHECK_HIP(hipMemcpy2DAsync(dst, full, out_v, vis, vis, (size_t)B, hipMemcpyDeviceToDevice, st));
+    BVC_CHECK_HIP(hipMemcpy2DAsync(dst + (size_t)nvis * D, full, s.x_out, dec, dec, (size_t)B, hipMemcpyDeviceToDevice, st));
+    return BVC_OK;
+}
+
 int bvc_videomae_tap(bvc_ctx* c, const char* name, float* dst, int64_t capacity, int64_t* numel, void* stream) {
     BVC_REQUIRE(c && name && dst && numel, "tap: null argument");
     BVC_REQUIRE(c->batch > 0, "tap: no forward has run");
@@ -466,6 +526,7 @@ int bvc_videomae_tap(bvc_ctx* c, const char* name, float* dst, int64_t capacity,
     BVC_REQUIRE(src, "tap: unknown activation '%s'", name);
     *numel = (int64_t)n;
     BVC_REQUIRE((int64_t)n <= capacity, "tap: destination holds %lld elements, '%s' has %lld", (long long)capacity, name, (long long)n);
+    if (src == c->dec.x_out && c->tail_on) return tail_tap(c, dst, (hipStream_t)stream);
     BVC_CHECK_HIP(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return BVC_OK;
 }

@@ -60,6 +60,13 @@ const char* bvc_version(void);
  *                 Read at every launch, so it may change between calls (not while a call is being enqueued elsewhere).
  *   "head_pad"    0 (default) / 1: 1 = heads of 80 / 88 dims run zero-padded to 96 (padded weight copies, pad / unpad launches), the
  *                 layout of earlier builds; 0 = in place.  Read when a model context allocates its stacks (same-process A/Bs only).
+ *   "dec_tail"    1 (default) / 0: tail mode of the VideoMAE pre-training step.  The head, the loss and the final LayerNorm read only the
+ *                 decoded rows of the decoder's [visible | decoded] rows per clip, so the LAST decoder layer runs everything behind its
+ *                 qkv product (attention queries, proj, LayerNorm 2, the MLP, their input- and weight-gradient products) on those
+ *                 rows alone.  Taken when the decoded rows per clip are a multiple of 128, the layer's LayerNorms run in the 384-wide
+ *                 epilogues ("row_ln"), the heads are 64 wide, a clip has more than 160 rows (below, the whole-head attention backward
+ *                 serves) and no gate is set; otherwise, and with 0, the layer runs on all rows with the launches and the results of
+ *                 earlier builds.  Read by every forward (its backward follows the forward).
  * bvc_get_option returns the value, or BVC_ERR_INVALID for an unknown name; bvc_set_option rejects values outside the list. */
 int bvc_set_option(const char* name, int value);
 int bvc_get_option(const char* name);
@@ -158,7 +165,10 @@ int bvc_videomae_backward(bvc_ctx* ctx, const float* grad_loss_dev, float* grads
 int bvc_videomae_shadow(bvc_ctx* ctx, int valid, void** shadow_bf16, int64_t* numel);
 
 /* Copies a saved activation of the last forward as f32 into dst_dev (parity probes: "embed",
- * "enc<i>", "x_full", "dec<i>", "labels").  Returns the element count via *numel. */
+ * "enc<i>", "x_full", "dec<i>", "labels").  Returns the element count via *numel.
+ * "dec<last>" always has nvis + ndec rows per clip.  After a forward in tail mode ("dec_tail") the visible rows of that output were
+ * never computed: the call completes them on the spot with the ordinary kernels (a few launches on B * nvis rows, in spare memory of
+ * the context, with the parameters the forward was given) - ask before an optimiser step rewrites those. */
 int bvc_videomae_tap(bvc_ctx* ctx, const char* name, float* dst_dev, int64_t capacity, int64_t* numel, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -361,8 +371,8 @@ typedef struct bvc_gemm_desc {
     float alpha;
     const float* alpha_dev;         /* optional device scalar multiplied into alpha */
     int epi, split_k;
-    void* C; int ldc; void* C2;
-    const float* bias; const float* resid; const void* aux; int ldaux;
+    void* C; int ldc; int seg_rows; void* C2;               /* seg_*: see below */
+    const float* bias; const float* resid; const void* aux; int ldaux; int seg_stride;
     const int* rowtok; const float* pos; const float* labels; float* partial;
     int rin, rout;
     float* rowsum;                  /* TN only: rowsum[m] += alpha * sum_k A(m,k)  (bias gradient of the same dY) */
@@ -376,9 +386,16 @@ typedef struct bvc_gemm_desc {
      *                   ln_dgamma += sum_m g xhat, ln_dbeta += sum_m g  (through ln_part: scratch of 256 x 2 x 384 floats). */
     const float* ln_gamma; const float* ln_beta;
     float* ln_mean; float* ln_rstd;
-    float ln_eps;
+    float ln_eps; int seg_off;
     const float* ln_x;
     float* ln_part; float* ln_dgamma; float* ln_dbeta;
+    /* BVC_EPI_RESID_LN / BVC_EPI_DLN only, optional (seg_rows == 0: none).  The product's M rows are the segments [seg_off, seg_off +
+     * seg_rows) of every seg_stride rows of a longer array, stored compact: row r of segment c is row c seg_stride + seg_off + r of
+     * that array.  ONE side pointer of the problem is addressed through the map - `resid` of RESID_LN (read), `C` of DLN (the f32
+     * residual gradient, read and written in place); every other pointer is compact.  seg_rows is a multiple of 128, so a 128-row
+     * tile lies in one segment and the map is one scalar per tile; bvc_op_gemm rejects a map that is not of that form (seg_rows a
+     * multiple of 128 that divides M, 0 <= seg_off, seg_off + seg_rows <= seg_stride) and any map on another epilogue.  (The three fields sit in the alignment holes behind ldc, ldaux
+     * and ln_eps: the descriptor's size and every other offset are what they were.) */
 } bvc_gemm_desc;
 /* tile_cfg: -1 auto; 0 = 128x128, 1 = 128x64, 2 = 64x64 (one workgroup per tile); 6 / 7 = persistent 128x128 / 128x64,
  * 9 = persistent 128x128 with deferred stores; 10 / 11 = 256x256 / 256x128, one 512-thread workgroup per CU (gemm8.hip);

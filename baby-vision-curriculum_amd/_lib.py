@@ -58,6 +58,7 @@ def pixel_format(pixel_values, mean, std, channels):
 
 
 OPT_MAX_GROUPS = 8     # BVC_OPT_MAX_GROUPS (include/bvc.h)
+OPT_TABLE_MAX_GROUPS = 1024     # BVC_OPT_TABLE_MAX_GROUPS: the device-table entry points (bvc_op_sgd_step_table / bvc_op_adam_step_table)
 
 
 class SgdGroupsC(ctypes.Structure):
@@ -231,6 +232,10 @@ SYMBOLS = {
                                          c_int, c_void_p, c_void_p]),
     "bvc_op_adam_step_segments": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "bvc_op_sgd_step_table": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 +
+                                      [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "bvc_op_adam_step_table": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 +
+                                       [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bvc_op_nonfinite_check": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "bvc_op_mask_index": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_dual_mask_index": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

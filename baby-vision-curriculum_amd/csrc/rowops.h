@@ -74,6 +74,15 @@ int launch_sgd_step_segments(float* p, float* g, float* buf, int64_t n, const in
 int launch_adam_step_segments(float* p, float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const int* seg_group,
                               const int* blk_seg, int nseg, const bvc_adam_groups* groups, float* state, double* hyper_dev,
                               const float* grad_scale, const float* found_inf, int write_grad, bf16_t* shadow, hipStream_t s);
+// the same with the groups' hyper-parameters in a device table (table: f32 [8 ngroups], written inside the call), any number of groups
+int launch_sgd_step_table(float* p, float* g, float* buf, int64_t n, const int64_t* seg_start, const int* seg_group, const int* blk_seg,
+                          int nseg, int ngroups, const float* lr, const float* momentum, const float* dampening, const float* wd,
+                          const int* nesterov, const int* first_step, const int* maximize, float* table, const float* grad_scale,
+                          const float* found_inf, int write_grad, bf16_t* shadow, hipStream_t s);
+int launch_adam_step_table(float* p, float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const int* seg_group,
+                           const int* blk_seg, int nseg, int ngroups, const double* lr, const double* beta1, const double* beta2,
+                           const double* eps, const double* wd, const int* decoupled, const int* maximize, float* state, float* table,
+                           const float* grad_scale, const float* found_inf, int write_grad, bf16_t* shadow, hipStream_t s);
 int launch_pad_heads(const bf16_t* wqkv, const float* bqkv, const bf16_t* wo, bf16_t* wqkv_p, float* bqkv_p, bf16_t* wo_p, int D, int H,
                      int hd, int hdp, hipStream_t s);
 int launch_unpad_head_grads(const float* gwqkv_p, const float* gbqkv_p, const float* gwo_p, float* gwqkv, float* gbqkv, float* gwo, int D,

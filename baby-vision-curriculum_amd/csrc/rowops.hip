@@ -1272,6 +1272,207 @@ __global__ __launch_bounds__(256) void adam_step_seg_kernel(float* __restrict__ 
     }
 }
 
+// ============================================================================ parameter groups beyond BVC_OPT_MAX_GROUPS: a device table
+// Layer-wise learning-rate decay gives 2 (L + 2) groups (28 / 52 / 68 at base / large / huge) - too many for a by-value struct with a
+// select chain.  The kernels below walk the SAME segment table and read the hyper-parameters of seg_group[s] from a device table
+// with one 32-byte row per group (two 16-byte loads per lane; a row is shared by every lane of a segment and stays in cache):
+//   SGD row:  { lr, wd, momentum, dampening | flags, 0, 0, 0 }               flags as in SgdGroupsDev
+//   Adam row: { omb1, beta2, omb2, eps | wd, decay_mul, flags, 0 }          flags as in AdamGroupsDev; step scalars in state[3 grp + ..]
+// The rows change per step under a schedule.  They reach the device as KERNEL ARGUMENTS of small writer kernels (a chunk of
+// BVC_OPT_TABLE_CHUNK groups by value per launch, stored with ordinary vector stores): the runtime copies kernel arguments at launch,
+// so there is no host buffer whose lifetime matters, no host synchronisation, and writer and consumer are ordered by the stream
+// however far the host runs ahead.  The arithmetic per element is that of sgd_step_seg_kernel / adam_step_seg_kernel, statement for
+// statement; a group index outside the table (a malformed segment table) is treated like -1: left untouched.
+constexpr int kOptRowFloats = 8;
+struct SgdChunkDev {
+    float lr[BVC_OPT_TABLE_CHUNK], wd[BVC_OPT_TABLE_CHUNK], momentum[BVC_OPT_TABLE_CHUNK], dampening[BVC_OPT_TABLE_CHUNK];
+    int flags[BVC_OPT_TABLE_CHUNK];
+};
+struct AdamChunkDev {
+    double lr[BVC_OPT_TABLE_CHUNK], beta1[BVC_OPT_TABLE_CHUNK], beta2[BVC_OPT_TABLE_CHUNK];     // for the step scalars, in double
+    float omb1[BVC_OPT_TABLE_CHUNK], beta2f[BVC_OPT_TABLE_CHUNK], omb2[BVC_OPT_TABLE_CHUNK], eps[BVC_OPT_TABLE_CHUNK], wd[BVC_OPT_TABLE_CHUNK],
+        decay_mul[BVC_OPT_TABLE_CHUNK];
+    int flags[BVC_OPT_TABLE_CHUNK];
+};
+static_assert(sizeof(SgdChunkDev) + 64 <= 4096 && sizeof(AdamChunkDev) + 64 <= 4096, "a chunk must fit the kernel-argument segment");
+
+// rows [g0, g0 + count) of the SGD table, one thread per group
+__global__ void sgd_table_write_kernel(float* __restrict__ table, int g0, int count, const SgdChunkDev C) {
+    const int t = threadIdx.x;
+    if (blockIdx.x != 0 || t >= count) return;
+    float* row = table + (size_t)(g0 + t) * kOptRowFloats;
+    *reinterpret_cast<f32x4*>(row) = f32x4{C.lr[t], C.wd[t], C.momentum[t], C.dampening[t]};
+    *reinterpret_cast<f32x4*>(row + 4) = f32x4{__int_as_float(C.flags[t]), 0.f, 0.f, 0.f};
+}
+
+// rows [g0, g0 + count) of the Adam table and the groups' step scalars (adam_prep_groups_kernel's formulas, in double; not advanced
+// on a step the scaler skips - the rows are written either way, adam_step_table_kernel does not read them on such a step)
+__global__ void adam_prep_table_kernel(float* __restrict__ state, float* __restrict__ table, int g0, int count, const AdamChunkDev C,
+                                       const float* __restrict__ found_inf) {
+    const int t = threadIdx.x;
+    if (blockIdx.x != 0 || t >= count) return;
+    const int grp = g0 + t;
+    float* row = table + (size_t)grp * kOptRowFloats;
+    *reinterpret_cast<f32x4*>(row) = f32x4{C.omb1[t], C.beta2f[t], C.omb2[t], C.eps[t]};
+    *reinterpret_cast<f32x4*>(row + 4) = f32x4{C.wd[t], C.decay_mul[t], __int_as_float(C.flags[t]), 0.f};
+    if (found_inf && *found_inf != 0.f) return;
+    const double lr = C.lr[t], beta1 = C.beta1[t], beta2 = C.beta2[t];
+    const double step = (double)state[3 * grp] + 1.0;
+    state[3 * grp] = (float)step;
+    state[3 * grp + 1] = (float)(lr / (1.0 - pow(beta1, step)));
+    state[3 * grp + 2] = (float)sqrt(1.0 - pow(beta2, step));
+}
+
+// Rounding.  This file is compiled with floating-point contraction on, and which multiply of a sum of two products the compiler fuses
+// (buf * momentum + g * (1 - dampening); v * beta2 + (1 - beta2) * g^2) follows the shape of the surrounding code, not the statement:
+// the by-value kernels fuse the LEFT product in their vector paths and neither in sgd_step_seg_kernel's element path, and
+// adam_step_seg_kernel's m + (1 - beta1) (g - m) is not fused at all (its sum is paired with the denominator's in one packed add).
+// Results here have to equal theirs bit for bit, so contraction is off in the two kernels below and every fused multiply-add the
+// by-value kernels perform is written out; tests/test_gpu_optim_groups.py compares the two paths bit for bit on the GPU.
+__global__ __launch_bounds__(256) void sgd_step_table_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf, int64_t n,
+                                                             const int64_t* __restrict__ seg_start, const int* __restrict__ seg_group,
+                                                             const int* __restrict__ blk_seg, const float* __restrict__ table, int ngroups,
+                                                             const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
+                                                             int write_grad, bf16_t* __restrict__ shadow) {
+#pragma clang fp contract(off)
+    if (found_inf && *found_inf != 0.f) return;
+    const float inv = grad_scale ? 1.f / *grad_scale : 1.f;
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    int s = find_segment(seg_start, blk_seg[blockIdx.x], i);
+    if (i + 4 <= n && i + 4 <= seg_start[s + 1]) {
+        const int grp = seg_group[s];
+        if (grp < 0 || grp >= ngroups) return;
+        const f32x4 r0 = *reinterpret_cast<const f32x4*>(table + (size_t)grp * kOptRowFloats);
+        const float lr = r0[0], wd = r0[1], momentum = r0[2], dampening = r0[3];
+        const int fl = __float_as_int(table[(size_t)grp * kOptRowFloats + 4]);
+        const f32x4 pv = *reinterpret_cast<f32x4*>(p + i);
+        f32x4 gv = *reinterpret_cast<f32x4*>(g + i) * inv;
+        if (fl & 2) gv = -gv;
+        const f32x4 gu = gv;
+        if (wd != 0.f) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) gv[e] = __builtin_fmaf(pv[e], wd, gv[e]);
+        }
+        f32x4 d = gv;
+        if (momentum != 0.f) {
+            f32x4 bv = gv;
+            if (!(fl & 4)) {
+                const f32x4 bo = *reinterpret_cast<f32x4*>(buf + i), gd = gv * (1.f - dampening);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bv[e] = __builtin_fmaf(bo[e], momentum, gd[e]);
+            }
+            *reinterpret_cast<f32x4*>(buf + i) = bv;
+            if (fl & 1) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) d[e] = __builtin_fmaf(bv[e], momentum, gv[e]);
+            } else {
+                d = bv;
+            }
+        }
+        f32x4 pn;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pn[e] = __builtin_fmaf(-d[e], lr, pv[e]);
+        *reinterpret_cast<f32x4*>(p + i) = pn;
+        if (shadow) *reinterpret_cast<uint2*>(shadow + i) = uint2{pack2bf(pn[0], pn[1]), pack2bf(pn[2], pn[3])};
+        if (write_grad) *reinterpret_cast<f32x4*>(g + i) = gu;
+    } else {
+        for (int64_t j = i; j < n && j < i + 4; ++j) {
+            s = find_segment(seg_start, s, j);
+            const int grp = seg_group[s];
+            if (grp < 0 || grp >= ngroups) continue;
+            const f32x4 r0 = *reinterpret_cast<const f32x4*>(table + (size_t)grp * kOptRowFloats);
+            const float lr = r0[0], wd = r0[1], momentum = r0[2], dampening = r0[3];
+            const int fl = __float_as_int(table[(size_t)grp * kOptRowFloats + 4]);
+            float gv = g[j] * inv;
+            if (fl & 2) gv = -gv;
+            const float gu = gv;
+            if (wd != 0.f) gv = __builtin_fmaf(p[j], wd, gv);
+            float d = gv;
+            if (momentum != 0.f) {
+                const float bv = (fl & 4) ? gv : buf[j] * momentum + gv * (1.f - dampening);      // both products rounded, as there
+                buf[j] = bv;
+                d = (fl & 1) ? __builtin_fmaf(bv, momentum, gv) : bv;
+            }
+            p[j] = __builtin_fmaf(-lr, d, p[j]);
+            if (shadow) shadow[j] = f2bf(p[j]);
+            if (write_grad) g[j] = gu;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void adam_step_table_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                              int64_t n, const int64_t* __restrict__ seg_start, const int* __restrict__ seg_group,
+                                                              const int* __restrict__ blk_seg, const float* __restrict__ table, int ngroups,
+                                                              const float* __restrict__ state, const float* __restrict__ grad_scale,
+                                                              const float* __restrict__ found_inf, int write_grad, bf16_t* __restrict__ shadow) {
+#pragma clang fp contract(off)
+    if (found_inf && *found_inf != 0.f) return;
+    const float inv = grad_scale ? 1.f / *grad_scale : 1.f;
+    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    int s = find_segment(seg_start, blk_seg[blockIdx.x], i0);
+    const bool vec = i0 + 4 <= n && i0 + 4 <= seg_start[s + 1];
+    const int cnt = i0 + 4 <= n ? 4 : (int)(n - i0);
+    float pv[4], gv[4], mv[4], vv[4], gu[4];
+    int grp4[4];
+    if (vec) {
+        *reinterpret_cast<f32x4*>(pv) = *reinterpret_cast<const f32x4*>(p + i0);
+        *reinterpret_cast<f32x4*>(gv) = *reinterpret_cast<const f32x4*>(g + i0);
+        *reinterpret_cast<f32x4*>(mv) = *reinterpret_cast<const f32x4*>(m + i0);
+        *reinterpret_cast<f32x4*>(vv) = *reinterpret_cast<const f32x4*>(v + i0);
+        const int grp = seg_group[s];
+        if (grp < 0 || grp >= ngroups) return;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) grp4[e] = grp;
+    } else {
+        for (int e = 0; e < 4; ++e) {
+            grp4[e] = -1;
+            pv[e] = gv[e] = mv[e] = vv[e] = 0.f;
+            if (e < cnt) {
+                s = find_segment(seg_start, s, i0 + e);
+                grp4[e] = seg_group[s] < ngroups ? seg_group[s] : -1;
+                pv[e] = p[i0 + e]; gv[e] = g[i0 + e]; mv[e] = m[i0 + e]; vv[e] = v[i0 + e];
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int grp = grp4[e] < 0 ? 0 : grp4[e];
+        const f32x4 r0 = *reinterpret_cast<const f32x4*>(table + (size_t)grp * kOptRowFloats);
+        const f32x4 r1 = *reinterpret_cast<const f32x4*>(table + (size_t)grp * kOptRowFloats + 4);
+        const float omb1 = r0[0], beta2 = r0[1], omb2 = r0[2], eps = r0[3], wd = r1[0], decay_mul = r1[1];
+        const int fl = __float_as_int(r1[2]);
+        const float step_size = state[3 * grp + 1], bc2s = state[3 * grp + 2];
+        float gr = gv[e] * inv;
+        if (fl & 2) gr = -gr;
+        gu[e] = gr;
+        float pe = pv[e];
+        if (wd != 0.f) {
+            if (fl & 1) pe *= decay_mul; else gr = __builtin_fmaf(wd, pe, gr);
+        }
+        const float me = mv[e] + omb1 * (gr - mv[e]);      // product and sum rounded separately, as there
+        const float ve = __builtin_fmaf(vv[e], beta2, omb2 * (gr * gr));
+        const float denom = sqrtf(ve) / bc2s + eps;
+        pv[e] = __builtin_fmaf(-step_size, me / denom, pe);
+        mv[e] = me; vv[e] = ve;
+    }
+    if (vec) {
+        *reinterpret_cast<f32x4*>(p + i0) = *reinterpret_cast<f32x4*>(pv);
+        *reinterpret_cast<f32x4*>(m + i0) = *reinterpret_cast<f32x4*>(mv);
+        *reinterpret_cast<f32x4*>(v + i0) = *reinterpret_cast<f32x4*>(vv);
+        if (shadow) *reinterpret_cast<uint2*>(shadow + i0) = uint2{pack2bf(pv[0], pv[1]), pack2bf(pv[2], pv[3])};
+        if (write_grad) *reinterpret_cast<f32x4*>(g + i0) = *reinterpret_cast<f32x4*>(gu);
+    } else {
+        for (int e = 0; e < cnt; ++e) {
+            if (grp4[e] < 0) continue;
+            p[i0 + e] = pv[e]; m[i0 + e] = mv[e]; v[i0 + e] = vv[e];
+            if (shadow) shadow[i0 + e] = f2bf(pv[e]);
+            if (write_grad) g[i0 + e] = gu[e];
+        }
+    }
+}
+
 // ============================================================================ zero-padded attention heads (hd -> hdp)
 // The JEPA predictor inherits the encoder's head COUNT (vision_transformer.py:447,463: num_heads=encoder.num_heads), so ViT-L
 // gives 16 heads of 24 dims - not an MFMA-friendly width.  The heads are run at 32 dims with zero padding: padded copies of
@@ -1744,6 +1945,70 @@ int launch_adam_step_segments(float* p, float* g, float* m, float* v, int64_t n,
     hipLaunchKernelGGL(adam_prep_groups_kernel, dim3(1), dim3(64), 0, s, state, gr->ngroups, hyper_dev, found_inf);
     hipLaunchKernelGGL(adam_step_seg_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, p, g, m, v, n, seg_start, seg_group, blk_seg, G, state,
                        grad_scale, found_inf, write_grad, shadow);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+static int check_table(const char* who, int64_t n, const int64_t* seg_start, const int* seg_group, const int* blk_seg, int nseg, int ngroups,
+                       const float* table) {
+    BVC_REQUIRE(seg_start && seg_group && blk_seg && nseg > 0, "%s: segment table missing", who);
+    BVC_REQUIRE(ngroups >= 1 && ngroups <= BVC_OPT_TABLE_MAX_GROUPS, "%s: %d parameter groups (1..%d)", who, ngroups, BVC_OPT_TABLE_MAX_GROUPS);
+    BVC_REQUIRE(table != nullptr && (uintptr_t)table % 16 == 0, "%s: the group table must be a 16-byte aligned device buffer", who);
+    BVC_REQUIRE(n > 0, "%s: empty range", who);
+    return BVC_OK;
+}
+
+int launch_sgd_step_table(float* p, float* g, float* buf, int64_t n, const int64_t* seg_start, const int* seg_group, const int* blk_seg,
+                          int nseg, int ngroups, const float* lr, const float* momentum, const float* dampening, const float* wd,
+                          const int* nesterov, const int* first_step, const int* maximize, float* table, const float* grad_scale,
+                          const float* found_inf, int write_grad, bf16_t* shadow, hipStream_t s) {
+    if (int rc = check_table("sgd_step_table", n, seg_start, seg_group, blk_seg, nseg, ngroups, table)) return rc;
+    BVC_REQUIRE(lr && momentum && dampening && wd && nesterov && first_step && maximize, "sgd_step_table: hyper-parameter array missing");
+    BVC_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && (buf == nullptr || (uintptr_t)buf % 16 == 0),
+                "sgd_step_table: buffers must be 16-byte aligned");
+    BVC_REQUIRE(shadow == nullptr || (uintptr_t)shadow % 8 == 0, "sgd_step_table: the bf16 shadow must be 8-byte aligned");
+    for (int i = 0; i < ngroups; ++i) BVC_REQUIRE(momentum[i] == 0.f || buf != nullptr, "sgd_step_table: momentum needs a buffer");
+    for (int g0 = 0; g0 < ngroups; g0 += BVC_OPT_TABLE_CHUNK) {
+        const int count = ngroups - g0 < BVC_OPT_TABLE_CHUNK ? ngroups - g0 : BVC_OPT_TABLE_CHUNK;
+        SgdChunkDev C;
+        for (int t = 0; t < BVC_OPT_TABLE_CHUNK; ++t) {
+            const int j = g0 + (t < count ? t : 0);
+            C.lr[t] = lr[j]; C.wd[t] = wd[j]; C.momentum[t] = momentum[j]; C.dampening[t] = dampening[j];
+            C.flags[t] = (nesterov[j] ? 1 : 0) | (maximize[j] ? 2 : 0) | (first_step[j] ? 4 : 0);
+        }
+        hipLaunchKernelGGL(sgd_table_write_kernel, dim3(1), dim3(BVC_OPT_TABLE_CHUNK), 0, s, table, g0, count, C);
+    }
+    hipLaunchKernelGGL(sgd_step_table_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, p, g, buf, n, seg_start, seg_group, blk_seg,
+                       (const float*)table, ngroups, grad_scale, found_inf, write_grad, shadow);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_adam_step_table(float* p, float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const int* seg_group,
+                           const int* blk_seg, int nseg, int ngroups, const double* lr, const double* beta1, const double* beta2,
+                           const double* eps, const double* wd, const int* decoupled, const int* maximize, float* state, float* table,
+                           const float* grad_scale, const float* found_inf, int write_grad, bf16_t* shadow, hipStream_t s) {
+    if (int rc = check_table("adam_step_table", n, seg_start, seg_group, blk_seg, nseg, ngroups, table)) return rc;
+    BVC_REQUIRE(lr && beta1 && beta2 && eps && wd && decoupled && maximize && state, "adam_step_table: hyper-parameter array / state missing");
+    BVC_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0),
+                "adam_step_table: buffers must be 16-byte aligned");
+    BVC_REQUIRE(shadow == nullptr || (uintptr_t)shadow % 8 == 0, "adam_step_table: the bf16 shadow must be 8-byte aligned");
+    for (int g0 = 0; g0 < ngroups; g0 += BVC_OPT_TABLE_CHUNK) {
+        const int count = ngroups - g0 < BVC_OPT_TABLE_CHUNK ? ngroups - g0 : BVC_OPT_TABLE_CHUNK;
+        AdamChunkDev C;
+        for (int t = 0; t < BVC_OPT_TABLE_CHUNK; ++t) {
+            const int j = g0 + (t < count ? t : 0);
+            // hyper-parameters arrive as doubles (python floats) and are combined in double before the cast, as torch does - on the
+            // host, with the very expressions of launch_adam_step_segments, so that both paths hand the kernels the same floats
+            C.omb1[t] = (float)(1.0 - beta1[j]); C.beta2f[t] = (float)beta2[j]; C.omb2[t] = (float)(1.0 - beta2[j]);
+            C.eps[t] = (float)eps[j]; C.wd[t] = (float)wd[j]; C.decay_mul[t] = (float)(1.0 - lr[j] * wd[j]);
+            C.flags[t] = (decoupled[j] ? 1 : 0) | (maximize[j] ? 2 : 0);
+            C.lr[t] = lr[j]; C.beta1[t] = beta1[j]; C.beta2[t] = beta2[j];
+        }
+        hipLaunchKernelGGL(adam_prep_table_kernel, dim3(1), dim3(BVC_OPT_TABLE_CHUNK), 0, s, state, table, g0, count, C, found_inf);
+    }
+    hipLaunchKernelGGL(adam_step_table_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, p, g, m, v, n, seg_start, seg_group, blk_seg,
+                       (const float*)table, ngroups, (const float*)state, grad_scale, found_inf, write_grad, shadow);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

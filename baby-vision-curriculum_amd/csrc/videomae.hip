@@ -1024,6 +1024,26 @@ int bvc_op_adam_step_segments(float* params, float* grads, float* exp_avg, float
     return launch_adam_step_segments(params, grads, exp_avg, exp_avg_sq, n, seg_start, seg_group, blk_seg, nseg, groups, state, hyper_scratch,
                                      grad_scale, found_inf, write_unscaled_grads, (bf16_t*)bf16_shadow, (hipStream_t)stream);
 }
+int bvc_op_sgd_step_table(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,
+                          const int32_t* blk_seg, int nseg, int ngroups, const float* lr, const float* momentum, const float* dampening,
+                          const float* weight_decay, const int32_t* nesterov, const int32_t* first_step, const int32_t* maximize,
+                          float* group_table, const float* grad_scale, const float* found_inf, int write_unscaled_grads,
+                          void* bf16_shadow, void* stream) {
+    BVC_REQUIRE(params && grads && n >= 0, "op_sgd_step_table: bad argument");
+    return launch_sgd_step_table(params, grads, momentum_buf, n, seg_start, seg_group, blk_seg, nseg, ngroups, lr, momentum, dampening,
+                                 weight_decay, nesterov, first_step, maximize, group_table, grad_scale, found_inf, write_unscaled_grads,
+                                 (bf16_t*)bf16_shadow, (hipStream_t)stream);
+}
+int bvc_op_adam_step_table(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const int64_t* seg_start,
+                           const int32_t* seg_group, const int32_t* blk_seg, int nseg, int ngroups, const double* lr, const double* beta1,
+                           const double* beta2, const double* eps, const double* weight_decay, const int32_t* decoupled,
+                           const int32_t* maximize, float* state, float* group_table, const float* grad_scale, const float* found_inf,
+                           int write_unscaled_grads, void* bf16_shadow, void* stream) {
+    BVC_REQUIRE(params && grads && exp_avg && exp_avg_sq && n >= 0, "op_adam_step_table: bad argument");
+    return launch_adam_step_table(params, grads, exp_avg, exp_avg_sq, n, seg_start, seg_group, blk_seg, nseg, ngroups, lr, beta1, beta2, eps,
+                                  weight_decay, decoupled, maximize, state, group_table, grad_scale, found_inf, write_unscaled_grads,
+                                  (bf16_t*)bf16_shadow, (hipStream_t)stream);
+}
 int bvc_videomae_shadow(bvc_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
     BVC_REQUIRE(c, "videomae_shadow: null context");
     if (shadow_bf16) *shadow_bf16 = c->wbf;

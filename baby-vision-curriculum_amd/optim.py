@@ -7,6 +7,10 @@ include/bvc.h).  The reference's JEPA optimiser (pretraining/predictive/helper.p
 with ``weight_decay`` 0) thereby costs two launches - encoder buffer, predictor buffer - like a single group does.  Parameters
 outside any flat buffer (an ordinary ``nn.Linear`` head) take one launch per run of memory-adjacent parameters of a group.
 
+More groups than the by-value struct carries (``_lib.OPT_MAX_GROUPS``) - layer-wise learning-rate decay makes ``2 * (layers + 2)`` of
+them, ``layer_decay_param_groups`` below - keep the one launch per flat module: the hyper-parameters then sit in a device table with
+one row per group (``bvc_op_sgd_step_table`` / ``bvc_op_adam_step_table``, up to ``_lib.OPT_TABLE_MAX_GROUPS`` groups), filled per
+step by one small writer launch per 64 groups.
 
 Same constructor and update rule as ``torch.optim.SGD`` (the reference builds
 ``torch.optim.SGD(xmodel.parameters(), lr, weight_decay, momentum, nesterov=True)`` at
@@ -42,10 +46,11 @@ def _owner(p):
 class _Plan:
     """Segment table of one flat module for one optimiser: device arrays + the parameters per group, built once."""
 
-    def __init__(self, module, items):
-        # items: [(offset in elements, parameter, group index)]
+    def __init__(self, module, items, table=False):
+        # items: [(offset in elements, parameter, group index)]; table: stepped through the device-table entry points
         items = sorted(items, key=lambda t: t[0])
-        self.module, self.items = module, items
+        self.module, self.items, self.table = module, items, table
+        self.host = None       # table path: the ctypes arrays the hyper-parameters are handed over in, the device table
         f = module._flat
         self.n = f.numel()
         self.base, self.gbase = f.data_ptr(), module._flat_grad.data_ptr()
@@ -90,6 +95,44 @@ def _build_plans(param_groups):
     return [_Plan(m, items) for m, items in per_module.values()], loose
 
 
+def _build_table_plans(param_groups, owner=_owner):
+    """As _build_plans for more than _lib.OPT_MAX_GROUPS groups: one table _Plan (group index = index into param_groups) per flat
+    module that owns parameters of this optimiser; loose carries only groups that have parameters outside flat buffers.
+    `owner` finds a parameter's flat module (tests pass their own for buffers that are not on a GPU)."""
+    if len(param_groups) > _lib.OPT_TABLE_MAX_GROUPS:
+        raise _lib.BvcError(f"{len(param_groups)} parameter groups: the device table carries {_lib.OPT_TABLE_MAX_GROUPS}")
+    loose, per_module = {}, {}
+    for gi, group in enumerate(param_groups):
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            m = owner(p)
+            if m is None:
+                loose.setdefault(gi, []).append(p)     # (checked for f32 CUDA where the runs are formed)
+                continue
+            if p.dtype != torch.float32 or p.grad.dtype != torch.float32:
+                raise _lib.BvcError("the bvc optimisers handle f32 CUDA parameters only")
+            per_module.setdefault(id(m), (m, []))[1].append(((p.data_ptr() - m._flat.data_ptr()) // 4, p, gi))
+    return [_Plan(m, items, table=True) for m, items in per_module.values()], loose
+
+
+def _choose_plans(param_groups):
+    """By-value plans up to _lib.OPT_MAX_GROUPS groups (unchanged), table plans up to _lib.OPT_TABLE_MAX_GROUPS, above that the
+    per-run path for everything (what _build_plans answers)."""
+    if _lib.OPT_MAX_GROUPS < len(param_groups) <= _lib.OPT_TABLE_MAX_GROUPS:
+        return _build_table_plans(param_groups)
+    return _build_plans(param_groups)
+
+
+def _table_host(ngroups, reals, ctype, flags, device):
+    """What a table plan keeps between steps: one ctypes array of `ngroups` entries per hyper-parameter (the library reads them
+    before the call returns and passes them on as kernel arguments) and the device table of 8 floats per group it writes."""
+    host = {n: (ctype * ngroups)() for n in reals}
+    host.update({n: (ctypes.c_int32 * ngroups)() for n in flags})
+    host["table"] = torch.zeros(8 * ngroups, dtype=torch.float32, device=device)
+    return host
+
+
 def _plans_key(param_groups):
     key = []
     for g in param_groups:
@@ -104,6 +147,27 @@ def _plans_key(param_groups):
                     ps[-1].grad.data_ptr() if ps[-1].grad is not None else 0,
                     sum(1 for p in ps if p.grad is not None)))
     return tuple(key)
+
+
+def _plans_still_valid(cached, key):
+    """The key moved although nothing the plans depend on did: gradients of parameters OUTSIDE flat buffers are fresh autograd
+    allocations every step, and where one of them is the first or last parameter of a group its address is part of the key.  True
+    if the groups are the same lists as before (lengths, first / last parameter, number of gradients) and every parameter of every
+    plan still sits, with its gradient, where the plan has it; then the plans - and the flat optimiser state that hangs on them - stay."""
+    old_key, plans, loose = cached
+    if len(old_key) != len(key):
+        return False
+    for a, b in zip(old_key, key):
+        if (a == 0) != (b == 0) or (a != 0 and (a[0], a[1], a[2], a[5]) != (b[0], b[1], b[2], b[5])):
+            return False
+    for plan in plans:
+        f, g = plan.module._flat, plan.module._flat_grad
+        if f is None or g is None or f.data_ptr() != plan.base or g.data_ptr() != plan.gbase:
+            return False
+        for off, p, _gi in plan.items:
+            if p.grad is None or p.data_ptr() != plan.base + 4 * off or p.grad.data_ptr() != plan.gbase + 4 * off:
+                return False
+    return all(p.grad is not None for ps in loose.values() for p in ps)
 
 
 class SGD(torch.optim.Optimizer):
@@ -122,8 +186,10 @@ class SGD(torch.optim.Optimizer):
 
     def _get_plans(self):
         key = _plans_key(self.param_groups)
+        if self._plans is not None and self._plans[0] != key and _plans_still_valid(self._plans, key):
+            self._plans = (key, self._plans[1], self._plans[2])
         if self._plans is None or self._plans[0] != key:
-            plans, loose = _build_plans(self.param_groups)
+            plans, loose = _choose_plans(self.param_groups)
             self._plans = (key, plans, loose)
             self._runs = {}
         return self._plans[1], self._plans[2]
@@ -164,6 +230,8 @@ class SGD(torch.optim.Optimizer):
         return runs
 
     def _group_runs(self, gi, ps):
+        if not ps:      # a group without gradients (the fallback for more groups than any table carries lists every group)
+            return []
         key = (len(ps), ps[0].data_ptr(), ps[-1].data_ptr(),
                ps[0].grad.data_ptr() if ps[0].grad is not None else 0,
                ps[-1].grad.data_ptr() if ps[-1].grad is not None else 0)
@@ -195,6 +263,36 @@ class SGD(torch.optim.Optimizer):
             fresh = not have
         return flat, fresh
 
+    def _step_table(self, plan, L, gs, fi, found_inf, stream):
+        """One flat module with more groups than the by-value struct carries: the hyper-parameters go as plain host arrays, the
+        library stores them into the plan's device table (one row per group) and steps the buffer with one launch."""
+        ng = len(self.param_groups)
+        if plan.host is None:
+            plan.host = _table_host(ng, ("lr", "momentum", "dampening", "weight_decay"), ctypes.c_float,
+                                    ("nesterov", "first_step", "maximize"), plan.module._flat.device)
+        H = plan.host
+        need_buf = any(g["momentum"] != 0 for g in self.param_groups)
+        flat, fresh = self._plan_momentum(plan) if need_buf else (None, {})
+        for gi, g in enumerate(self.param_groups):
+            H["lr"][gi], H["momentum"][gi], H["dampening"][gi], H["weight_decay"][gi] = float(g["lr"]), float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"])
+            H["nesterov"][gi], H["maximize"][gi] = int(g["nesterov"]), int(g["maximize"])
+            # torch's first step sets buf = g without dampening; only matters when dampening != 0
+            H["first_step"][gi] = int(bool(fresh.get(gi)) and g["dampening"] != 0 and found_inf is None)
+        _lib.check(L.bvc_op_sgd_step_table(
+            plan.base, plan.gbase, flat.data_ptr() if flat is not None else None, plan.n, plan.seg_start.data_ptr(),
+            plan.seg_group.data_ptr(), plan.blk_seg.data_ptr(), plan.nseg, ng, H["lr"], H["momentum"], H["dampening"], H["weight_decay"],
+            H["nesterov"], H["first_step"], H["maximize"], H["table"].data_ptr(), gs, fi, 1, _flat.shadow_for(plan.base, plan.n), stream),
+            "bvc_op_sgd_step_table")
+        if fresh:
+            plan.state = (flat, {})
+
+    def load_state_dict(self, state_dict):
+        """torch's, then the cached plans and runs are dropped: their flat state lives outside ``self.state``, the next step rebuilds
+        it from the loaded per-parameter tensors (a rollback or a resume into an optimiser that has already stepped)."""
+        super().load_state_dict(state_dict)
+        self._plans = None
+        self._runs = {}
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -209,6 +307,9 @@ class SGD(torch.optim.Optimizer):
         fi = found_inf.data_ptr() if found_inf is not None else None
         plans, loose = self._get_plans()
         for plan in plans:
+            if plan.table:
+                self._step_table(plan, L, gs, fi, found_inf, stream)
+                continue
             G = _lib.SgdGroupsC()
             G.ngroups = len(self.param_groups)
             need_buf = any(g["momentum"] != 0 for g in self.param_groups)
@@ -268,13 +369,20 @@ class Adam(torch.optim.Optimizer):
     _group_runs = SGD._group_runs
     _get_plans = SGD._get_plans
 
+    def load_state_dict(self, state_dict):
+        """As SGD.load_state_dict: the cached flat state is dropped, the next step adopts the loaded ``step`` / ``exp_avg`` / ``exp_avg_sq``."""
+        super().load_state_dict(state_dict)
+        self._plans = None
+        self._runs = {}
+
     def _plan_state(self, plan):
         """Flat exp_avg / exp_avg_sq per flat module, the per-group step scalars (3 per group) and the f64 upload scratch."""
         if plan.state is None:
             dev = plan.module._flat.device
             m, v = torch.zeros(plan.n, dtype=torch.float32, device=dev), torch.zeros(plan.n, dtype=torch.float32, device=dev)
-            state = torch.zeros(3 * _lib.OPT_MAX_GROUPS, dtype=torch.float32, device=dev)
-            hyper = torch.zeros(3 * _lib.OPT_MAX_GROUPS, dtype=torch.float64, device=dev)
+            # (a table plan has a row of step scalars for every group of the optimiser and needs no upload scratch)
+            state = torch.zeros(3 * (len(self.param_groups) if plan.table else _lib.OPT_MAX_GROUPS), dtype=torch.float32, device=dev)
+            hyper = None if plan.table else torch.zeros(3 * _lib.OPT_MAX_GROUPS, dtype=torch.float64, device=dev)
             for off, p, gi in plan.items:
                 st = self.state[p]
                 k = p.numel()
@@ -327,6 +435,22 @@ class Adam(torch.optim.Optimizer):
         plans, loose = self._get_plans()
         for plan in plans:
             m, v, state, hyper = self._plan_state(plan)
+            if plan.table:
+                ng = len(self.param_groups)
+                if plan.host is None:
+                    plan.host = _table_host(ng, ("lr", "beta1", "beta2", "eps", "weight_decay"), ctypes.c_double,
+                                            ("decoupled", "maximize"), plan.module._flat.device)
+                H = plan.host
+                for gi, g in enumerate(self.param_groups):
+                    b1, b2 = g["betas"]
+                    H["lr"][gi], H["beta1"][gi], H["beta2"][gi], H["eps"][gi], H["weight_decay"][gi] = float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"])
+                    H["decoupled"][gi], H["maximize"][gi] = int(self._decoupled), int(g["maximize"])
+                _lib.check(L.bvc_op_adam_step_table(
+                    plan.base, plan.gbase, m.data_ptr(), v.data_ptr(), plan.n, plan.seg_start.data_ptr(), plan.seg_group.data_ptr(),
+                    plan.blk_seg.data_ptr(), plan.nseg, ng, H["lr"], H["beta1"], H["beta2"], H["eps"], H["weight_decay"], H["decoupled"],
+                    H["maximize"], state.data_ptr(), H["table"].data_ptr(), gs, fi, 1, _flat.shadow_for(plan.base, plan.n), stream),
+                    "bvc_op_adam_step_table")
+                continue
             G = _lib.AdamGroupsC()
             G.ngroups = len(self.param_groups)
             for gi, g in enumerate(self.param_groups):
@@ -365,3 +489,68 @@ class AdamW(Adam):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
+
+
+# ---------------------------------------------------------------------------------------------- layer-wise learning-rate decay
+def _layer_ids(model):
+    """-> ({parameter name: layer id}, L) with id 0 for the embeddings, i + 1 for encoder layer i and L + 1 for everything after."""
+    import re
+    from .jepa import VisionTransformer
+    from .videomae import VideoMAEForVideoClassification
+    names = [n for n, _ in model.named_parameters()]
+    if isinstance(model, VideoMAEForVideoClassification):
+        layer, emb = re.compile(r"videomae\.encoder\.layer\.(\d+)\."), "videomae.embeddings."
+        depth = int(model.config.num_hidden_layers)
+        ids = {}
+        for n in names:
+            hit = layer.match(n)
+            ids[n] = 0 if n.startswith(emb) else int(hit.group(1)) + 1 if hit else depth + 1
+        return ids, depth
+    if isinstance(model, VisionTransformer):
+        layer = re.compile(r"blocks\.(\d+)\.")
+        depth = 1 + max(int(layer.match(n).group(1)) for n in names if layer.match(n))
+        ids = {}
+        for n in names:
+            hit = layer.match(n)
+            if n == "pos_embed" or n.startswith("patch_embed."):
+                ids[n] = 0
+            elif hit:
+                ids[n] = int(hit.group(1)) + 1
+            elif n.startswith("norm."):
+                ids[n] = depth + 1
+            else:
+                raise ValueError(f"layer_decay_param_groups: no layer id for parameter {n!r}")
+        return ids, depth
+    raise TypeError(f"layer_decay_param_groups: {type(model).__name__} is neither VideoMAEForVideoClassification nor a JEPA encoder")
+
+
+def layer_decay_param_groups(model, lr, weight_decay, layer_decay, no_weight_decay=()):
+    """Parameter groups for fine-tuning with layer-wise learning-rate decay, for ``bvc.optim.AdamW`` (or ``torch.optim.AdamW``).
+
+    With L encoder layers, the embeddings have layer id 0, encoder layer i has id i + 1, everything after the encoder (final norm,
+    ``fc_norm``, ``classifier``) has id L + 1; a parameter of layer id k trains at ``lr * layer_decay ** (L + 1 - k)``.  Each layer is
+    split in two: 1-D tensors, ``*.bias`` and the names in ``no_weight_decay`` get ``weight_decay`` 0, the rest the given value.
+    That is up to ``2 * (L + 2)`` groups (``layer_{k}_decay`` / ``layer_{k}_no_decay``; empty ones are left out), each with its
+    ``lr_scale`` so that a schedule can rescale them (``set_base_lr``).  Parameters with ``requires_grad=False`` are left out."""
+    ids, depth = _layer_ids(model)
+    skip = set(no_weight_decay)
+    groups = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        k = ids[name]
+        plain = p.ndim == 1 or name.endswith(".bias") or name in skip
+        key = (k, plain)
+        if key not in groups:
+            scale = float(layer_decay) ** (depth + 1 - k)
+            groups[key] = {"name": f"layer_{k}_{'no_decay' if plain else 'decay'}", "lr_scale": scale, "lr": lr * scale,
+                           "weight_decay": 0.0 if plain else weight_decay, "params": []}
+        groups[key]["params"].append(p)
+    return [groups[key] for key in sorted(groups, key=lambda t: (t[0], t[1]))]
+
+
+def set_base_lr(optimizer, lr):
+    """Sets every group's ``lr`` to ``lr * group["lr_scale"]`` (1 where a group has none): the one line a warm-up or cosine schedule
+    needs on top of ``layer_decay_param_groups``."""
+    for g in optimizer.param_groups:
+        g["lr"] = lr * g.get("lr_scale", 1.0)

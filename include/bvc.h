@@ -514,6 +514,25 @@ int bvc_op_adam_step_segments(float* params, float* grads, float* exp_avg, float
                               const int32_t* seg_group, const int32_t* blk_seg, int nseg, const bvc_adam_groups* groups, float* state,
                               double* hyper_scratch, const float* grad_scale, const float* found_inf, int write_unscaled_grads,
                               void* bf16_shadow, void* stream);
+/* The segment updates for MORE parameter groups than a by-value struct carries (layer-wise learning-rate decay: 2 (layers + 2)
+ * groups, 28 / 52 / 68 at base / large / huge).  Same segment table, same arithmetic per element; the hyper-parameters are plain host
+ * arrays of `ngroups` entries (1..BVC_OPT_TABLE_MAX_GROUPS), read before the call returns.  Inside the call they are stored into
+ * group_table (device f32 [8 ngroups], 16-byte aligned, owned by the caller, contents need not survive between calls) by small
+ * kernels that take BVC_OPT_TABLE_CHUNK groups per launch as kernel arguments - no host synchronisation, no copy out of host memory
+ * that has to outlive the call - and the update kernel reads row seg_group[s] of it.  A segment whose group is outside [0, ngroups) is
+ * left untouched.  state = device f32 [3 ngroups] as for bvc_op_adam_step_segments. */
+#define BVC_OPT_TABLE_MAX_GROUPS 1024
+#define BVC_OPT_TABLE_CHUNK 64
+int bvc_op_sgd_step_table(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,
+                          const int32_t* blk_seg, int nseg, int ngroups, const float* lr, const float* momentum, const float* dampening,
+                          const float* weight_decay, const int32_t* nesterov, const int32_t* first_step, const int32_t* maximize,
+                          float* group_table, const float* grad_scale, const float* found_inf, int write_unscaled_grads,
+                          void* bf16_shadow, void* stream);
+int bvc_op_adam_step_table(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const int64_t* seg_start,
+                           const int32_t* seg_group, const int32_t* blk_seg, int nseg, int ngroups, const double* lr, const double* beta1,
+                           const double* beta2, const double* eps, const double* weight_decay, const int32_t* decoupled,
+                           const int32_t* maximize, float* state, float* group_table, const float* grad_scale, const float* found_inf,
+                           int write_unscaled_grads, void* bf16_shadow, void* stream);
 /* GradScaler's inf check (scaler.step at pretrain_videomae.py:313 -> torch.amp.GradScaler._check_inf_per_device) as one read-only
  * pass over a flat f32 range: *found_inf (device f32) is set to 1 if any element is Inf or NaN; it is never cleared here. */
 int bvc_op_nonfinite_check(const float* x, int64_t n, float* found_inf, void* stream);

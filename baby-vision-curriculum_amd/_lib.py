@@ -71,6 +71,11 @@ class AdamGroupsC(ctypes.Structure):
                [(n, c_int * OPT_MAX_GROUPS) for n in ("decoupled", "maximize")]
 
 
+class NormItemC(ctypes.Structure):
+    """bvc_norm_item (include/bvc.h): one work item of the gradient-norm pass"""
+    _fields_ = [("start", c_int64), ("length", ctypes.c_int32), ("segment", ctypes.c_int32)]
+
+
 class GemmDesc(ctypes.Structure):
     _fields_ = [
         ("A", c_void_p), ("B", c_void_p),
@@ -237,6 +242,12 @@ SYMBOLS = {
     "bvc_op_adam_step_table": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 +
                                        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bvc_op_nonfinite_check": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "bvc_op_grad_norm_item_cap": (c_int, []),
+    "bvc_op_grad_norm_chain": (c_int, []),
+    "bvc_grad_norm_items_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, ctypes.POINTER(c_int64)]),
+    "bvc_op_grad_sqnorm_items": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "bvc_op_clip_finalize": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_scale_by_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "bvc_op_mask_index": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_dual_mask_index": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_gather_patches": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

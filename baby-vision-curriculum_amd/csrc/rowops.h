@@ -88,6 +88,15 @@ int launch_pad_heads(const bf16_t* wqkv, const float* bqkv, const bf16_t* wo, bf
 int launch_unpad_head_grads(const float* gwqkv_p, const float* gbqkv_p, const float* gwo_p, float* gwqkv, float* gbqkv, float* gwo, int D,
                             int H, int hd, int hdp, hipStream_t s);
 int launch_nonfinite_check(const float* x, size_t n, float* found_inf, hipStream_t s);
+// gradient norms for clipping (include/bvc.h, "gradient-norm clipping"): the host work list, the item kernel + fixed-order reduce
+// (one launch pair), the clip values on the device, x *= *coef
+int grad_norm_chain();
+int grad_norm_items_host(const int64_t* seg_start, const int32_t* seg_group, int nseg, bvc_norm_item* items, int64_t items_cap,
+                         int64_t* seg_first_item, int64_t* nitems);
+int launch_grad_sqnorm_items(const float* x, const bvc_norm_item* items, int64_t nitems, const int64_t* seg_first_item, int nseg,
+                             double* item_partial, float* seg_sq, float* total_sq, int as_norm, float* found_inf, hipStream_t s);
+int launch_clip_finalize(const float* sq, int nranges, float max_norm, const float* grad_scale, float* out3, hipStream_t s);
+int launch_scale_by_dev(float* x, size_t n, const float* coef, hipStream_t s);
 int launch_row_normalize(const float* f, bf16_t* fn, float* inv, int n, int p, float eps, hipStream_t s);
 int launch_row_normalize_bwd(const float* f, const float* inv, const float* dfn, float* df, int n, int p, hipStream_t s);
 int launch_nce_finalize(const float* partial, int ntiles, float inv_t, double npos, float* loss, float* stats, hipStream_t s);

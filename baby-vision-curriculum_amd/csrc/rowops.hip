@@ -1529,6 +1529,117 @@ __global__ void nonfinite_check_kernel(const float* __restrict__ x, size_t n, fl
     if (__any(bad) && (threadIdx.x & 63) == 0) *found_inf = 1.0f;
 }
 
+// ---------------------------------------------------------------------------------------------- gradient norms (clipping)
+// Squared norm of the owned segments of a flat f32 range in ONE read, with GradScaler's inf check riding on the same read.
+// The range is cut on the host (grad_norm_items_host below) into items of at most kNormItemCap elements that never cross a segment
+// boundary; one workgroup takes one item.  Inside an item the first 16-byte boundary splits off up to 3 head elements, whole 16-byte
+// vectors follow and up to 3 tail elements remain; thread t takes vectors t, t + 256, ... (at most kNormChain of them) into four f32
+// accumulators by fused multiply-add - the longest serial f32 chain any element's square passes through is kNormChain terms.
+// Everything after that (the four lanes, the head / tail squares, the wave, the four waves, the items of a segment, the segments)
+// is added in f64 in a fixed order: no atomics, the same bits on every run, and no f32 rounding besides the final cast.
+constexpr int kNormItemCap = BVC_GRAD_NORM_ITEM_CAP;
+constexpr int kNormChain = kNormItemCap / (256 * 4);
+static_assert(kNormChain * 256 * 4 == kNormItemCap, "an item is a whole number of 16-byte vectors per thread");
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// 256 threads -> the sum in thread 0 (waves added as (w0 + w1) + (w2 + w3))
+__device__ __forceinline__ double block_sum_f64(double v, double* lds4) {
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+
+__global__ __launch_bounds__(256) void grad_sqnorm_items_kernel(const float* __restrict__ x, const bvc_norm_item* __restrict__ items,
+                                                                double* __restrict__ item_partial, float* __restrict__ found_inf) {
+    __shared__ double lds4[4];
+    const bvc_norm_item it = items[blockIdx.x];
+    const float* __restrict__ p = x + it.start;
+    const int len = it.length, tid = threadIdx.x;
+    int head = (int)((4 - (((uintptr_t)p >> 2) & 3)) & 3);       // elements before the first 16-byte boundary
+    head = head < len ? head : len;
+    const int nvec = (len - head) >> 2;
+    const int tail0 = head + 4 * nvec;
+    const f32x4* __restrict__ pv = reinterpret_cast<const f32x4*>(p + head);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float t = 0.f;                                               // (v - v) is 0 for finite values and NaN for Inf / NaN
+    if (nvec == kNormChain * 256) {                              // a full item: every load of the thread is issued before the first use
+        f32x4 v[kNormChain];
+#pragma unroll
+        for (int k = 0; k < kNormChain; ++k) v[k] = pv[tid + 256 * k];
+#pragma unroll
+        for (int k = 0; k < kNormChain; ++k) {
+            acc = __builtin_elementwise_fma(v[k], v[k], acc);
+            t += (v[k][0] - v[k][0]) + (v[k][1] - v[k][1]) + (v[k][2] - v[k][2]) + (v[k][3] - v[k][3]);
+        }
+    } else {
+#pragma unroll 4
+        for (int i = tid; i < nvec; i += 256) {
+            const f32x4 v = pv[i];
+            acc = __builtin_elementwise_fma(v, v, acc);
+            t += (v[0] - v[0]) + (v[1] - v[1]) + (v[2] - v[2]) + (v[3] - v[3]);
+        }
+    }
+    double ht = 0.0;                                             // head / tail elements: at most one of each per thread
+    if (tid < head) { const float h = p[tid]; ht = (double)h * (double)h; t += h - h; }
+    if (tail0 + tid < len) { const float e = p[tail0 + tid]; ht += (double)e * (double)e; t += e - e; }
+    const double mine = (((double)acc[0] + (double)acc[1]) + ((double)acc[2] + (double)acc[3])) + ht;
+    const double sum = block_sum_f64(mine, lds4);
+    if (tid == 0) item_partial[blockIdx.x] = sum;
+    if (found_inf != nullptr && __any(t != 0.f) && (tid & 63) == 0) *found_inf = 1.0f;
+}
+
+// item partials -> seg_sq[s] (block s < nseg: the items seg_first_item[s] .. seg_first_item[s + 1] of segment s, nothing for an unowned
+// one) and total_sq (the last block: every item), f64 in a fixed order, cast to f32 at the end; as_norm: the square roots instead
+__global__ __launch_bounds__(256) void grad_sqnorm_reduce_kernel(const double* __restrict__ item_partial, const int64_t* __restrict__ seg_first_item,
+                                                                 int nseg, int64_t nitems, float* __restrict__ seg_sq,
+                                                                 float* __restrict__ total_sq, int as_norm) {
+    __shared__ double lds4[4];
+    const bool total = seg_sq == nullptr || (int)blockIdx.x == nseg;
+    const int64_t lo = total ? 0 : seg_first_item[blockIdx.x], hi = total ? nitems : seg_first_item[blockIdx.x + 1];
+    double a = 0.0;
+#pragma unroll 8
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) a += item_partial[i];      // (loads run ahead, the additions keep their order)
+    const double sum = block_sum_f64(a, lds4);
+    if (threadIdx.x == 0) {
+        const float r = as_norm ? (float)sqrt(sum) : (float)sum;
+        if (total) *total_sq = r; else seg_sq[blockIdx.x] = r;
+    }
+}
+
+// out = {total_norm, clip_coef, eff_scale}: total_norm = sqrt(sum sq) / scale, clip_coef = min(1, max_norm / (total_norm + 1e-6)) with
+// torch's clamp (a NaN stays a NaN), eff_scale = scale / clip_coef - what a step kernel divides the gradients by to unscale AND clip.
+// The few sq entries are added in f64, the rest is f32 arithmetic as torch.nn.utils.clip_grad_norm_ does it.
+__global__ void clip_finalize_kernel(const float* __restrict__ sq, int nranges, float max_norm, const float* __restrict__ grad_scale,
+                                     float* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = 0; i < nranges; ++i) s += (double)sq[i];
+    const float scale = grad_scale ? *grad_scale : 1.f;
+    const float norm = sqrtf((float)s) / scale;
+    const float c = max_norm / (norm + 1e-6f);
+    const float coef = c > 1.f ? 1.f : c;
+    out[0] = norm; out[1] = coef; out[2] = scale / coef;
+}
+
+// x *= *coef; nothing is written when *coef == 1 (an inactive clip costs the read of one scalar)
+__global__ void scale_by_dev_kernel(float* __restrict__ x, size_t n, const float* __restrict__ coef) {
+    const float c = *coef;
+    if (c == 1.0f) return;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (size_t)gridDim.x * blockDim.x;
+    size_t head = (4 - (((uintptr_t)x >> 2) & 3)) & 3;
+    head = head < n ? head : n;
+    const size_t nvec = (n - head) / 4;
+    f32x4* __restrict__ xv = reinterpret_cast<f32x4*>(x + head);
+    for (size_t i = tid; i < nvec; i += nthreads) xv[i] = xv[i] * c;
+    if (tid < head) x[tid] *= c;
+    if (head + 4 * nvec + tid < n) x[head + 4 * nvec + tid] *= c;
+}
+
 // ============================================================================ launchers
 static inline unsigned blocks_for(size_t items, int per = 256) { return (unsigned)((items + per - 1) / per); }
 
@@ -2035,6 +2146,60 @@ int launch_nonfinite_check(const float* x, size_t n, float* found_inf, hipStream
     const size_t want = (n / 4 + 255) / 256 + 1;
     const unsigned blocks = (unsigned)(want < 8192 ? want : 8192);
     hipLaunchKernelGGL(nonfinite_check_kernel, dim3(blocks), dim3(256), 0, s, x, n, found_inf);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int grad_norm_chain() { return kNormChain; }
+
+// The static work list of a segment table (host): every owned segment (seg_group >= 0) is cut front to back into items of at most
+// kNormItemCap elements, in segment order, so that the items of a segment are adjacent and ascending; seg_first_item[s] is the index
+// of segment s's first item (seg_first_item[nseg] = the item count).  items == nullptr: count only.
+int grad_norm_items_host(const int64_t* seg_start, const int32_t* seg_group, int nseg, bvc_norm_item* items, int64_t items_cap,
+                         int64_t* seg_first_item, int64_t* nitems) {
+    int64_t count = 0;
+    for (int s = 0; s < nseg; ++s) {
+        BVC_REQUIRE(seg_start[s] <= seg_start[s + 1], "grad_norm_items: seg_start must ascend (segment %d)", s);
+        if (seg_first_item) seg_first_item[s] = count;
+        if (seg_group[s] < 0) continue;
+        for (int64_t at = seg_start[s]; at < seg_start[s + 1]; at += kNormItemCap) {
+            const int64_t left = seg_start[s + 1] - at;
+            if (items) {
+                BVC_REQUIRE(count < items_cap, "grad_norm_items: more than the %lld items the caller has room for", (long long)items_cap);
+                items[count] = bvc_norm_item{at, (int32_t)(left < kNormItemCap ? left : kNormItemCap), (int32_t)s};
+            }
+            ++count;
+        }
+    }
+    if (seg_first_item) seg_first_item[nseg] = count;
+    *nitems = count;
+    return BVC_OK;
+}
+
+int launch_grad_sqnorm_items(const float* x, const bvc_norm_item* items, int64_t nitems, const int64_t* seg_first_item, int nseg,
+                             double* item_partial, float* seg_sq, float* total_sq, int as_norm, float* found_inf, hipStream_t s) {
+    BVC_REQUIRE(((uintptr_t)x % 4) == 0, "grad_sqnorm_items: the range must be 4-byte aligned");
+    BVC_REQUIRE(nitems <= 0x7fffffff, "grad_sqnorm_items: %lld items", (long long)nitems);
+    BVC_REQUIRE(nitems == 0 || (items != nullptr && item_partial != nullptr), "grad_sqnorm_items: item table / partials missing");
+    BVC_REQUIRE(seg_sq == nullptr || (seg_first_item != nullptr && nseg >= 0), "grad_sqnorm_items: seg_sq needs seg_first_item");
+    if (nitems > 0)
+        hipLaunchKernelGGL(grad_sqnorm_items_kernel, dim3((unsigned)nitems), dim3(256), 0, s, x, items, item_partial, found_inf);
+    hipLaunchKernelGGL(grad_sqnorm_reduce_kernel, dim3(seg_sq ? (unsigned)nseg + 1 : 1u), dim3(256), 0, s, (const double*)item_partial,
+                       seg_first_item, nseg, nitems, seg_sq, total_sq, as_norm);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_clip_finalize(const float* sq, int nranges, float max_norm, const float* grad_scale, float* out3, hipStream_t s) {
+    hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(64), 0, s, sq, nranges, max_norm, grad_scale, out3);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_scale_by_dev(float* x, size_t n, const float* coef, hipStream_t s) {
+    if (n == 0) return BVC_OK;
+    const size_t want = (n / 4 + 255) / 256 + 1;
+    hipLaunchKernelGGL(scale_by_dev_kernel, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, s, x, n, coef);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

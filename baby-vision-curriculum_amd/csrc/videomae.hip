@@ -1055,6 +1055,28 @@ int bvc_op_nonfinite_check(const float* x, int64_t n, float* found_inf, void* st
     BVC_REQUIRE(x && found_inf && n >= 0, "op_nonfinite_check: bad argument");
     return launch_nonfinite_check(x, (size_t)n, found_inf, (hipStream_t)stream);
 }
+int bvc_op_grad_norm_item_cap(void) { return BVC_GRAD_NORM_ITEM_CAP; }
+int bvc_op_grad_norm_chain(void) { return grad_norm_chain(); }
+int bvc_grad_norm_items_host(const int64_t* seg_start, const int32_t* seg_group, int nseg, bvc_norm_item* items, int64_t items_cap,
+                             int64_t* seg_first_item, int64_t* nitems) {
+    BVC_REQUIRE(nseg >= 0 && nitems && (nseg == 0 || (seg_start && seg_group)) && (items == nullptr || items_cap >= 0),
+                "grad_norm_items_host: bad argument");
+    return grad_norm_items_host(seg_start, seg_group, nseg, items, items_cap, seg_first_item, nitems);
+}
+int bvc_op_grad_sqnorm_items(const float* x, const bvc_norm_item* items, int64_t nitems, const int64_t* seg_first_item, int nseg,
+                             double* item_partial, float* seg_sq, float* total_sq, int as_norm, float* found_inf, void* stream) {
+    BVC_REQUIRE(x && total_sq && nitems >= 0, "op_grad_sqnorm_items: bad argument");
+    return launch_grad_sqnorm_items(x, items, nitems, seg_first_item, nseg, item_partial, seg_sq, total_sq, as_norm, found_inf,
+                                    (hipStream_t)stream);
+}
+int bvc_op_clip_finalize(const float* sq, int nranges, float max_norm, const float* grad_scale, float* out3, void* stream) {
+    BVC_REQUIRE(out3 && nranges >= 0 && (nranges == 0 || sq) && !(max_norm < 0.f) && max_norm == max_norm, "op_clip_finalize: bad argument");
+    return launch_clip_finalize(sq, nranges, max_norm, grad_scale, out3, (hipStream_t)stream);
+}
+int bvc_op_scale_by_dev(float* x, int64_t n, const float* coef, void* stream) {
+    BVC_REQUIRE(x && coef && n >= 0 && ((uintptr_t)x % 4) == 0, "op_scale_by_dev: bad argument");
+    return launch_scale_by_dev(x, (size_t)n, coef, (hipStream_t)stream);
+}
 int bvc_op_row_normalize(const float* f, void* fn_bf16, float* inv_norm, int n, int p, float eps, void* stream) {
     BVC_REQUIRE(f && fn_bf16 && inv_norm, "op_row_normalize: null argument");
     return launch_row_normalize(f, (bf16_t*)fn_bf16, inv_norm, n, p, eps, (hipStream_t)stream);

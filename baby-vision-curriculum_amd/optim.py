@@ -19,6 +19,15 @@ pretraining/generative/pretrain_videomae.py:187-189) and the same ``state_dict``
 ``_step_supports_amp_scaling`` so the scaler hands over its device-side ``grad_scale`` / ``found_inf``
 and the step neither unscales in a separate pass nor synchronises with the host
 (``scaler.step(optimizer)`` at pretrain_videomae.py:313 is unchanged).
+
+``max_grad_norm=c`` (keyword-only, on all three classes) clips the gradients by their global norm as
+``torch.nn.utils.clip_grad_norm_(params, c)`` before the step would, without a pass of its own: one read-only launch pair per flat
+buffer gives the squared norm of the segments this optimiser owns (``bvc_op_grad_sqnorm_items``; ``bvc.amp.GradScaler`` takes its inf
+check from that same read), ``bvc_op_clip_finalize`` turns the squares into ``{total_norm, clip_coef, scale / clip_coef}`` on the
+device, and the step calls are handed the address of the last where they were handed the scale's - the kernels that divide by the scale
+thereby clip too.  ``optimizer.grad_norm`` / ``optimizer.clip_coef`` are 0-d device views of the last step's values.  Immediate forms:
+``clip_grad_norm_`` (torch's signature) and ``grad_norms(module)`` (per-parameter norms in one launch pair).  DESIGN.md
+"Gradient-norm clipping".
 """
 import ctypes
 
@@ -67,6 +76,8 @@ class _Plan:
         starts.append(self.n)
         dev = f.device
         self.nseg = len(groups)
+        self.starts, self.groups = starts, groups      # the host copy of the table (the gradient-norm work list is cut from it)
+        self.norm = None       # _NormTable of this table, built by the first clipped step
         self.seg_start = torch.tensor(starts, dtype=torch.int64, device=dev)
         self.seg_group = torch.tensor(groups, dtype=torch.int32, device=dev)
         nblk = (self.n + 1023) // 1024
@@ -170,12 +181,75 @@ def _plans_still_valid(cached, key):
     return all(p.grad is not None for ps in loose.values() for p in ps)
 
 
+# ---------------------------------------------------------------------------------------------- gradient norms
+def _checked_max_grad_norm(value):
+    if value is None:
+        return None
+    value = float(value)
+    if value != value or value < 0.0:
+        raise ValueError(f"max_grad_norm must be a non-negative number or None, not {value}")
+    return value
+
+
+def grad_norm_work_list(seg_start, seg_group):
+    """The work list of the gradient-norm pass for a segment table (``bvc_grad_norm_items_host``; host only, no GPU):
+    -> (items: int64 CPU tensor [nitems][3] of (start, length, segment), seg_first_item: int64 CPU tensor [nseg + 1])."""
+    raw, first = _work_list_raw(seg_start, seg_group)
+    return torch.stack([raw[:, 0], raw[:, 1] & 0xFFFFFFFF, raw[:, 1] >> 32], dim=1), first
+
+
+def _work_list_raw(seg_start, seg_group):
+    """-> (the bvc_norm_item array as an int64 CPU tensor [nitems][2], seg_first_item)"""
+    nseg = len(seg_group)
+    if len(seg_start) != nseg + 1:
+        raise _lib.BvcError("a segment table has one more start than segments")
+    L = _lib.lib()
+    starts, groups = torch.tensor(list(seg_start), dtype=torch.int64), torch.tensor(list(seg_group), dtype=torch.int32)
+    first, n = torch.zeros(nseg + 1, dtype=torch.int64), ctypes.c_int64()
+    _lib.check(L.bvc_grad_norm_items_host(starts.data_ptr(), groups.data_ptr(), nseg, None, 0, first.data_ptr(), ctypes.byref(n)),
+               "bvc_grad_norm_items_host")
+    raw = torch.zeros((n.value, 2), dtype=torch.int64)
+    if n.value:
+        _lib.check(L.bvc_grad_norm_items_host(starts.data_ptr(), groups.data_ptr(), nseg, raw.data_ptr(), n.value, first.data_ptr(),
+                                              ctypes.byref(n)), "bvc_grad_norm_items_host")
+    return raw, first
+
+
+class _NormTable:
+    """The gradient-norm work list of one segment table on a device, with the f64 item partials the pass writes: static, built once."""
+
+    def __init__(self, seg_start, seg_group, device):
+        raw, first = _work_list_raw(seg_start, seg_group)
+        self.nseg, self.nitems = len(seg_group), raw.shape[0]
+        self.items, self.first = raw.to(device), first.to(device)
+        self.partial = torch.zeros(max(self.nitems, 1), dtype=torch.float64, device=device)
+
+    def launch(self, L, base, total, found_inf, stream, seg_out=None, as_norm=0):
+        """One launch pair over the range at address `base`: the total (squared) norm to address `total`, per segment to `seg_out`."""
+        _lib.check(L.bvc_op_grad_sqnorm_items(base, self.items.data_ptr() if self.nitems else None, self.nitems, self.first.data_ptr(),
+                                              self.nseg, self.partial.data_ptr(), seg_out, total, as_norm, found_inf, stream),
+                   "bvc_op_grad_sqnorm_items")
+
+
+_RUN_TABLES = {}     # (elements, device) -> the one-segment _NormTable of a plain contiguous range (launches of one stream share it)
+
+
+def _run_table(n, device):
+    hit = _RUN_TABLES.get((n, device))
+    if hit is None:
+        hit = _RUN_TABLES[(n, device)] = _NormTable([0, n], [0], device)
+    return hit
+
+
 class SGD(torch.optim.Optimizer):
     _step_supports_amp_scaling = True
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False):
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False,
+                 max_grad_norm=None):
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
             raise ValueError("invalid hyper-parameter")
+        self.max_grad_norm = _checked_max_grad_norm(max_grad_norm)
+        self._clip = None    # clipping: the device scalars and the squares of the last norm pass
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
@@ -193,6 +267,70 @@ class SGD(torch.optim.Optimizer):
             self._plans = (key, plans, loose)
             self._runs = {}
         return self._plans[1], self._plans[2]
+
+    # ---- gradient-norm clipping (max_grad_norm=): the clip rides on the scale pointer of the step calls, no kernel of theirs changes
+    def _clip_device(self):
+        for g in self.param_groups:
+            for p in g["params"]:
+                return p.device
+        raise _lib.BvcError("an optimiser without parameters has no gradient norm")
+
+    def _clip_buffers(self):
+        """{out: device f32 {total_norm, clip_coef, eff_scale}, sq: one square per flat buffer / loose run, nranges, tag}"""
+        if self._clip is None:
+            dev = self._clip_device()
+            self._clip = {"out": torch.zeros(3, dtype=torch.float32, device=dev), "sq": torch.zeros(8, dtype=torch.float32, device=dev),
+                          "nranges": 0, "tag": None}
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """0-d device view: the unscaled gradient norm of the last step before clipping (nonfinite where the gradients were).  No sync."""
+        return self._clip_buffers()["out"][0]
+
+    @property
+    def clip_coef(self):
+        """0-d device view: the coefficient the last step multiplied the gradients by (1 = the clip was inactive).  No sync."""
+        return self._clip_buffers()["out"][1]
+
+    def _grad_sq(self, found_inf=None, tag=None):
+        """Squared gradient norm of every plan (its owned segments: one launch pair over the plan's segment table) and of every loose
+        run (one launch pair each) into the `sq` buffer; `found_inf` (a device scalar) gets GradScaler's inf check out of the same
+        read.  `tag` marks the squares as taken for the step a scaler is about to make (bvc.amp.GradScaler, which withdraws the tag when
+        its step() returns)."""
+        L, stream = _lib.lib(), _lib.current_stream_ptr()
+        plans, loose = self._get_plans()
+        runs = [run for gi, ps in loose.items() for run in self._group_runs(gi, ps)]
+        c = self._clip_buffers()
+        dev = c["out"].device
+        if any(pl.module._flat.device != dev for pl in plans) or any(run[0].device != dev for run in runs):
+            raise _lib.BvcError("max_grad_norm needs all parameters of the optimiser on one device")
+        nr = len(plans) + len(runs)
+        if c["sq"].numel() < nr:
+            c["sq"] = torch.zeros(2 * nr, dtype=torch.float32, device=dev)
+        sq, fi = c["sq"].data_ptr(), found_inf.data_ptr() if found_inf is not None else None
+        for i, plan in enumerate(plans):
+            if plan.norm is None:
+                plan.norm = _NormTable(plan.starts, plan.groups, dev)
+            plan.norm.launch(L, plan.gbase, sq + 4 * i, fi, stream)
+        for i, run in enumerate(runs, len(plans)):
+            _run_table(sum(p.numel() for p in run), dev).launch(L, run[0].grad.data_ptr(), sq + 4 * i, fi, stream)
+        c["nranges"], c["tag"] = nr, tag
+        return c
+
+    def _clip_scale(self, L, stream, grad_scale, gs):
+        """-> the address the step calls divide the gradients by: eff_scale = scale / clip_coef of this step's norm.  The squares
+        bvc.amp.GradScaler left for this very step are consumed (they are of the scaled gradients: only together with the scale),
+        otherwise the norms are taken here."""
+        c = self._clip
+        if c is None or c["tag"] is None or grad_scale is None:
+            c = self._grad_sq()
+        c["tag"] = None
+        if c["nranges"] == 0:
+            return gs
+        _lib.check(L.bvc_op_clip_finalize(c["sq"].data_ptr(), c["nranges"], self.max_grad_norm, gs, c["out"].data_ptr(), stream),
+                   "bvc_op_clip_finalize")
+        return c["out"].data_ptr() + 8
 
     def _plan_momentum(self, plan):
         """One flat momentum buffer per flat module; the per-parameter ``momentum_buffer`` entries are views into it."""
@@ -306,6 +444,8 @@ class SGD(torch.optim.Optimizer):
         gs = grad_scale.data_ptr() if grad_scale is not None else None
         fi = found_inf.data_ptr() if found_inf is not None else None
         plans, loose = self._get_plans()
+        if self.max_grad_norm is not None:
+            gs = self._clip_scale(L, stream, grad_scale, gs)
         for plan in plans:
             if plan.table:
                 self._step_table(plan, L, gs, fi, found_inf, stream)
@@ -356,9 +496,12 @@ class Adam(torch.optim.Optimizer):
     _step_supports_amp_scaling = True
     _decoupled = False
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False,
+                 max_grad_norm=None):
         if amsgrad:
             raise NotImplementedError("amsgrad is not implemented (the reference does not use it)")
+        self.max_grad_norm = _checked_max_grad_norm(max_grad_norm)
+        self._clip = None
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=maximize))
@@ -368,6 +511,8 @@ class Adam(torch.optim.Optimizer):
     _contiguous_runs = staticmethod(SGD._contiguous_runs)
     _group_runs = SGD._group_runs
     _get_plans = SGD._get_plans
+    _clip_device, _clip_buffers, _grad_sq, _clip_scale = SGD._clip_device, SGD._clip_buffers, SGD._grad_sq, SGD._clip_scale
+    grad_norm, clip_coef = SGD.grad_norm, SGD.clip_coef
 
     def load_state_dict(self, state_dict):
         """As SGD.load_state_dict: the cached flat state is dropped, the next step adopts the loaded ``step`` / ``exp_avg`` / ``exp_avg_sq``."""
@@ -433,6 +578,8 @@ class Adam(torch.optim.Optimizer):
         L = _lib.lib()
         stream = _lib.current_stream_ptr()
         plans, loose = self._get_plans()
+        if self.max_grad_norm is not None:
+            gs = self._clip_scale(L, stream, grad_scale, gs)
         for plan in plans:
             m, v, state, hyper = self._plan_state(plan)
             if plan.table:
@@ -487,8 +634,10 @@ class AdamW(Adam):
     """torch.optim.AdamW: decoupled weight decay, default 1e-2."""
     _decoupled = True
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         max_grad_norm=max_grad_norm)
 
 
 # ---------------------------------------------------------------------------------------------- layer-wise learning-rate decay
@@ -554,3 +703,80 @@ def set_base_lr(optimizer, lr):
     needs on top of ``layer_decay_param_groups``."""
     for g in optimizer.param_groups:
         g["lr"] = lr * g.get("lr_scale", 1.0)
+
+
+# ---------------------------------------------------------------------------------------------- the immediate forms
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """``torch.nn.utils.clip_grad_norm_`` (same signature, same return value) for torch optimisers, or for gradients that are to be
+    clipped before they are logged; the ``bvc.optim`` optimisers clip inside their step (``max_grad_norm=``) at no extra pass.
+
+    f32 CUDA gradients with ``norm_type == 2``: one launch pair per run of memory-adjacent parameters (a whole flat module is one
+    run), one launch for the clip values on the device, one in-place scaling per run that writes nothing while the clip is inactive;
+    no host synchronisation unless ``error_if_nonfinite``.  Anything else goes to torch's function."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = list(parameters)
+    with_grad = [p for p in params if p.grad is not None]
+    fast = bool(with_grad) and float(norm_type) == 2.0 and all(
+        p.is_cuda and p.dtype == torch.float32 and p.grad.dtype == torch.float32 and p.grad.device == with_grad[0].device
+        and p.grad.is_contiguous() and p.is_contiguous() for p in with_grad)
+    if not fast:
+        return torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    max_norm = _checked_max_grad_norm(max_norm)
+    dev = with_grad[0].device
+    L = _lib.lib()
+    runs = SGD._contiguous_runs(with_grad)
+    sq, out = torch.zeros(len(runs), dtype=torch.float32, device=dev), torch.zeros(3, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream_ptr()
+        sizes = [sum(p.numel() for p in run) for run in runs]
+        for i, (run, n) in enumerate(zip(runs, sizes)):
+            _run_table(n, dev).launch(L, run[0].grad.data_ptr(), sq.data_ptr() + 4 * i, None, stream)
+        _lib.check(L.bvc_op_clip_finalize(sq.data_ptr(), len(runs), max_norm, None, out.data_ptr(), stream), "bvc_op_clip_finalize")
+        if error_if_nonfinite and not bool(torch.isfinite(out[0])):      # (the one case that waits for the device)
+            raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be "
+                               "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                               "`error_if_nonfinite=False`")
+        for run, n in zip(runs, sizes):
+            _lib.check(L.bvc_op_scale_by_dev(run[0].grad.data_ptr(), n, out.data_ptr() + 4, stream), "bvc_op_scale_by_dev")
+    return out[0]
+
+
+def grad_norms(module):
+    """Per-parameter gradient norms of a module in ONE launch pair and without a host synchronisation:
+    ``{state-dict name: 0-d device view}`` for every parameter that has a gradient, and ``"total"``.  The gradients are taken as one
+    segment table in address order - a flat module's gradient buffer is one stretch of it, gradients outside it are further
+    segments, the memory between them belongs to nobody - so the work list is rebuilt only when a gradient has moved.  The views
+    alias one device tensor that the next call for the same module overwrites."""
+    named = [(n, p) for n, p in module.named_parameters() if p.grad is not None]
+    if not named:
+        raise _lib.BvcError("grad_norms: no parameter of the module has a gradient")
+    dev = named[0][1].grad.device
+    for n, p in named:
+        g = p.grad
+        if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == dev):
+            raise _lib.BvcError(f"grad_norms: the gradient of {n} is not a contiguous f32 tensor on {dev}")
+    named.sort(key=lambda t: t[1].grad.data_ptr())
+    key = tuple((p.grad.data_ptr(), p.numel()) for _, p in named)
+    cache = getattr(module, "_bvc_grad_norms", None)
+    if cache is None or cache[0] != key:
+        base, starts, groups, where, pos = key[0][0], [], [], {}, 0
+        for (name, _p), (ptr, k) in zip(named, key):
+            off = (ptr - base) // 4
+            if off < pos or (ptr - base) % 4:
+                raise _lib.BvcError(f"grad_norms: the gradient of {name} overlaps another one")
+            if off > pos:
+                starts.append(pos); groups.append(-1)
+            where[name] = len(groups)
+            starts.append(off); groups.append(0)
+            pos = off + k
+        starts.append(pos)
+        table = _NormTable(starts, groups, dev)
+        cache = (key, table, where, torch.zeros(table.nseg + 1, dtype=torch.float32, device=dev))
+        module._bvc_grad_norms = cache
+    _key, table, where, out = cache
+    with torch.cuda.device(dev):
+        table.launch(_lib.lib(), key[0][0], out.data_ptr() + 4 * table.nseg, None, _lib.current_stream_ptr(), seg_out=out.data_ptr(), as_norm=1)
+    norms = {name: out[i] for name, i in where.items()}
+    norms["total"] = out[table.nseg]
+    return norms

@@ -536,6 +536,46 @@ int bvc_op_adam_step_table(float* params, float* grads, float* exp_avg, float* e
 /* GradScaler's inf check (scaler.step at pretrain_videomae.py:313 -> torch.amp.GradScaler._check_inf_per_device) as one read-only
  * pass over a flat f32 range: *found_inf (device f32) is set to 1 if any element is Inf or NaN; it is never cleared here. */
 int bvc_op_nonfinite_check(const float* x, int64_t n, float* found_inf, void* stream);
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_) without a pass of its own over the gradients.
+ *
+ * The squared norm of the OWNED segments of a flat f32 range - the segment table of the optimiser entry points above: seg_start
+ * [nseg + 1], seg_group [nseg], -1 = owned by nobody - comes out of one read, and GradScaler's inf check rides on the same read.  A
+ * plain contiguous range is a table of one segment.
+ *
+ * bvc_grad_norm_items_host (host, no GPU): the static work list of a table.  Every element of every owned segment lies in exactly one
+ * item (start, length, segment); no item crosses a segment boundary or is longer than bvc_op_grad_norm_item_cap() elements; unowned
+ * segments get none; the items of a segment are adjacent and ascending, seg_first_item [nseg + 1] (may be NULL) indexes them.
+ * items == NULL: only *nitems (and seg_first_item) are written, so a caller can size its array.
+ *
+ * bvc_op_grad_sqnorm_items: one launch pair.  The first launch takes one workgroup per item and writes the item's sum of squares to
+ * item_partial [nitems] (device f64): 16-byte loads from the first 16-byte boundary inside the item on, scalar loads for the up to
+ * three elements before it and after the last whole vector, so `x` needs 4-byte alignment only and segments may start anywhere.
+ * found_inf (device f32, may be NULL) is set to 1 if an element INSIDE AN ITEM is Inf or NaN (the test of bvc_op_nonfinite_check);
+ * it is never cleared.  The second launch adds the partials in a fixed order into seg_sq [nseg] (may be NULL; 0 for an unowned
+ * segment) and total_sq [1]; with as_norm != 0 both receive the square roots.  No atomics: the same bits on every run.
+ * Accuracy: a thread adds at most bvc_op_grad_norm_chain() squares serially in f32 (fused multiply-add); everything above that is
+ * added in f64 and rounded to f32 once.
+ *
+ * bvc_op_clip_finalize: out3 = {total_norm, clip_coef, eff_scale} from sq [nranges] (one entry per flat buffer or loose run of an
+ * optimiser), in one tiny launch: total_norm = sqrt(sum sq) / scale, clip_coef = min(1, max_norm / (total_norm + 1e-6)),
+ * eff_scale = scale / clip_coef, scale = *grad_scale or 1 when grad_scale is NULL.  Passing &out3[2] where a step entry point takes
+ * grad_scale makes that step unscale AND clip; no optimiser kernel knows about clipping.
+ *
+ * bvc_op_scale_by_dev: x[i] *= *coef (device scalar) for the immediate form; nothing is written when *coef == 1. */
+#define BVC_GRAD_NORM_ITEM_CAP 16384
+typedef struct bvc_norm_item {
+    int64_t start;      /* first element, relative to the range */
+    int32_t length;     /* 1 .. BVC_GRAD_NORM_ITEM_CAP */
+    int32_t segment;
+} bvc_norm_item;
+int bvc_op_grad_norm_item_cap(void);
+int bvc_op_grad_norm_chain(void);
+int bvc_grad_norm_items_host(const int64_t* seg_start, const int32_t* seg_group, int nseg, bvc_norm_item* items, int64_t items_cap,
+                             int64_t* seg_first_item, int64_t* nitems);
+int bvc_op_grad_sqnorm_items(const float* x, const bvc_norm_item* items, int64_t nitems, const int64_t* seg_first_item, int nseg,
+                             double* item_partial, float* seg_sq, float* total_sq, int as_norm, float* found_inf, void* stream);
+int bvc_op_clip_finalize(const float* sq, int nranges, float max_norm, const float* grad_scale, float* out3, void* stream);
+int bvc_op_scale_by_dev(float* x, int64_t n, const float* coef, void* stream);
 /* boolean mask -> ascending visible / masked token lists (the order x[~mask] / x[mask] produce, HF:121,578-579) */
 int bvc_op_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, void* stream);
 /* the same with a decode mask: the visible list and the ascending list of the ndec decoded tokens per clip; *status |= 1 when a clip's

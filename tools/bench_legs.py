@@ -111,16 +111,20 @@ def jepa_leg(bvc, dev, model="vit_large", batch=16, nctx=100, npred=25, warmup=6
             "tflops": round(gf * B / dt / 1e3, 1), "frac_of_mfma_peak": round(gf * B / dt / 1e3 / 2500.0, 4), "final_loss": round(loss, 5)}
 
 
-def videomae_leg(bvc, dev, arch="base", batch=16, warmup=5, steps=10, mask_ratio=0.9, decode_ratio=None):
+def videomae_leg(bvc, dev, arch="base", batch=16, warmup=5, steps=10, mask_ratio=0.9, decode_ratio=None, clip_grad=None, clip_grad_torch=False):
     """VideoMAE pre-training step of one VIDEOMAE_ARCHS size: synthetic 16 x 224^2 clips, tube masking at mask_ratio, bf16 autocast,
     backward, fused SGD-Nesterov with GradScaler - the headline's step at another model size.  decode_ratio: the decoder reconstructs
-    that share of every frame's masked patches (bool_decode_pos from DecoderSubsetGenerator); None = all of them, no decode mask."""
+    that share of every frame's masked patches (bool_decode_pos from DecoderSubsetGenerator); None = all of them, no decode mask.
+    clip_grad: clip the gradients by their global norm - inside the fused step (max_grad_norm=), or, with clip_grad_torch, the route
+    without it: scaler.unscale_ + torch.nn.utils.clip_grad_norm_ before the step."""
     torch.manual_seed(0)
     cfg = bvc.videomae_config(arch)
     model = bvc.VideoMAEForPreTraining(cfg).to(dev).train()
     model._ensure_flat(dev)
     # bench.py's optimiser and scaler: the fused SGD-Nesterov over the flat parameters, bvc.amp.GradScaler
-    opt = bvc.optim.SGD(model.parameters(), lr=0.1, momentum=0.9, nesterov=True, weight_decay=0.0)
+    opt = bvc.optim.SGD(model.parameters(), lr=0.1, momentum=0.9, nesterov=True, weight_decay=0.0,
+                        max_grad_norm=None if clip_grad_torch else clip_grad)
+    torch_clip = clip_grad is not None and clip_grad_torch
     scaler = bvc.amp.GradScaler("cuda")
     B, T, g = batch, cfg.num_frames // cfg.tubelet_size, cfg.image_size // cfg.patch_size
     gen = torch.Generator().manual_seed(1234)
@@ -138,6 +142,9 @@ def videomae_leg(bvc, dev, arch="base", batch=16, warmup=5, steps=10, mask_ratio
         with torch.autocast("cuda", dtype=torch.bfloat16):
             loss = model(clips, bool_masked_pos=mask, **kw).loss
         scaler.scale(loss).backward()
+        if torch_clip:
+            scaler.unscale_(opt)
+            torch.nn.utils.clip_grad_norm_(model.parameters(), clip_grad)
         scaler.step(opt)
         scaler.update()
         return loss

@@ -3,11 +3,14 @@ on synthetic 16 x 224^2 clips, every one of the 1568 tokens through the encoder.
 
     python tools/bench_videomae_cls.py --arch {small,base,large,huge} --batch B[,B2,...] [--steps K --warmup W]
                                        [--hidden-dropout P] [--drop-path R] [--layer-decay D]
+                                       [--grad-scaler] [--clip-grad C [--clip-grad-torch]]
 
 --hidden-dropout / --drop-path switch the gate on the residual branches on (config.hidden_dropout_prob / config.drop_path_rate);
 left at 0 the step is the ungated one, kernel for kernel.  --layer-decay D builds the optimiser from
 bvc.optim.layer_decay_param_groups (2 (layers + 2) parameter groups, layer-wise learning-rate decay D); without it the optimiser
-has one group.  Several batch sizes give one line each.  `optimizer_launches_per_step` counts the kernels of one optimiser step
+has one group.  --clip-grad C clips the gradients by their global norm inside the fused step (bvc.optim.AdamW(max_grad_norm=C)); with
+--clip-grad-torch it runs the route without it for the A/B: torch.nn.utils.clip_grad_norm_ before the step, after scaler.unscale_
+where --grad-scaler puts the step under bvc.amp.GradScaler (scaled loss, inf check, scaler.step / update).  Several batch sizes give one line each.  `optimizer_launches_per_step` counts the kernels of one optimiser step
 from the library calls it makes (a per-run Adam update is two: prepare + step; a by-value segment call two; a table call one plus
 one writer per 64 groups).
 
@@ -38,7 +41,8 @@ def gflop_per_clip(cfg):
     return (3 * cfg.num_hidden_layers * layer + 2 * pe) / 1e9, pe / 1e9, layer / 1e9
 
 
-OPT_ENTRY_POINTS = ("bvc_op_adam_prepare", "bvc_op_adam_step", "bvc_op_adam_step_segments", "bvc_op_adam_step_table")
+OPT_ENTRY_POINTS = ("bvc_op_adam_prepare", "bvc_op_adam_step", "bvc_op_adam_step_segments", "bvc_op_adam_step_table",
+                    "bvc_op_grad_sqnorm_items", "bvc_op_clip_finalize")
 
 
 def optimizer_launches(bvc, opt):
@@ -57,7 +61,8 @@ def optimizer_launches(bvc, opt):
         for k, fn in saved.items():
             setattr(lib, k, fn)
     writers = (len(opt.param_groups) + 63) // 64
-    per_call = {"bvc_op_adam_prepare": 1, "bvc_op_adam_step": 1, "bvc_op_adam_step_segments": 2, "bvc_op_adam_step_table": 1 + writers}
+    per_call = {"bvc_op_adam_prepare": 1, "bvc_op_adam_step": 1, "bvc_op_adam_step_segments": 2, "bvc_op_adam_step_table": 1 + writers,
+                "bvc_op_grad_sqnorm_items": 2, "bvc_op_clip_finalize": 1}
     return sum(n * per_call[k] for k, n in calls.items()), calls
 
 
@@ -71,6 +76,9 @@ def main():
     ap.add_argument("--hidden-dropout", type=float, default=0.0)
     ap.add_argument("--drop-path", type=float, default=0.0)
     ap.add_argument("--layer-decay", type=float, default=None, help="layer-wise learning-rate decay: the optimiser gets 2 (layers + 2) groups")
+    ap.add_argument("--grad-scaler", action="store_true", help="run the step under bvc.amp.GradScaler")
+    ap.add_argument("--clip-grad", type=float, default=None, help="clip the gradients by their global norm at this value")
+    ap.add_argument("--clip-grad-torch", action="store_true", help="with --clip-grad: torch.nn.utils.clip_grad_norm_ (after scaler.unscale_) instead of max_grad_norm=")
     args = ap.parse_args()
     ge.build()
     bvc = ge.load_package()
@@ -89,10 +97,13 @@ def run(bvc, args, B):
     cfg = bvc.videomae_config(args.arch, num_labels=args.num_labels, **drop)
     free0 = torch.cuda.mem_get_info(dev)[0]
     m = bvc.VideoMAEForVideoClassification(cfg).to(dev).train()
+    torch_clip = args.clip_grad is not None and args.clip_grad_torch
+    clip = {} if args.clip_grad is None or torch_clip else {"max_grad_norm": args.clip_grad}
     if args.layer_decay is None:
-        opt = bvc.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.05)
+        opt = bvc.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.05, **clip)
     else:
-        opt = bvc.optim.AdamW(bvc.optim.layer_decay_param_groups(m, 1e-4, 0.05, args.layer_decay), lr=1e-4)
+        opt = bvc.optim.AdamW(bvc.optim.layer_decay_param_groups(m, 1e-4, 0.05, args.layer_decay), lr=1e-4, **clip)
+    scaler = bvc.amp.GradScaler("cuda") if args.grad_scaler else None
     g = torch.Generator().manual_seed(1)
     clips = torch.randint(0, 256, (B, cfg.num_frames, 3, cfg.image_size, cfg.image_size), generator=g, dtype=torch.uint8).to(dev)
     labels = torch.randint(0, args.num_labels, (B,), generator=g).to(dev)
@@ -100,8 +111,18 @@ def run(bvc, args, B):
     def step():
         opt.zero_grad()
         out = m(pixel_values=clips, labels=labels)
-        out.loss.backward()
-        opt.step()
+        if scaler is None:
+            out.loss.backward()
+            if torch_clip:
+                torch.nn.utils.clip_grad_norm_(m.parameters(), args.clip_grad)
+            opt.step()
+            return out.loss
+        scaler.scale(out.loss).backward()
+        if torch_clip:
+            scaler.unscale_(opt)
+            torch.nn.utils.clip_grad_norm_(m.parameters(), args.clip_grad)
+        scaler.step(opt)
+        scaler.update()
         return out.loss
 
     for _ in range(args.warmup):
@@ -119,6 +140,7 @@ def run(bvc, args, B):
     torch.cuda.synchronize()
     print(json.dumps({"metric": f"VideoMAE-{args.arch} fine-tuning step (forward + backward + AdamW), all tokens, bf16 operands",
                       "arch": args.arch, "batch": B, "hidden_dropout": args.hidden_dropout, "drop_path": args.drop_path, "layer_decay": args.layer_decay,
+                      "grad_scaler": bool(args.grad_scaler), "clip_grad": args.clip_grad, "clip_route": None if args.clip_grad is None else "torch" if torch_clip else "fused",
                       "optimizer_groups": len(opt.param_groups), "optimizer_launches_per_step": launches, "optimizer_calls": calls, "ms_per_step": round(1e3 * dt, 3), "clips_per_s": round(B / dt, 1),
                       "gflop_per_clip": round(gf, 2), "gflop_patch_embed_fwd": round(pe, 3), "gflop_layer_fwd": round(layer, 3),
                       "tflops": round(tflops, 1), "frac_peak": round(tflops / PEAK_TFLOPS, 4), "device_mem_gb": round(used / 1e9, 2),

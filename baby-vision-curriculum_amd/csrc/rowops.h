@@ -56,6 +56,13 @@ int launch_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, in
 int launch_dual_mask_index(const uint8_t* mask, const uint8_t* decode, int B, int L, int nvis, int ndec, int* vis_idx, int* dec_idx,
                            int* status, hipStream_t s);
 int launch_gather_patches(PixelSrc clip, const int* vis_idx, bf16_t* A, int B, int nvis, PatchGeom pg, hipStream_t s);
+// the same with clip b composed with clip mix[b].partner on the way (Mixup / CutMix, bvc_clip_mix in include/bvc.h); mix is a device
+// table of B entries; entries out of range are clamped and raise bit 0 of *status (status may be null: clamped silently)
+typedef bvc_clip_mix ClipMix;
+int launch_gather_patches_mix(PixelSrc clip, const int* idx, bf16_t* A, int B, int n, PatchGeom pg, const ClipMix* mix, hipStream_t s,
+                              int* status = nullptr);
+// x[0 .. count) = NaN when bit 0 of *status is set (the device-side report of a failed input check; no host sync)
+int launch_poison_on_status(float* x, size_t count, const int* status, hipStream_t s);
 // dec_idx [B][ndec]: the tokens the decoder reconstructs (every masked token, or the decoded subset), ascending per clip;
 // Ld = nvis + ndec: the decoder's rows per clip
 int launch_labels(PixelSrc clip, const int* dec_idx, float* labels, int B, int ndec, PatchGeom pg, int norm_pix, hipStream_t s);

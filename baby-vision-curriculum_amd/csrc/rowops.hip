@@ -579,6 +579,73 @@ __global__ void gather_patches_kernel(const PixelSrc clip, const int* __restrict
         uint4{pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(d[0], d[1]), pack2bf(d[2], d[3])};
 }
 
+// ============================================================================ tube-patch gather with Mixup / CutMix
+// The gather above with clip b composed, on its way into A, with a partner clip (ClipMix = bvc_clip_mix, one entry per clip): inside
+// the entry's box the partner's pixel, outside it lam * own + (1 - lam) * partner in f32 (the own pixel itself when lam == 1).  Both
+// come through load_pixels4, so they are normalised values for either source dtype, and the mixed clip is never written anywhere.
+// A thread's 8-pixel run lies in one image row.  A run the box covers whole reads the partner only, a run outside the box with
+// lam == 1 reads its own clip only - the second load is not issued where its value is unused, so a CutMix moves the bytes of the plain
+// gather; only a run a box edge cuts, or one that is blended, reads both.  A 64-lane wave covers one 16 x 16 patch over two frames,
+// so the branch is wave-uniform except on the patches a vertical box edge crosses.
+// WAVE_ROW: K / 8 is a multiple of 64 (every configuration of the reference: K = 1536), so a wave lies in one row of A and the row,
+// its clip, its token and the clip's table entry are wave-uniform: read once per wave through the scalar unit, decoded in SGPRs.
+// Entries are not trusted: a partner outside [0, B) and a box outside the image are clamped before any address is formed, and bit 0 of
+// *status (when given) is raised, as is done for a lam outside [0, 1].
+template <bool WAVE_ROW>
+__global__ void gather_patches_mix_kernel(const PixelSrc clip, const int* __restrict__ idx, bf16_t* __restrict__ A, int B, int n,
+                                          PatchGeom pg, const ClipMix* __restrict__ mix, int* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int K = pg.C * pg.ts * pg.ps * pg.ps;
+    const int k8 = K >> 3;
+    if (i >= (size_t)B * n * k8) return;
+    const int mv = (int)(i / k8);
+    const int m = WAVE_ROW ? __builtin_amdgcn_readfirstlane(mv) : mv;
+    const int k = (int)(i - (size_t)m * k8) * 8;
+    const int dx = k % pg.ps, dy = (k / pg.ps) % pg.ps, dt = (k / (pg.ps * pg.ps)) % pg.ts, c = k / (pg.ps * pg.ps * pg.ts);
+    const int b = m / n, tok = idx[m];
+    const int wp = pg.W / pg.ps, hp = pg.H / pg.ps;
+    const int tp = tok / (hp * wp), yp = (tok / wp) % hp, xp = tok % wp;
+    const int y = yp * pg.ps + dy, x = xp * pg.ps + dx;
+    const ClipMix e = mix[b];
+    const int partner = min(max(e.partner, 0), B - 1);
+    const int y0 = min(max(e.y0, 0), pg.H), y1 = min(max(e.y1, 0), pg.H), x0 = min(max(e.x0, 0), pg.W), x1 = min(max(e.x1, 0), pg.W);
+    const float lam = e.lam;
+    if (status && k == 0 && m % n == 0 &&
+        (partner != e.partner || y0 != e.y0 || y1 != e.y1 || x0 != e.x0 || x1 != e.x1 || !(lam >= 0.f && lam <= 1.f)))
+        atomicOr(status, 1);
+    const size_t in_clip = ((((size_t)(tp * pg.ts + dt)) * pg.C + c) * pg.H + y) * pg.W + x;
+    const size_t per_clip = (size_t)pg.T * pg.C * pg.H * pg.W;
+    const size_t own = (size_t)b * per_clip + in_clip, oth = (size_t)partner * per_clip + in_clip;
+    // pixels of the run inside the box: [lo, hi) in run coordinates
+    const bool row_in = y >= y0 && y < y1;
+    const int lo = row_in ? max(x0 - x, 0) : 8, hi = row_in ? min(x1 - x, 8) : 0;
+    const bool all_in = lo == 0 && hi == 8, none_in = lo >= hi;
+    // every lane reads one source: the partner where the box covers the run, its own clip otherwise; only a run that is cut or blended
+    // goes on to read the partner as well
+    const size_t first = all_in ? oth : own;
+    f32x4 a = load_pixels4(clip, first, c);
+    f32x4 d = load_pixels4(clip, first + 4, c);
+    if (!(all_in || (none_in && lam == 1.0f))) {
+        const f32x4 a1 = load_pixels4(clip, oth, c), d1 = load_pixels4(clip, oth + 4, c);
+        const float rem = 1.0f - lam;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ma = lam == 1.0f ? a[j] : lam * a[j] + rem * a1[j];
+            const float md = lam == 1.0f ? d[j] : lam * d[j] + rem * d1[j];
+            a[j] = (j >= lo && j < hi) ? a1[j] : ma;
+            d[j] = (j + 4 >= lo && j + 4 < hi) ? d1[j] : md;
+        }
+    }
+    *reinterpret_cast<uint4*>(A + (size_t)m * K + k) =
+        uint4{pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(d[0], d[1]), pack2bf(d[2], d[3])};
+}
+
+// x[i] = NaN for every i when bit 0 of *status is set: how a call whose device-side input check failed reports it without a host sync
+__global__ void poison_on_status_kernel(float* __restrict__ x, size_t count, const int* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count && (*status & 1)) x[i] = __builtin_nanf("");
+}
+
 // ============================================================================ pixel targets (HF:588-661)
 // one workgroup per masked token: un-normalise, per-channel mean / unbiased variance over ts*ps*ps
 // values, labels[(dt,dy,dx,c)] = (f - mean) / (sqrt(var) + 1e-6)
@@ -1857,6 +1924,26 @@ int launch_gather_patches(PixelSrc clip, const int* vis_idx, bf16_t* A, int B, i
     BVC_REQUIRE(pg.ps % 8 == 0 && pg.W % 4 == 0, "gather_patches: patch size must be a multiple of 8");
     const size_t items = (size_t)B * nvis * (pg.C * pg.ts * pg.ps * pg.ps / 8);
     hipLaunchKernelGGL(gather_patches_kernel, dim3(blocks_for(items)), dim3(256), 0, s, clip, vis_idx, A, B, nvis, pg);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_gather_patches_mix(PixelSrc clip, const int* idx, bf16_t* A, int B, int n, PatchGeom pg, const ClipMix* mix, hipStream_t s,
+                              int* status) {
+    BVC_REQUIRE(clip.ptr && idx && A && mix, "gather_patches_mix: null argument");
+    BVC_REQUIRE(B >= 1 && n >= 1, "gather_patches_mix: B=%d clips of n=%d tokens", B, n);
+    BVC_REQUIRE(pg.ps % 8 == 0 && pg.W % 4 == 0, "gather_patches_mix: patch size must be a multiple of 8");
+    const size_t items = (size_t)B * n * (pg.C * pg.ts * pg.ps * pg.ps / 8);
+    if ((pg.C * pg.ts * pg.ps * pg.ps / 8) % 64 == 0)
+        hipLaunchKernelGGL(gather_patches_mix_kernel<true>, dim3(blocks_for(items)), dim3(256), 0, s, clip, idx, A, B, n, pg, mix, status);
+    else
+        hipLaunchKernelGGL(gather_patches_mix_kernel<false>, dim3(blocks_for(items)), dim3(256), 0, s, clip, idx, A, B, n, pg, mix, status);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_poison_on_status(float* x, size_t count, const int* status, hipStream_t s) {
+    hipLaunchKernelGGL(poison_on_status_kernel, dim3(blocks_for(count)), dim3(256), 0, s, x, count, status);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

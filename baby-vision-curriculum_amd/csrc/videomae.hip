@@ -154,6 +154,43 @@ int pixel_src(const void* pixels, const bvc_pixel_format* fmt, int channels, Pix
 }
 }  // namespace
 
+// ------------------------------------------------------------------ Mixup / CutMix of a classification context (bvc_*_set_mix)
+namespace {
+struct MixState {
+    ClipMix* table = nullptr;          // the context's copy, max_batch entries
+    int* status = nullptr;             // bit 0: an entry of the last mixed forward was out of range
+    const bvc_clip_mix* armed = nullptr;
+    int samples = 0;
+};
+
+int alloc_mix(Arena& a, MixState& m, int max_batch) {
+    TRY(a.alloc(&m.table, (size_t)max_batch));
+    return a.alloc(&m.status, 4);
+}
+
+int set_mix(MixState& m, const bvc_clip_mix* mix, int samples, int max_batch, const char* who) {
+    m.armed = nullptr;
+    if (!mix) return BVC_OK;
+    BVC_REQUIRE(samples >= 1 && samples <= max_batch, "%s: %d samples outside [1, %d]", who, samples, max_batch);
+    m.armed = mix;
+    m.samples = samples;
+    return BVC_OK;
+}
+
+// the gather of a forward: the plain kernel, or - consuming an armed table - the mix kernel on the context's copy of it
+int gather_for_forward(MixState& m, bool* mixed, PixelSrc pixels, const int* idx, bf16_t* A, int B, int N, PatchGeom pg, const char* who,
+                       hipStream_t st) {
+    const bvc_clip_mix* src = m.armed;
+    m.armed = nullptr;
+    *mixed = src != nullptr;
+    if (!src) return launch_gather_patches(pixels, idx, A, B, N, pg, st);
+    BVC_REQUIRE(m.samples == B, "%s: the mix was set for %d samples, the call has %d", who, m.samples, B);
+    BVC_CHECK_HIP(hipMemcpyAsync(m.table, src, (size_t)B * sizeof(ClipMix), hipMemcpyDeviceToDevice, st));
+    BVC_CHECK_HIP(hipMemsetAsync(m.status, 0, 4, st));
+    return launch_gather_patches_mix(pixels, idx, A, B, N, pg, m.table, st, m.status);
+}
+}  // namespace
+
 // ============================================================================ C ABI
 extern "C" {
 
@@ -548,6 +585,7 @@ struct bvc_encoder_ctx {
     int* idx_all;
     int pooled_batch = 0;    // clips whose pre-norm pooled rows and fc_norm statistics the last encode left (0: none)
     DropState drop;          // bvc_videomae_encoder_set_drop: the forward gate of a train-mode module on the forward-only path
+    MixState mix;            // bvc_videomae_encoder_set_mix
 };
 
 void bvc_videomae_encoder_destroy(bvc_encoder_ctx* c) {
@@ -583,6 +621,7 @@ int bvc_videomae_encoder_create(const bvc_videomae_config* cfg, int max_batch, b
     A(c->arena.alloc(&c->Ape, M * c->P));
     A(alloc_stack(c->arena, c->st, D, I, H, 1, cfg->layer_norm_eps, M, (size_t)max_batch * H * c->L));
     A(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
+    A(alloc_mix(c->arena, c->mix, max_batch));
     A(c->arena.alloc(&c->xa, M * D));
     A(c->arena.alloc(&c->xb, M * D));
     A(c->arena.alloc(&c->pooled, (size_t)max_batch * D));
@@ -631,7 +670,8 @@ int bvc_videomae_encode_ex(bvc_encoder_ctx* c, const void* pixels_any, const bvc
     TRY(take_drop(c->drop, B, N, "encode"));
     const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
     TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
-    TRY(launch_gather_patches(pixels, c->idx_all, c->Ape, B, N, pg, st));
+    bool mixed = false;
+    TRY(gather_for_forward(c->mix, &mixed, pixels, c->idx_all, c->Ape, B, N, pg, "encode", st));
     const size_t slot = (size_t)M * D;                         // one hidden state
     float* x = hs ? hs : c->xa;                                // given hidden_states, slot 0 is the embedding output
     float* y = c->xb;
@@ -652,6 +692,7 @@ int bvc_videomae_encode_ex(bvc_encoder_ctx* c, const void* pixels_any, const bvc
         if (dst == y) std::swap(x, y); else x = dst;
     }
     if (hs && tokens) BVC_CHECK_HIP(hipMemcpyAsync(tokens, x, slot * 4, hipMemcpyDeviceToDevice, st));
+    if (mixed && tokens) TRY(launch_poison_on_status(tokens, slot, c->mix.status, st));
     c->drop.active = false;      // forward only: nothing follows that would need the gate
     c->pooled_batch = 0;
     if (pooled) {
@@ -660,6 +701,7 @@ int bvc_videomae_encode_ex(bvc_encoder_ctx* c, const void* pixels_any, const bvc
         if (fc_norm_w)
             TRY(launch_ln_fwd(mp, identity_rows(), fc_norm_w, fc_norm_b, nullptr, c->mean, c->rstd, B, D, fc_norm_eps, st, pooled));
         if (fc_norm_w) c->pooled_batch = B;
+        if (mixed) TRY(launch_poison_on_status(pooled, (size_t)B * D, c->mix.status, st));
     }
     return BVC_OK;
 }
@@ -667,6 +709,12 @@ int bvc_videomae_encode_ex(bvc_encoder_ctx* c, const void* pixels_any, const bvc
 int bvc_videomae_encoder_set_drop(bvc_encoder_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
     BVC_REQUIRE(c, "encoder_set_drop: null context");
     return set_drop(c->drop, drop, samples, "encoder_set_drop", (hipStream_t)stream);
+}
+
+int bvc_videomae_encoder_set_mix(bvc_encoder_ctx* c, const bvc_clip_mix* mix_dev, int samples, void* stream) {
+    (void)stream;      // the table is copied by the forward that consumes it, on that forward's stream
+    BVC_REQUIRE(c, "encoder_set_mix: null context");
+    return set_mix(c->mix, mix_dev, samples, c->max_batch, "encoder_set_mix");
 }
 
 int bvc_videomae_encoder_fc_norm_backward(bvc_encoder_ctx* c, const float* dpooled, const float* fc_norm_w, float* dfc_norm_w,
@@ -699,6 +747,7 @@ struct bvc_cls_ctx {
     bool have_forward = false;
     bool shadow_valid = false;   // as bvc_ctx::shadow_valid
     DropState drop;              // bvc_videomae_cls_set_drop
+    MixState mix;                // bvc_videomae_cls_set_mix
 };
 
 void bvc_videomae_cls_destroy(bvc_cls_ctx* c) {
@@ -743,6 +792,7 @@ int bvc_videomae_cls_create(const bvc_videomae_config* cfg, int max_batch, bvc_c
     A(c->arena.alloc(&c->Ape, M * P));
     A(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, M, (size_t)max_batch * H * L));
     A(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
+    A(alloc_mix(c->arena, c->mix, max_batch));
     A(c->arena.alloc(&c->pooled_pre, (size_t)max_batch * D));
     A(c->arena.alloc(&c->mean, (size_t)max_batch));
     A(c->arena.alloc(&c->rstd, (size_t)max_batch));
@@ -779,7 +829,8 @@ int bvc_videomae_cls_forward_px(bvc_cls_ctx* c, const void* pixels_any, const bv
     const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
     if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
     c->shadow_valid = false;
-    TRY(launch_gather_patches(pixels, c->idx_all, c->Ape, B, N, pg, st));
+    bool mixed = false;
+    TRY(gather_for_forward(c->mix, &mixed, pixels, c->idx_all, c->Ape, B, N, pg, "cls_forward", st));
     {
         GemmProblem p = gemm(c->Ape, (size_t)M * P, P, c->wbf + L.pe_w, (size_t)D * P, P, M, D, P, EPI_POS, c->enc.act[0].x_in, D);
         p.bias = params + L.pe_b; p.rowtok = c->idx_all; p.pos = c->pos_enc;
@@ -792,6 +843,10 @@ int bvc_videomae_cls_forward_px(bvc_cls_ctx* c, const void* pixels_any, const bv
     TRY(launch_ln_fwd(c->pooled_pre, identity_rows(), fc_norm_w, fc_norm_b, nullptr, c->mean, c->rstd, B, D, fc_norm_eps, st, pooled));
     BVC_CHECK_HIP(hipMemcpyAsync(c->fcw, fc_norm_w, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
     if (tokens) BVC_CHECK_HIP(hipMemcpyAsync(tokens, c->enc.x_out, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+    if (mixed) {
+        TRY(launch_poison_on_status(pooled, (size_t)B * D, c->mix.status, st));
+        if (tokens) TRY(launch_poison_on_status(tokens, (size_t)M * D, c->mix.status, st));
+    }
     c->have_forward = true;
     return BVC_OK;
 }
@@ -846,6 +901,12 @@ int bvc_videomae_cls_introspect(bvc_cls_ctx* c, const bvc_introspect* out, void*
 int bvc_videomae_cls_set_drop(bvc_cls_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
     BVC_REQUIRE(c, "cls_set_drop: null context");
     return set_drop(c->drop, drop, samples, "cls_set_drop", (hipStream_t)stream);
+}
+
+int bvc_videomae_cls_set_mix(bvc_cls_ctx* c, const bvc_clip_mix* mix_dev, int samples, void* stream) {
+    (void)stream;      // the table is copied by the forward that consumes it, on that forward's stream
+    BVC_REQUIRE(c, "cls_set_mix: null context");
+    return set_mix(c->mix, mix_dev, samples, c->max_batch, "cls_set_mix");
 }
 
 int bvc_videomae_cls_shadow(bvc_cls_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
@@ -1107,6 +1168,15 @@ int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A, int B,
                           int ps, void* stream) {
     BVC_REQUIRE(clip && vis_idx && A, "op_gather_patches: null argument");
     return launch_gather_patches(pixels_f32(clip), vis_idx, (bf16_t*)A, B, nvis, PatchGeom{T, C, H, W, ts, ps}, (hipStream_t)stream);
+}
+int bvc_op_gather_patches_mix(const void* clip, const bvc_pixel_format* fmt, const int* idx, void* A, const bvc_clip_mix* mix, int B, int n,
+                              int T, int C, int H, int W, int ts, int ps, void* stream) {
+    BVC_REQUIRE(clip && idx && A && mix, "op_gather_patches_mix: null argument");
+    BVC_REQUIRE(T >= 1 && C >= 1 && H >= 1 && W >= 1 && ts >= 1 && ps >= 1 && T % ts == 0 && H % ps == 0 && W % ps == 0,
+                "op_gather_patches_mix: bad geometry");
+    PixelSrc px;
+    TRY(pixel_src(clip, fmt, C, &px));
+    return launch_gather_patches_mix(px, idx, (bf16_t*)A, B, n, PatchGeom{T, C, H, W, ts, ps}, mix, (hipStream_t)stream);
 }
 int bvc_op_pixel_labels(const float* clip, const int* msk_idx, float* labels, int B, int nmask, int T, int C, int H, int W, int ts,
                         int ps, int norm_pix, void* stream) {

@@ -352,10 +352,19 @@ def infer_problem_type(num_labels, labels):
     return "multi_label_classification"
 
 
+def soft_target_cross_entropy(logits, target):
+    """mean over b of -sum_k target[b, k] * log_softmax(logits)[b, k]: cross-entropy against soft targets [B, K] (rows summing to 1),
+    as Mixup / CutMix with label smoothing produce them."""
+    if target.shape != logits.shape:
+        raise ValueError(f"soft targets {tuple(target.shape)} must have the logits' shape {tuple(logits.shape)}")
+    return torch.sum(-target.to(device=logits.device, dtype=logits.dtype) * nn.functional.log_softmax(logits, dim=-1), dim=-1).mean()
+
+
 def classification_loss(config, logits, labels):
     """transformers 5.15.0 VideoMAEForVideoClassification.forward -> loss_utils.ForSequenceClassificationLoss: infers
     config.problem_type when it is None and writes it back, then MSE (regression) / cross-entropy with ignore_index -100 /
-    BCEWithLogits on the [B, num_labels] logits."""
+    BCEWithLogits on the [B, num_labels] logits.  One extension, never inferred: ``config.problem_type ==
+    "soft_label_classification"`` is ``soft_target_cross_entropy`` on [B, num_labels] float labels (the targets ``bvc.Mixup`` makes)."""
     num_labels = int(getattr(config, "num_labels", 2))
     if getattr(config, "problem_type", None) is None:
         config.problem_type = infer_problem_type(num_labels, labels)
@@ -368,6 +377,8 @@ def classification_loss(config, logits, labels):
         return nn.functional.cross_entropy(logits.view(-1, num_labels), labels.view(-1), ignore_index=-100)
     if config.problem_type == "multi_label_classification":
         return nn.functional.binary_cross_entropy_with_logits(logits, labels)
+    if config.problem_type == "soft_label_classification":
+        return soft_target_cross_entropy(logits, labels)
     raise ValueError(f"problem_type {config.problem_type!r} unknown")
 
 
@@ -437,9 +448,9 @@ class _ClsTrain(torch.autograd.Function):
     buffer (views as .grad) and returns fc_norm's gradients to autograd."""
 
     @staticmethod
-    def forward(ctx, anchor, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False):
+    def forward(ctx, anchor, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False, mix=None):
         ctx.model = model
-        pooled, tokens, hs, att = model._run_train_forward(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions)
+        pooled, tokens, hs, att = model._run_train_forward(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions, mix)
         ctx.stamp = model._stamp_forward()
         _mark_detached(ctx, tokens, hs, att)
         return pooled, tokens, hs, att
@@ -448,16 +459,16 @@ class _ClsTrain(torch.autograd.Function):
     def backward(ctx, dpooled, _dtokens, _dhs, _datt):
         ctx.model._check_generation(ctx.stamp)
         dw, db = ctx.model._run_train_backward(dpooled)
-        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None
+        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None, None
 
 
 class _FcNormProbe(torch.autograd.Function):
     """The inference context's encode (today's call, the same bits) with fc_norm under autograd: the linear-probe case."""
 
     @staticmethod
-    def forward(ctx, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False):
+    def forward(ctx, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False, mix=None):
         ctx.model = model
-        pooled, tokens, hs, att = model._run_encode(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions)
+        pooled, tokens, hs, att = model._run_encode(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions, mix)
         ctx.stamp = model._stamp_forward()
         ctx.save_for_backward(fc_w)
         _mark_detached(ctx, tokens, hs, att)
@@ -473,7 +484,7 @@ class _FcNormProbe(torch.autograd.Function):
         dw, db = torch.empty_like(w), torch.empty_like(w)
         _lib.check(_lib.lib().bvc_videomae_encoder_fc_norm_backward(m._ctx, g.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                                                     _lib.current_stream_ptr()), "bvc_videomae_encoder_fc_norm_backward")
-        return dw if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None, None, None
+        return dw if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None, None, None, None
 
 
 class VideoMAEForVideoClassification(FlatParamModule):
@@ -600,6 +611,11 @@ class VideoMAEForVideoClassification(FlatParamModule):
         if self.training and self._gate.enabled:
             self._gate.arm(set_drop, h, dev, B, self.config.seq_length)
 
+    def _arm_mix(self, set_mix, h, mix, B):
+        """Hand a ClipMix to the context that runs next (``set_mix`` = its bvc_*_set_mix): that forward gathers through it and disarms."""
+        if mix is not None:
+            _lib.check(set_mix(h, mix.table.data_ptr(), int(B), _lib.current_stream_ptr()), "set_mix")
+
     def _encoder_trainable(self):
         return any(self._param(n).requires_grad for n in self._names)
 
@@ -607,7 +623,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
     def _fc_norm_args(self, fc_w, fc_b, dev):
         return fc_w.detach().to(device=dev, dtype=torch.float32).contiguous(), fc_b.detach().to(device=dev, dtype=torch.float32).contiguous()
 
-    def _run_encode(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False):
+    def _run_encode(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False, mix=None):
         cfg = self.config
         B, dev = pixels.shape[0], pixels.device
         fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
@@ -619,6 +635,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
         if want_tokens:     # with hidden states the residual stream already ends in the caller's array: its last slot
             tokens = hs[-1] if hs is not None else torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev)
         self._arm_gate(_lib.lib().bvc_videomae_encoder_set_drop, h, B, dev)     # train mode on the forward-only path: the same gate
+        self._arm_mix(_lib.lib().bvc_videomae_encoder_set_mix, h, mix, B)
         args = (h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
                 float(self.fc_norm.eps), tokens.data_ptr() if tokens is not None and hs is None else None, pooled.data_ptr())
         out = _lib.introspect(hs, att)
@@ -628,7 +645,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
             _lib.check(_lib.lib().bvc_videomae_encode_ex(*args, ctypes.byref(out), _lib.current_stream_ptr()), "bvc_videomae_encode_ex")
         return pooled, tokens, hs, att
 
-    def _run_train_forward(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False):
+    def _run_train_forward(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False, mix=None):
         cfg = self.config
         B, dev = pixels.shape[0], pixels.device
         fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
@@ -639,6 +656,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
         tokens = torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev) if want_tokens else None
         self._shadow_vouch(h)
         self._arm_gate(_lib.lib().bvc_videomae_cls_set_drop, h, B, dev)
+        self._arm_mix(_lib.lib().bvc_videomae_cls_set_mix, h, mix, B)
         _lib.check(_lib.lib().bvc_videomae_cls_forward_px(
             h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
             float(self.fc_norm.eps), pooled.data_ptr(), tokens.data_ptr() if tokens is not None else None, _lib.current_stream_ptr()),
@@ -663,14 +681,21 @@ class VideoMAEForVideoClassification(FlatParamModule):
         return dw.to(self.fc_norm.weight.dtype), db.to(self.fc_norm.bias.dtype)
 
     def forward(self, pixel_values=None, labels=None, output_last_hidden_state=False, output_hidden_states=None, output_attentions=None,
-                **kwargs):
+                mix=None, **kwargs):
         """``output_hidden_states`` / ``output_attentions`` (None = ``config.output_hidden_states`` / ``config.output_attentions``, as in
         transformers): ``hidden_states`` is a tuple of L + 1 tensors (B, N, D) - the embedding output, then every layer's output -
         and ``attentions`` a tuple of L tensors (B, H, N, N) of softmax probabilities (row = query).  Each tuple is f32 views of one
         allocation; ``attentions`` takes ``attentions_nbytes(config, B)`` bytes and the call raises ValueError before allocating when
         that exceeds the free device memory.  Unlike transformers', both are detached (no gradient flows through them, as through
         ``last_hidden_state``).  They are those of the forward that ran: in train mode they include the drop-path / dropout gates.
-        The logits are the same bits with or without them."""
+        The logits are the same bits with or without them.
+
+        ``mix`` (a ``ClipMix`` from ``bvc.Mixup``, train mode only): the clips enter the patch embedding mixed with their partners
+        (Mixup / CutMix inside the patch gather, uint8 or f32 input; nothing is written back and ``pixel_values`` is untouched).
+        It serves this forward alone.  Pass the soft targets that came with it as ``labels`` under
+        ``config.problem_type = "soft_label_classification"``.  A table entry out of range makes the logits NaN."""
+        if mix is not None and not self.training:
+            raise ValueError("mix= in eval mode: evaluating on mixed clips is a mistake (call .train(), or pass mix=None)")
         if pixel_values is None or not pixel_values.is_cuda:
             raise _lib.BvcError("VideoMAEForVideoClassification runs on a GPU only (libbvc_hip.so has no CPU path)")
         cfg = self.config
@@ -680,6 +705,11 @@ class VideoMAEForVideoClassification(FlatParamModule):
         if C != cfg.num_channels or H != cfg.image_size or W != cfg.image_size or T != cfg.num_frames:
             raise ValueError(f"Input size ({T}x{C}x{H}*{W}) doesn't match model ({cfg.num_frames}x{cfg.num_channels}x{cfg.image_size}*{cfg.image_size}).")
         dev = pixel_values.device
+        if mix is not None:
+            if mix.batch_size != B:
+                raise ValueError(f"mix was built for a batch of {mix.batch_size} clips, pixel_values holds {B}")
+            if mix.table is None or mix.table.device != dev:
+                raise ValueError(f"mix has no device table on {dev}: build it with device=pixel_values.device")
         self._ensure_flat(dev)
         pixels = pixel_values.detach()
         pixels = (pixels if pixels.dtype == torch.uint8 else pixels.to(dtype=torch.float32)).contiguous()
@@ -688,17 +718,17 @@ class VideoMAEForVideoClassification(FlatParamModule):
         fc_w, fc_b = self.fc_norm.weight, self.fc_norm.bias
         if classification_path(self.training, grad, trainable) == "train":
             anchor = next(self._param(n) for n in self._names if self._param(n).requires_grad)
-            pooled, tokens, hs, att = _ClsTrain.apply(anchor, fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att)
+            pooled, tokens, hs, att = _ClsTrain.apply(anchor, fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att, mix)
         else:
             if grad and trainable and not self._warned_eval_grad:
                 self._warned_eval_grad = True
                 warnings.warn("VideoMAEForVideoClassification in eval mode: the encoder receives no gradient (call .train() to "
                               "fine-tune it); fc_norm and the classifier still do", stacklevel=2)
             if grad and (fc_w.requires_grad or fc_b.requires_grad):
-                pooled, tokens, hs, att = _FcNormProbe.apply(fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att)
+                pooled, tokens, hs, att = _FcNormProbe.apply(fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att, mix)
             else:
                 with torch.no_grad():
-                    pooled, tokens, hs, att = self._run_encode(pixels, fc_w, fc_b, output_last_hidden_state, want_hs, want_att)
+                    pooled, tokens, hs, att = self._run_encode(pixels, fc_w, fc_b, output_last_hidden_state, want_hs, want_att, mix)
                 self._stamp_forward()     # a pending backward of an earlier forward must not run on overwritten state
         logits = self.classifier(pooled)
         loss = classification_loss(cfg, logits, labels) if labels is not None else None

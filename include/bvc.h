@@ -271,6 +271,29 @@ typedef struct bvc_branch_drop {
 int bvc_videomae_cls_set_drop(bvc_cls_ctx* ctx, const bvc_branch_drop* drop, int samples, void* stream);
 /* forward only (a train-mode module under torch.no_grad(), a train-mode linear probe) */
 int bvc_videomae_encoder_set_drop(bvc_encoder_ctx* ctx, const bvc_branch_drop* drop, int samples, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Mixup / CutMix inside the patch gather.  One entry per clip of the call: clip b enters the patch-embedding product composed with
+ * clip `partner`, at pixel (t, c, y, x) of either source dtype (values as normalised by the pixel format)
+ *     inside the box, rows [y0, y1) x columns [x0, x1) of every frame:   the partner's pixel
+ *     outside it:                                                         lam * own + (1 - lam) * partner in f32 (own when lam == 1)
+ * and is then rounded to bf16 as the plain gather rounds.  Mixup = empty box, lam < 1; CutMix = a box, lam = 1; partner = b with
+ * lam = 1 and an empty box leaves the clip as it is.  The mixed clip is never written: a run of pixels the box covers is read from
+ * the partner alone, a run outside it with lam == 1 from the clip alone, so CutMix moves the bytes of the plain gather and Mixup reads
+ * the source twice.  The backward is unchanged (the patch-embedding weight gradient reads the gathered operand; pixels get none).
+ * The *_set_mix calls arm the NEXT forward of the context (cls_forward_px; encode_px / encode_ex): that forward copies the table
+ * (device memory, `samples` entries, alive until that forward has been enqueued) into the context on its stream, gathers through
+ * it and disarms; `samples` must equal its batch (BVC_ERR_INVALID otherwise).  mix_dev == NULL disarms.  With nothing armed a
+ * forward launches exactly what it launches without this interface.  An entry with a partner outside [0, samples), a box outside
+ * the image or a lam outside [0, 1] is clamped before any address is formed and makes that forward's pooled rows (and tokens) NaN:
+ * the flag is checked on the device, without a host sync. */
+typedef struct bvc_clip_mix {
+    int partner;
+    float lam;
+    int y0, y1, x0, x1;
+} bvc_clip_mix; /* 24 bytes */
+int bvc_videomae_cls_set_mix(bvc_cls_ctx* ctx, const bvc_clip_mix* mix_dev, int samples, void* stream);
+/* forward only (a train-mode linear probe, a train-mode module under torch.no_grad()) */
+int bvc_videomae_encoder_set_mix(bvc_encoder_ctx* ctx, const bvc_clip_mix* mix_dev, int samples, void* stream);
 /* keep bytes (1 = kept, 0 = dropped) of the M x N element mask of one branch, row-major, on the device and on the host */
 int bvc_op_dropout_mask(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_dev, void* stream);
 int bvc_dropout_mask_host(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_host);
@@ -585,6 +608,10 @@ int bvc_op_dual_mask_index(const uint8_t* mask, const uint8_t* decode_mask, int 
 /* tube patches of the visible tokens in Conv3d weight order (HF:157-177) */
 int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A_bf16, int B, int nvis, int T, int C, int H, int W,
                           int ts, int ps, void* stream);
+/* the same through a bvc_clip_mix table of B entries (device), from either pixel format (fmt NULL = f32); idx [B][n] tokens per clip.
+ * Out-of-range entries are clamped (no status word at this level). */
+int bvc_op_gather_patches_mix(const void* clip, const bvc_pixel_format* fmt, const int* idx, void* A_bf16, const bvc_clip_mix* mix,
+                              int B, int n, int T, int C, int H, int W, int ts, int ps, void* stream);
 /* per-patch-normalised pixel targets of the masked tokens (HF:588-661) */
 int bvc_op_pixel_labels(const float* clip, const int* msk_idx, float* labels, int B, int nmask, int T, int C, int H, int W,
                         int ts, int ps, int norm_pix, void* stream);

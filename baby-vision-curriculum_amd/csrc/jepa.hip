@@ -1,5 +1,6 @@
 // JEPA encoder / predictor on gfx950: contexts and forward / backward schedules (host code; kernels live in
-// gemm.hip / attention.hip / rowops.hip, the transformer layer schedule in stack.hip).
+// gemm.hip / attention.hip / rowops.hip, the transformer layer schedule in stack.hip, what the contexts share around it in
+// context.hip, the JEPA operator entry points in ops.hip).
 //
 // Follows pretraining/predictive/vision_transformer.py:
 //   VisionTransformer.forward          :378-402  patch embed (Conv3d) + pos_embed, apply_masks, blocks, norm
@@ -13,7 +14,7 @@
 #include <algorithm>
 #include <string.h>
 
-#include "stack.h"
+#include "context.h"
 
 using namespace bvc;
 
@@ -38,15 +39,10 @@ int check_vit(const bvc_vit_config& c) {
     return BVC_OK;
 }
 
-int vit_seq(const bvc_vit_config& c) {
-    const int g = c.image_size / c.patch_size;
-    return (c.num_frames / c.tubelet_size) * g * g;
-}
-
 VitLayout make_vit_layout(const bvc_vit_config& c) {
     VitLayout L;
     const int64_t D = c.embed_dim;
-    L.pos = L.add("pos_embed", {1, vit_seq(c), D});
+    L.pos = L.add("pos_embed", {1, seq_len(patch_geom(c)), D});
     L.pe_w = L.add("patch_embed.proj.weight", {D, c.num_channels, c.tubelet_size, c.patch_size, c.patch_size});
     L.pe_b = L.add("patch_embed.proj.bias", {D});
     for (int i = 0; i < c.depth; ++i) L.blocks.push_back(add_layer_params(L, "blocks." + std::to_string(i) + ".", D, c.mlp_hidden, false));
@@ -87,15 +83,6 @@ PredLayout make_pred_layout(const bvc_predictor_config& c) {
     return L;
 }
 
-int param_info(const ParamTable& L, int index, char* name, int name_cap, int64_t* offset, int64_t* numel, int* ndim, int64_t shape[5]) {
-    BVC_REQUIRE(index >= 0 && index < (int)L.entries.size(), "param_info: index %d out of range", index);
-    const ParamEntry& e = L.entries[index];
-    snprintf(name, name_cap, "%s", e.name.c_str());
-    *offset = e.offset; *numel = e.numel; *ndim = e.ndim;
-    for (int i = 0; i < 5; ++i) shape[i] = e.shape[i];
-    return BVC_OK;
-}
-
 }  // namespace
 
 struct bvc_vit_ctx {
@@ -104,14 +91,12 @@ struct bvc_vit_ctx {
     Arena arena;
     Work w;
     Stack st;
-    int max_batch, L, Kp;
+    int max_batch, L;
     int batch = 0, ntok = 0;
     bool have_forward = false;
-    bf16_t* wbf;
-    bool shadow_valid = false;   // set by bvc_vit_shadow for ONE forward: wbf already matches the parameters it will be given
-    int* idx_all;      // identity token list [max_batch * L]
+    Shadow shadow;     // bvc_vit_shadow
+    PatchFront front;  // with the identity token list [max_batch * L]
     const int* idx;    // token list of the current call
-    bf16_t* Ape;       // bf16 [B*N][Kp]
     float *meanf, *rstdf;
     bf16_t* dout_bf;   // bf16 [B*N][D]
     float* dres;
@@ -127,8 +112,7 @@ struct bvc_pred_ctx {
     int max_batch, max_sets, max_tokens;
     int B = 0, Nc = 0, Np = 0, nsets = 0;
     bool have_forward = false;
-    bf16_t* wbf;
-    bool shadow_valid = false;   // see bvc_predictor_shadow
+    Shadow shadow;     // bvc_predictor_shadow
     bf16_t* z_bf;      // bf16 [B*Nc][D]
     float* xe;         // f32 [B*Nc][Dp] embedded context tokens (+ pos)
     const int *idx_ctx, *idx_pred;
@@ -169,29 +153,24 @@ int bvc_vit_create(const bvc_vit_config* cfg, int max_batch, bvc_vit_ctx** out) 
     BVC_REQUIRE(cfg && out && max_batch >= 1, "vit_create: bad argument");
     TRY(check_vit(*cfg));
     bvc_vit_ctx* c = new bvc_vit_ctx();
+    Making guard{[&] { bvc_vit_destroy(c); }};
     c->cfg = *cfg;
     c->lay = make_vit_layout(*cfg);
     c->max_batch = max_batch;
-    c->L = vit_seq(*cfg);
-    c->Kp = cfg->num_channels * cfg->tubelet_size * cfg->patch_size * cfg->patch_size;
+    const PatchGeom pg = patch_geom(*cfg);
+    c->L = seq_len(pg);
     const size_t M = (size_t)max_batch * c->L;
     const int D = cfg->embed_dim, I = cfg->mlp_hidden, H = cfg->num_heads;
-    int rc = BVC_OK;
-    auto fail = [&](int r) { bvc_vit_destroy(c); return r; };
-#define A(expr) if ((rc = (expr)) != BVC_OK) return fail(rc)
-    A(c->arena.alloc(&c->wbf, (size_t)c->lay.total));
-    A(c->arena.alloc(&c->idx_all, M));
-    A(c->arena.alloc(&c->Ape, M * c->Kp));
-    A(alloc_stack(c->arena, c->st, D, I, H, cfg->depth, cfg->eps, M, (size_t)max_batch * H * c->L));
-    A(alloc_drop(c->arena, c->drop, cfg->depth, max_batch));
-    A(c->arena.alloc(&c->meanf, M));
-    A(c->arena.alloc(&c->rstdf, M));
-    A(c->arena.alloc(&c->dout_bf, M * D));
-    A(c->arena.alloc(&c->dres, M * D));
-    A(alloc_work(c->arena, c->w, M * D, M * I, (size_t)max_batch * H * c->L, ln_bwd_workspace_floats_upto((int)M, D)));
-    A(launch_iota_mod(c->idx_all, (int)M, c->L, nullptr));
-    if (hipStreamSynchronize(nullptr) != hipSuccess) { set_error("vit_create: init sync failed"); return fail(BVC_ERR_HIP); }
-#undef A
+    TRY(c->shadow.alloc(c->arena, c->lay.total));
+    TRY(c->front.alloc(c->arena, pg, M, true));
+    TRY(alloc_stack(c->arena, c->st, D, I, H, cfg->depth, cfg->eps, M, (size_t)max_batch * H * c->L));
+    TRY(alloc_drop(c->arena, c->drop, cfg->depth, max_batch));
+    TRY(c->arena.alloc(&c->meanf, M));
+    TRY(c->arena.alloc(&c->rstdf, M));
+    TRY(c->arena.alloc(&c->dout_bf, M * D));
+    TRY(c->arena.alloc(&c->dres, M * D));
+    TRY(alloc_work(c->arena, c->w, M * D, M * I, (size_t)max_batch * H * c->L, ln_bwd_workspace_floats_upto((int)M, D)));
+    guard.done = true;
     *out = c;
     return BVC_OK;
 }
@@ -207,43 +186,24 @@ int bvc_vit_forward(bvc_vit_ctx* c, const float* imgs, const int* idx, int batch
 int bvc_vit_forward_px(bvc_vit_ctx* c, const void* imgs_any, const bvc_pixel_format* fmt, const int* idx, int batch, int ntok,
                        const float* params, float* out, void* stream) {
     BVC_REQUIRE(c && imgs_any && params && out, "vit_forward: null argument");
-    PixelSrc imgs = pixels_f32((const float*)imgs_any);
-    if (fmt && fmt->dtype != BVC_PIXELS_F32) {
-        BVC_REQUIRE(fmt->dtype == BVC_PIXELS_U8 && c->cfg.num_channels <= 4, "vit_forward: unsupported pixel format");
-        imgs.is_u8 = 1;
-        for (int k = 0; k < 4; ++k) {
-            BVC_REQUIRE(fmt->std[k] != 0.f || k >= c->cfg.num_channels, "vit_forward: std[%d] is zero", k);
-            imgs.mean[k] = fmt->mean[k];
-            imgs.stdv[k] = k < c->cfg.num_channels ? fmt->std[k] : 1.f;
-        }
-    }
+    PixelSrc imgs;
+    TRY(pixel_src("vit_forward", imgs_any, fmt, c->cfg.num_channels, &imgs));
     BVC_REQUIRE(batch >= 1 && batch <= c->max_batch, "vit_forward: batch %d outside [1, %d]", batch, c->max_batch);
     if (!idx) ntok = c->L;
     BVC_REQUIRE(ntok >= 1 && ntok <= c->L, "vit_forward: ntok %d outside [1, %d]", ntok, c->L);
     hipStream_t st = (hipStream_t)stream;
-    const bvc_vit_config& cf = c->cfg;
     const VitLayout& L = c->lay;
-    const int B = batch, N = ntok, M = B * N, D = cf.embed_dim;
+    const int B = batch, N = ntok, M = B * N, D = c->cfg.embed_dim;
     c->have_forward = false;
     c->batch = B; c->ntok = N;
-    c->idx = idx ? idx : c->idx_all;
-    c->w.params = params; c->w.wbf = c->wbf;
+    c->idx = idx ? idx : c->front.idx_all;
+    c->w.params = params; c->w.wbf = c->shadow.wbf;
     c->w.drop = &c->drop;
     TRY(take_drop(c->drop, B, N, "vit_forward"));
-    const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
-    if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.total, st));     // see bvc_vit_shadow
-    c->shadow_valid = false;
-    TRY(launch_gather_patches(imgs, c->idx, c->Ape, B, N, pg, st));
-    {
-        GemmProblem p = gemm(c->Ape, (size_t)M * c->Kp, c->Kp, c->wbf + L.pe_w, (size_t)D * c->Kp, c->Kp, M, D, c->Kp, EPI_POS, c->st.act[0].x_in, D);
-        p.bias = params + L.pe_b; p.rowtok = c->idx; p.pos = params + L.pos;
-        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
-    }
-    for (int i = 0; i < c->st.nlayers; ++i) {
-        float* xo = i + 1 < c->st.nlayers ? c->st.act[i + 1].x_in : c->st.x_out;
-        TRY(layer_forward(c->w, c->st, i, L.blocks[i], c->st.act[i].x_in, xo, B, N, st, i + 1 < c->st.nlayers ? &L.blocks[i + 1] : nullptr));
-    }
-    TRY(launch_ln_fwd(c->st.x_out, identity_rows(), params + L.norm_w, params + L.norm_b, nullptr, c->meanf, c->rstdf, M, D, cf.eps, st, out));
+    TRY(c->shadow.refresh(params, st));
+    TRY(c->front.embed(imgs, c->idx, B, N, c->shadow.wbf + L.pe_w, params + L.pe_b, params + L.pos, c->st.act[0].x_in, D, st, "vit_forward"));
+    TRY(stack_forward(c->w, c->st, L.blocks, B, N, st, true));
+    TRY(launch_ln_fwd(c->st.x_out, identity_rows(), params + L.norm_w, params + L.norm_b, nullptr, c->meanf, c->rstdf, M, D, c->cfg.eps, st, out));
     c->have_forward = true;
     return BVC_OK;
 }
@@ -251,10 +211,7 @@ int bvc_vit_forward_px(bvc_vit_ctx* c, const void* imgs_any, const bvc_pixel_for
 // dout f32 [B*ntok][D] -> grads (flat f32, overwritten).  Pixels and pos_embed receive no gradient.
 int bvc_vit_shadow(bvc_vit_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
     BVC_REQUIRE(c, "vit_shadow: null context");
-    if (shadow_bf16) *shadow_bf16 = c->wbf;
-    if (numel) *numel = (int64_t)c->lay.total;
-    if (valid >= 0) c->shadow_valid = valid != 0;
-    return BVC_OK;
+    return c->shadow.query(valid, shadow_bf16, numel);
 }
 
 int bvc_vit_set_drop(bvc_vit_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
@@ -277,16 +234,9 @@ int bvc_vit_backward(bvc_vit_ctx* c, const float* dout, float* G, bvc_bucket_fn 
     TRY(launch_ln_bwd(c->dout_bf, c->st.x_out, identity_rows(), c->meanf, c->rstdf, params + L.norm_w, c->dres, 0, c->w.dyb[0],
                       G + L.norm_w, G + L.norm_b, c->w.ln_part, M, D, st, top_gate(c->drop, gtop)));
     if (on_bucket) on_bucket(L.norm_w, L.total - L.norm_w, user);
-    for (int i = c->st.nlayers - 1; i >= 0; --i)
-        TRY(layer_backward(c->w, c->st, i, L.blocks[i], c->st.act[i].x_in, c->dres, G, B, N, st, on_bucket, user));
-    {
-        GemmProblem p = gemm(c->w.dyb[c->w.seq % 3], (size_t)M * D, D, c->Ape, (size_t)M * c->Kp, c->Kp, D, c->Kp, M, EPI_F32, G + L.pe_w, c->Kp);
-        p.rowsum = G + L.pe_b;
-        const int tile = plan_dw(&p, 1);
-        TRY(launch_gemm(&p, 1, GEMM_TN, tile, st));
-    }
-    TRY(join_side(c->w, c->w.seq & 1, st, on_bucket, user));
-    TRY(join_side(c->w, (c->w.seq + 1) & 1, st, on_bucket, user));
+    TRY(stack_backward(c->w, c->st, L.blocks, c->dres, G, B, N, st, on_bucket, user));
+    TRY(c->front.embed_backward(c->w, M, D, G + L.pe_w, G + L.pe_b, st));
+    TRY(join_both(c->w, st, on_bucket, user));
     if (on_bucket) on_bucket(0, L.blocks.front().ln1w, user);
     return BVC_OK;
 }
@@ -319,28 +269,26 @@ int bvc_predictor_create(const bvc_predictor_config* cfg, int max_batch, int max
     BVC_REQUIRE(cfg && out && max_batch >= 1 && max_sets >= 1 && max_tokens >= 2, "predictor_create: bad argument");
     TRY(check_pred(*cfg));
     bvc_pred_ctx* c = new bvc_pred_ctx();
+    Making guard{[&] { bvc_predictor_destroy(c); }};
     c->cfg = *cfg;
     c->lay = make_pred_layout(*cfg);
     c->max_batch = max_batch; c->max_sets = max_sets; c->max_tokens = max_tokens;
     const size_t S = (size_t)max_batch * max_sets, M = S * max_tokens, Mc = (size_t)max_batch * max_tokens;
     const int D = cfg->embed_dim, Dp = cfg->pred_dim, I = cfg->mlp_hidden, H = cfg->num_heads;
-    int rc = BVC_OK;
-    auto fail = [&](int r) { bvc_predictor_destroy(c); return r; };
-#define A(expr) if ((rc = (expr)) != BVC_OK) return fail(rc)
-    A(c->arena.alloc(&c->wbf, (size_t)c->lay.total));
-    A(c->arena.alloc(&c->z_bf, Mc * D));
-    A(c->arena.alloc(&c->xe, Mc * Dp));
-    A(alloc_stack(c->arena, c->st, Dp, I, H, cfg->depth, cfg->eps, M, S * H * max_tokens));
-    A(alloc_drop(c->arena, c->drop, cfg->depth, (int)S));
-    A(c->arena.alloc(&c->meanf, M));
-    A(c->arena.alloc(&c->rstdf, M));
-    A(c->arena.alloc(&c->lnf, M * Dp));
-    A(c->arena.alloc(&c->dout_bf, M * D));
-    A(c->arena.alloc(&c->dres, M * Dp));
-    A(c->arena.alloc(&c->dxe, Mc * Dp));
+    TRY(c->shadow.alloc(c->arena, c->lay.total));
+    TRY(c->arena.alloc(&c->z_bf, Mc * D));
+    TRY(c->arena.alloc(&c->xe, Mc * Dp));
+    TRY(alloc_stack(c->arena, c->st, Dp, I, H, cfg->depth, cfg->eps, M, S * H * max_tokens));
+    TRY(alloc_drop(c->arena, c->drop, cfg->depth, (int)S));
+    TRY(c->arena.alloc(&c->meanf, M));
+    TRY(c->arena.alloc(&c->rstdf, M));
+    TRY(c->arena.alloc(&c->lnf, M * Dp));
+    TRY(c->arena.alloc(&c->dout_bf, M * D));
+    TRY(c->arena.alloc(&c->dres, M * Dp));
+    TRY(c->arena.alloc(&c->dxe, Mc * Dp));
     // dctx / dqkv scratch is as wide as the (possibly zero-padded) attention rows: Da = H * 32 when the heads are 24 wide
-    A(alloc_work(c->arena, c->w, M * (size_t)std::max(Dp, c->st.Da), M * I, S * H * max_tokens, ln_bwd_workspace_floats_upto((int)M, Dp)));
-#undef A
+    TRY(alloc_work(c->arena, c->w, M * (size_t)std::max(Dp, c->st.Da), M * I, S * H * max_tokens, ln_bwd_workspace_floats_upto((int)M, Dp)));
+    guard.done = true;
     *out = c;
     return BVC_OK;
 }
@@ -351,7 +299,8 @@ int bvc_predictor_create(const bvc_predictor_config* cfg, int max_batch, int max
 int bvc_predictor_forward(bvc_pred_ctx* c, const float* z, const int* idx_ctx, const int* idx_pred, int B, int Nc, int nsets, int Np,
                           const float* params, float* out, void* stream) {
     BVC_REQUIRE(c && z && idx_ctx && idx_pred && params && out, "predictor_forward: null argument");
-    BVC_REQUIRE(B >= 1 && B <= c->max_batch && nsets >= 1 && nsets <= c->max_sets, "predictor_forward: batch / mask-set count out of range");
+    BVC_REQUIRE(B >= 1 && B <= c->max_batch && nsets >= 1 && nsets <= c->max_sets, "predictor_forward: batch %d outside [1, %d] or %d mask sets outside [1, %d]",
+                B, c->max_batch, nsets, c->max_sets);
     BVC_REQUIRE(Nc >= 1 && Np >= 1 && Nc + Np <= c->max_tokens, "predictor_forward: %d + %d tokens exceed %d", Nc, Np, c->max_tokens);
     hipStream_t st = (hipStream_t)stream;
     const bvc_predictor_config& cf = c->cfg;
@@ -360,26 +309,23 @@ int bvc_predictor_forward(bvc_pred_ctx* c, const float* z, const int* idx_ctx, c
     c->have_forward = false;
     c->B = B; c->Nc = Nc; c->Np = Np; c->nsets = nsets;
     c->idx_ctx = idx_ctx; c->idx_pred = idx_pred;
-    c->w.params = params; c->w.wbf = c->wbf;
+    c->w.params = params; c->w.wbf = c->shadow.wbf;
     c->w.drop = &c->drop;
     TRY(take_drop(c->drop, S, T, "predictor_forward"));
-    if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.total, st));     // see bvc_predictor_shadow
-    c->shadow_valid = false;
+    const bf16_t* W = c->shadow.wbf;
+    TRY(c->shadow.refresh(params, st));
     TRY(launch_gather_rows_bf16(z, identity_rows(), c->z_bf, Mc, D, st));
     {   // predictor_embed + bias + pos[masks_x]
-        GemmProblem p = gemm(c->z_bf, (size_t)Mc * D, D, c->wbf + L.emb_w, (size_t)Dp * D, D, Mc, Dp, D, EPI_POS, c->xe, Dp);
+        GemmProblem p = gemm(c->z_bf, (size_t)Mc * D, D, W + L.emb_w, (size_t)Dp * D, D, Mc, Dp, D, EPI_POS, c->xe, Dp);
         p.bias = params + L.emb_b; p.rowtok = idx_ctx; p.pos = params + L.pos;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
     TRY(launch_pred_assemble(c->xe, params + L.mask_token, params + L.pos, idx_pred, c->st.act[0].x_in, nsets, B, Nc, Np, Dp, st));
-    for (int i = 0; i < c->st.nlayers; ++i) {
-        float* xo = i + 1 < c->st.nlayers ? c->st.act[i + 1].x_in : c->st.x_out;
-        TRY(layer_forward(c->w, c->st, i, L.blocks[i], c->st.act[i].x_in, xo, S, T, st, i + 1 < c->st.nlayers ? &L.blocks[i + 1] : nullptr));
-    }
+    TRY(stack_forward(c->w, c->st, L.blocks, S, T, st, true));
     const RowMap tail{Np, T, Nc};
     TRY(launch_ln_fwd(c->st.x_out, tail, params + L.norm_w, params + L.norm_b, c->lnf, c->meanf, c->rstdf, Mo, Dp, cf.eps, st));
     {
-        GemmProblem p = gemm(c->lnf, (size_t)Mo * Dp, Dp, c->wbf + L.proj_w, (size_t)D * Dp, Dp, Mo, D, Dp, EPI_F32, out, D);
+        GemmProblem p = gemm(c->lnf, (size_t)Mo * Dp, Dp, W + L.proj_w, (size_t)D * Dp, Dp, Mo, D, Dp, EPI_F32, out, D);
         p.bias = params + L.proj_b;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
@@ -390,10 +336,7 @@ int bvc_predictor_forward(bvc_pred_ctx* c, const float* z, const int* idx_ctx, c
 // dout f32 [nsets*B*Np][D] -> grads (flat f32, overwritten) and dz f32 [B*Nc][D] (gradient for the context encoder)
 int bvc_predictor_shadow(bvc_pred_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
     BVC_REQUIRE(c, "predictor_shadow: null context");
-    if (shadow_bf16) *shadow_bf16 = c->wbf;
-    if (numel) *numel = (int64_t)c->lay.total;
-    if (valid >= 0) c->shadow_valid = valid != 0;
-    return BVC_OK;
+    return c->shadow.query(valid, shadow_bf16, numel);
 }
 
 int bvc_predictor_set_drop(bvc_pred_ctx* c, const bvc_branch_drop* drop, int samples, void* stream) {
@@ -417,7 +360,7 @@ int bvc_predictor_backward_cb(bvc_pred_ctx* c, const float* dout, float* G, floa
     const int B = c->B, Nc = c->Nc, Np = c->Np, nsets = c->nsets;
     const int D = cf.embed_dim, Dp = cf.pred_dim, T = Nc + Np, S = nsets * B, Mc = B * Nc, Mo = S * Np, M = S * T;
     const float* params = c->w.params;
-    const bf16_t* W = c->wbf;
+    const bf16_t* W = c->shadow.wbf;
     begin_backward(c->w);
     BVC_CHECK_HIP(hipMemsetAsync(G, 0, (size_t)L.total * 4, st));
     TRY(launch_gather_rows_bf16(dout, identity_rows(), c->dout_bf, Mo, D, st));
@@ -438,10 +381,8 @@ int bvc_predictor_backward_cb(bvc_pred_ctx* c, const float* dout, float* G, floa
     TRY(launch_ln_bwd(c->w.dln, c->st.x_out, tail, c->meanf, c->rstdf, params + L.norm_w, c->dres, 0, c->w.dyb[0],
                       G + L.norm_w, G + L.norm_b, c->w.ln_part, Mo, Dp, st, top_gate(c->drop, gtop)));
     if (on_bucket) on_bucket(L.norm_w, L.total - L.norm_w, user);
-    for (int i = c->st.nlayers - 1; i >= 0; --i)
-        TRY(layer_backward(c->w, c->st, i, L.blocks[i], c->st.act[i].x_in, c->dres, G, S, T, st, on_bucket, user));
-    TRY(join_side(c->w, c->w.seq & 1, st, on_bucket, user));
-    TRY(join_side(c->w, (c->w.seq + 1) & 1, st, on_bucket, user));
+    TRY(stack_backward(c->w, c->st, L.blocks, c->dres, G, S, T, st, on_bucket, user));
+    TRY(join_both(c->w, st, on_bucket, user));
     // sequence assembly: mask token (summed over every predicted position), context tokens (summed over the nsets copies)
     TRY(launch_colsum_f32(c->dres, tail, Mo, Dp, G + L.mask_token, st));
     TRY(launch_pred_ctx_grad(c->dres, c->dxe, nsets, B, Nc, Np, Dp, st));
@@ -457,34 +398,6 @@ int bvc_predictor_backward_cb(bvc_pred_ctx* c, const float* dout, float* G, floa
     }
     if (on_bucket) on_bucket(0, L.blocks.front().ln1w, user);      // mask token, (frozen) positions, predictor_embed
     return BVC_OK;
-}
-
-// ============================================================================ JEPA operator-level entry points
-int bvc_op_target_select(const float* h, const int* idx_pred, float* out, int nsets, int B, int Np, int L, int D, float eps, void* stream) {
-    BVC_REQUIRE(h && idx_pred && out, "op_target_select: null argument");
-    return launch_target_select(h, idx_pred, out, nsets, B, Np, L, D, eps, (hipStream_t)stream);
-}
-int bvc_op_smooth_l1_workspace(int64_t n) { return smooth_l1_blocks((size_t)n); }
-int bvc_op_smooth_l1_fwd(const float* z, const float* h, int64_t n, float* workspace, float* loss, void* stream) {
-    BVC_REQUIRE(z && h && workspace && loss && n > 0, "op_smooth_l1_fwd: bad argument");
-    return launch_smooth_l1_fwd(z, h, (size_t)n, workspace, loss, (hipStream_t)stream);
-}
-int bvc_op_smooth_l1_bwd(const float* z, const float* h, const float* grad_loss, int64_t n, float* dz, void* stream) {
-    BVC_REQUIRE(z && h && grad_loss && dz && n > 0, "op_smooth_l1_bwd: bad argument");
-    return launch_smooth_l1_bwd(z, h, grad_loss, (size_t)n, dz, (hipStream_t)stream);
-}
-int bvc_op_ema(float* target, const float* online, int64_t n, float momentum, void* stream) {
-    BVC_REQUIRE(target && online && n >= 0, "op_ema: bad argument");
-    return launch_ema(target, online, (size_t)n, momentum, (hipStream_t)stream);
-}
-
-int bvc_op_token_mean(const float* x, int batch, int ntok, int dim, float* out, void* stream) {
-    BVC_REQUIRE(x && out && batch > 0 && ntok > 0 && dim > 0, "op_token_mean: bad argument");
-    return launch_token_mean(x, batch, ntok, dim, out, (hipStream_t)stream);
-}
-int bvc_op_token_mean_bwd(const float* dmean, int batch, int ntok, int dim, float* dx, void* stream) {
-    BVC_REQUIRE(dmean && dx && batch > 0 && ntok > 0 && dim > 0, "op_token_mean_bwd: bad argument");
-    return launch_token_mean_bwd(dmean, batch, ntok, dim, dx, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// VideoMAE pre-training step on gfx950: context, workspaces and the forward / backward schedules.
-// Host code only - every kernel lives in gemm.hip / attention.hip / rowops.hip.
+// VideoMAE on gfx950: the pre-training, inference and fine-tuning contexts, their workspaces and forward / backward schedules.
+// Host code only - every kernel lives in gemm.hip / attention.hip / rowops.hip, the layer schedule in stack.hip, what the contexts
+// share around it in context.hip, and the entry points that belong to no model in ops.hip.
 //
 // Follows VideoMAEForPreTraining.forward (HF:531-671; instantiated by the reference at
 // pretraining/generative/pretrain_videomae.py:61-64) with these MI355X-first changes:
@@ -12,27 +13,14 @@
 // Numerics: bf16 MFMA operands, f32 accumulation, f32 residual stream, f32 LayerNorm / softmax / loss
 // statistics, f32 master weights and gradients.
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <string>
 #include <vector>
 
-#include "stack.h"
-
-namespace bvc {
-static thread_local char g_err[1024] = "";
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace bvc
+#include "context.h"
 
 using namespace bvc;
 
@@ -42,7 +30,6 @@ namespace {
 struct Layout : ParamTable {
     int64_t pe_w = 0, pe_b = 0, e2d_w = 0, mask_token = 0, norm_w = 0, norm_b = 0, head_w = 0, head_b = 0;
     std::vector<LayerOff> enc, dec;
-
 };
 
 int check_config(const bvc_videomae_config& c) {
@@ -92,7 +79,7 @@ Layout make_layout(const bvc_videomae_config& c) {
 struct bvc_ctx {
     bvc_videomae_config cfg;
     Layout lay;
-    int max_batch, nmask, nvis, L, P, Kp;
+    int max_batch, nmask, nvis, L, P;
     // the decoder reconstructs ndec of the nmask masked tokens (all of them unless the context was made by bvc_videomae_create_dual):
     // Ld = nvis + ndec rows per clip, the visible tokens first
     int ndec, Ld;
@@ -103,11 +90,10 @@ struct bvc_ctx {
     // per-step state
     int batch = 0;
     bool have_forward = false;
-    bf16_t* wbf;       // bf16 copy of the flat parameters
-    bool shadow_valid = false;   // set by bvc_videomae_shadow for ONE forward: wbf already matches the parameters it will be given
+    Shadow shadow;     // bf16 copy of the flat parameters (bvc_videomae_shadow)
     const float* params = nullptr;
     int *vis_idx, *dec_idx, *status;     // dec_idx [B][ndec]: the decoded masked tokens, ascending
-    bf16_t* Ape;       // bf16 [B*nvis][Kp] gathered visible tubes
+    PatchFront front;  // the visible tubes
     Stack enc, dec;
     bf16_t* xe_bf;     // bf16 [B*nvis][D] encoder output
     float *meanf, *rstdf;
@@ -125,101 +111,24 @@ struct bvc_ctx {
 
 namespace {
 
-void sinusoid(std::vector<float>& out, int n, int d) {   // HF:80-91, float64 then cast
-    out.resize((size_t)n * d);
+int upload_sinusoid(float* dst, int n, int d) {   // HF:80-91, float64 then cast
+    std::vector<float> out((size_t)n * d);
     for (int p = 0; p < n; ++p)
         for (int j = 0; j < d; ++j) {
             const double ang = (double)p / pow(10000.0, 2.0 * (j / 2) / (double)d);
             out[(size_t)p * d + j] = (float)((j & 1) ? cos(ang) : sin(ang));
         }
-}
-
-}  // namespace
-
-namespace {
-int pixel_src(const void* pixels, const bvc_pixel_format* fmt, int channels, PixelSrc* out) {
-    PixelSrc px = pixels_f32((const float*)pixels);
-    if (fmt && fmt->dtype != BVC_PIXELS_F32) {
-        BVC_REQUIRE(fmt->dtype == BVC_PIXELS_U8, "pixel format: dtype %d unknown", fmt->dtype);
-        BVC_REQUIRE(channels <= 4, "pixel format: uint8 input supports at most 4 channels");
-        px.is_u8 = 1;
-        for (int c = 0; c < 4; ++c) {
-            BVC_REQUIRE(fmt->std[c] != 0.f || c >= channels, "pixel format: std[%d] is zero", c);
-            px.mean[c] = fmt->mean[c];
-            px.stdv[c] = c < channels ? fmt->std[c] : 1.f;
-        }
-    }
-    *out = px;
-    return BVC_OK;
-}
-}  // namespace
-
-// ------------------------------------------------------------------ Mixup / CutMix of a classification context (bvc_*_set_mix)
-namespace {
-struct MixState {
-    ClipMix* table = nullptr;          // the context's copy, max_batch entries
-    int* status = nullptr;             // bit 0: an entry of the last mixed forward was out of range
-    const bvc_clip_mix* armed = nullptr;
-    int samples = 0;
-};
-
-int alloc_mix(Arena& a, MixState& m, int max_batch) {
-    TRY(a.alloc(&m.table, (size_t)max_batch));
-    return a.alloc(&m.status, 4);
-}
-
-int set_mix(MixState& m, const bvc_clip_mix* mix, int samples, int max_batch, const char* who) {
-    m.armed = nullptr;
-    if (!mix) return BVC_OK;
-    BVC_REQUIRE(samples >= 1 && samples <= max_batch, "%s: %d samples outside [1, %d]", who, samples, max_batch);
-    m.armed = mix;
-    m.samples = samples;
+    if (hipMemcpy(dst, out.data(), out.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("create: pos upload failed"); return BVC_ERR_HIP; }
     return BVC_OK;
 }
 
-// the gather of a forward: the plain kernel, or - consuming an armed table - the mix kernel on the context's copy of it
-int gather_for_forward(MixState& m, bool* mixed, PixelSrc pixels, const int* idx, bf16_t* A, int B, int N, PatchGeom pg, const char* who,
-                       hipStream_t st) {
-    const bvc_clip_mix* src = m.armed;
-    m.armed = nullptr;
-    *mixed = src != nullptr;
-    if (!src) return launch_gather_patches(pixels, idx, A, B, N, pg, st);
-    BVC_REQUIRE(m.samples == B, "%s: the mix was set for %d samples, the call has %d", who, m.samples, B);
-    BVC_CHECK_HIP(hipMemcpyAsync(m.table, src, (size_t)B * sizeof(ClipMix), hipMemcpyDeviceToDevice, st));
-    BVC_CHECK_HIP(hipMemsetAsync(m.status, 0, 4, st));
-    return launch_gather_patches_mix(pixels, idx, A, B, N, pg, m.table, st, m.status);
-}
+// the softmax scale a stack passes to its attention launches: the true head's when the heads run zero-padded, the default otherwise
+float stack_sm_scale(const Stack& s) { return s.hdp != s.hd ? 1.0f / sqrtf((float)s.hd) : 0.f; }
+
 }  // namespace
 
 // ============================================================================ C ABI
 extern "C" {
-
-const char* bvc_last_error(void) { return bvc::last_error(); }
-const char* bvc_version(void) { return "gfx950;bvc-hip-r5"; }
-
-int bvc_set_option(const char* name, int value) {
-    BVC_REQUIRE(name != nullptr, "set_option: null name");
-    if (!strcmp(name, "gemm8")) { BVC_REQUIRE(value >= -1 && value <= 1, "set_option: gemm8 takes -1 / 0 / 1"); options().gemm8 = value; }
-    else if (!strcmp(name, "dw_overlap")) options().dw_overlap = value != 0;
-    else if (!strcmp(name, "row_stagger")) options().row_stagger = value != 0;
-    else if (!strcmp(name, "row_ln")) { BVC_REQUIRE(value >= -1 && value <= 1, "set_option: row_ln takes -1 / 0 / 1"); options().row_ln = value; }
-    else if (!strcmp(name, "deterministic")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: deterministic takes 0 / 1"); options().deterministic = value; }
-    else if (!strcmp(name, "head_pad")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: head_pad takes 0 / 1"); options().head_pad = value; }
-    else if (!strcmp(name, "dec_tail")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: dec_tail takes 0 / 1"); options().dec_tail = value; }
-    else BVC_REQUIRE(false, "set_option: unknown option '%s'", name);
-    return BVC_OK;
-}
-int bvc_get_option(const char* name) {
-    if (name && !strcmp(name, "gemm8")) return options().gemm8;
-    if (name && !strcmp(name, "dw_overlap")) return options().dw_overlap;
-    if (name && !strcmp(name, "row_ln")) return options().row_ln;
-    if (name && !strcmp(name, "row_stagger")) return options().row_stagger;
-    if (name && !strcmp(name, "deterministic")) return options().deterministic;
-    if (name && !strcmp(name, "head_pad")) return options().head_pad;
-    if (name && !strcmp(name, "dec_tail")) return options().dec_tail;
-    bvc::set_error("get_option: unknown option '%s'", name ? name : "(null)");
-    return BVC_ERR_INVALID;
-}
 
 int bvc_videomae_param_count(const bvc_videomae_config* cfg) {
     if (!cfg || check_config(*cfg) != BVC_OK) return BVC_ERR_INVALID;
@@ -235,13 +144,7 @@ int bvc_videomae_param_info(const bvc_videomae_config* cfg, int index, char* nam
                             int64_t* numel, int* ndim, int64_t shape[5]) {
     BVC_REQUIRE(cfg && name && offset && numel && ndim && shape, "param_info: null argument");
     TRY(check_config(*cfg));
-    const Layout L = make_layout(*cfg);
-    BVC_REQUIRE(index >= 0 && index < (int)L.entries.size(), "param_info: index %d out of range", index);
-    const ParamEntry& e = L.entries[index];
-    snprintf(name, name_cap, "%s", e.name.c_str());
-    *offset = e.offset; *numel = e.numel; *ndim = e.ndim;
-    for (int i = 0; i < 5; ++i) shape[i] = e.shape[i];
-    return BVC_OK;
+    return param_info(make_layout(*cfg), index, name, name_cap, offset, numel, ndim, shape);
 }
 
 void bvc_videomae_destroy(bvc_ctx* c) {
@@ -259,84 +162,56 @@ int bvc_videomae_create_dual(const bvc_videomae_config* cfg, int max_batch, int 
     BVC_REQUIRE(cfg && out, "create: null argument");
     TRY(check_config(*cfg));
     BVC_REQUIRE(max_batch >= 1, "create: max_batch must be >= 1");
+    const PatchGeom pg = patch_geom(*cfg);
+    const int L = seq_len(pg), nvis = L - num_masked, Ld = nvis + num_decoded;
+    BVC_REQUIRE(num_masked >= 1 && nvis >= 1, "create: num_masked=%d must leave at least one visible and one masked token of %d", num_masked, L);
+    BVC_REQUIRE(num_decoded >= 1 && num_decoded <= num_masked, "create: num_decoded=%d must lie in [1, num_masked=%d]", num_decoded, num_masked);
+    // decoder side: Md rows of Ld per clip, Mm decoded rows
+    const size_t B = max_batch, Mv = B * nvis, Md = B * Ld, Mm = B * num_decoded;
+    const int D = cfg->hidden_size, Dd = cfg->decoder_hidden_size, I = cfg->intermediate_size, Id = cfg->decoder_intermediate_size;
+    const int H = cfg->num_attention_heads, Hd = cfg->decoder_num_attention_heads;
+    {   // refuse before allocating anything (alloc_stack checks it again).  The widest operand is the decoder's fc1 output (VideoMAE-H:
+        // 1568 x 2560 per clip, 4 GiB at 534 clips; from 2 GiB, 267 clips, the 256-row persistent GEMM hands those products to the
+        // 128 x 128 kernels)
+        const size_t we = std::max<size_t>(3 * (size_t)H * attn_width(D / H), (size_t)I), wd = std::max<size_t>(3 * (size_t)Hd * attn_width(Dd / Hd), (size_t)Id);
+        const bool dec = Ld * wd >= nvis * we;
+        TRY(refuse_operand_extent("create", max_batch, dec ? Ld : nvis, dec ? wd : we, dec ? "decoder" : "encoder"));
+    }
     bvc_ctx* c = new bvc_ctx();
+    Making guard{[&] { bvc_videomae_destroy(c); }};
     c->cfg = *cfg;
     c->lay = make_layout(*cfg);
     c->max_batch = max_batch;
-    const int g = cfg->image_size / cfg->patch_size;
-    c->L = (cfg->num_frames / cfg->tubelet_size) * g * g;
-    c->nmask = num_masked;
-    c->nvis = c->L - num_masked;
-    c->P = cfg->num_channels * cfg->tubelet_size * cfg->patch_size * cfg->patch_size;
-    c->Kp = c->P;
-    if (!(num_masked >= 1 && c->nvis >= 1)) {
-        delete c;
-        set_error("create: num_masked=%d must leave at least one visible and one masked token of %d", num_masked, c->L);
-        return BVC_ERR_INVALID;
-    }
-    if (!(num_decoded >= 1 && num_decoded <= num_masked)) {
-        delete c;
-        set_error("create: num_decoded=%d must lie in [1, num_masked=%d]", num_decoded, num_masked);
-        return BVC_ERR_INVALID;
-    }
-    c->ndec = num_decoded;
-    c->Ld = c->nvis + num_decoded;
-    // decoder side: Md rows of Ld per clip, Mm decoded rows
-    const size_t B = max_batch, Mv = B * c->nvis, Md = B * c->Ld, Mm = B * c->ndec;
-    const int D = cfg->hidden_size, Dd = cfg->decoder_hidden_size, I = cfg->intermediate_size, Id = cfg->decoder_intermediate_size;
-    const int H = cfg->num_attention_heads, Hd = cfg->decoder_num_attention_heads;
-    int rc = BVC_OK;
-    auto fail = [&](int r) { bvc_videomae_destroy(c); return r; };
-    {   // every bf16 operand travels with a 32-bit byte extent: refuse before allocating anything (alloc_stack checks it again).  The
-        // widest is the decoder's fc1 output (VideoMAE-H: 1568 x 2560 per clip, 4 GiB at 534 clips; from 2 GiB, 267 clips, the
-        // 256-row persistent GEMM hands those products to the 128 x 128 kernels)
-        const size_t we = std::max<size_t>(3 * (size_t)H * attn_width(D / H), (size_t)I), wd = std::max<size_t>(3 * (size_t)Hd * attn_width(Dd / Hd), (size_t)Id);
-        const size_t ee = Mv * we * 2, ed = Md * wd * 2;
-        if (ee >= 0xFFFFFFF0ull || ed >= 0xFFFFFFF0ull) {
-            const bool dec = ed >= ee;
-            set_error("create: max_batch %d exceeds the 4 GiB operand extent: the %s's %zu tokens x %zu bf16 columns are %.2f GiB; at most %zu clips",
-                      max_batch, dec ? "decoder" : "encoder", dec ? Md : Mv, dec ? wd : we, (dec ? ed : ee) / 1073741824.0,
-                      (size_t)(0xFFFFFFEFull / std::max((dec ? ed : ee) / B, (size_t)1)));
-            delete c;
-            return BVC_ERR_INVALID;
-        }
-    }
-#define A(expr) if ((rc = (expr)) != BVC_OK) return fail(rc)
-    A(c->arena.alloc(&c->pos_enc, (size_t)c->L * D));
-    A(c->arena.alloc(&c->pos_dec, (size_t)c->L * Dd));
-    A(c->arena.alloc(&c->wbf, (size_t)c->lay.total));
-    A(c->arena.alloc(&c->vis_idx, Mv));
-    A(c->arena.alloc(&c->dec_idx, Mm));
+    c->L = L; c->P = patch_dim(pg);
+    c->nmask = num_masked; c->nvis = nvis; c->ndec = num_decoded; c->Ld = Ld;
+    TRY(c->arena.alloc(&c->pos_enc, (size_t)L * D));
+    TRY(c->arena.alloc(&c->pos_dec, (size_t)L * Dd));
+    TRY(c->shadow.alloc(c->arena, c->lay.total));
+    TRY(c->arena.alloc(&c->vis_idx, Mv));
+    TRY(c->arena.alloc(&c->dec_idx, Mm));
     // token 0 everywhere: a clip whose mask (or decode) count differs from the context's leaves entries unwritten, and the gather kernels
     // must then read in-range indices (the status word flags the clip; the Python side raises on the next step)
-    if (hipMemset(c->vis_idx, 0, (size_t)Mv * sizeof(int)) != hipSuccess || hipMemset(c->dec_idx, 0, (size_t)Mm * sizeof(int)) != hipSuccess) {
-        set_error("videomae_create: hipMemset of the token lists failed");
-        bvc_videomae_destroy(c);
-        return BVC_ERR_HIP;
-    }
-    A(c->arena.alloc(&c->status, 4));
-    A(c->arena.alloc(&c->Ape, Mv * c->Kp));
-    A(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, Mv, B * H * c->nvis));
-    A(alloc_stack(c->arena, c->dec, Dd, Id, Hd, cfg->decoder_num_hidden_layers, cfg->layer_norm_eps, Md, B * Hd * c->Ld));
-    A(c->arena.alloc(&c->xe_bf, Mv * D));
-    A(c->arena.alloc(&c->meanf, Mm));
-    A(c->arena.alloc(&c->rstdf, Mm));
-    A(c->arena.alloc(&c->lnf, Mm * Dd));
-    A(c->arena.alloc(&c->labels, Mm * c->P));
-    A(c->arena.alloc(&c->diff, Mm * c->P));
-    A(c->arena.alloc(&c->partial, (Mm / 64 + 2) * (c->P / 64 + 2)));
-    A(c->arena.alloc(&c->dres_enc, Mv * D));
-    A(c->arena.alloc(&c->dres_dec, Md * Dd));
-    const size_t MD = std::max(Mv * D, Md * Dd), MI = std::max(Mv * I, Md * Id);
-    A(c->arena.alloc(&c->de2d, Mv * Dd));
-    A(alloc_work(c->arena, c->w, MD, MI, std::max(B * H * c->nvis, B * Hd * c->Ld),
-                 std::max(ln_bwd_workspace_floats_upto((int)Mv, D), ln_bwd_workspace_floats_upto((int)Md, Dd))));
-#undef A
-    std::vector<float> tab;
-    sinusoid(tab, c->L, D);
-    if (hipMemcpy(c->pos_enc, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("create: pos upload failed"); return fail(BVC_ERR_HIP); }
-    sinusoid(tab, c->L, Dd);
-    if (hipMemcpy(c->pos_dec, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("create: pos upload failed"); return fail(BVC_ERR_HIP); }
+    BVC_CHECK_HIP(hipMemset(c->vis_idx, 0, (size_t)Mv * sizeof(int)));
+    BVC_CHECK_HIP(hipMemset(c->dec_idx, 0, (size_t)Mm * sizeof(int)));
+    TRY(c->arena.alloc(&c->status, 4));
+    TRY(c->front.alloc(c->arena, pg, Mv, false));
+    TRY(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, Mv, B * H * nvis));
+    TRY(alloc_stack(c->arena, c->dec, Dd, Id, Hd, cfg->decoder_num_hidden_layers, cfg->layer_norm_eps, Md, B * Hd * Ld));
+    TRY(c->arena.alloc(&c->xe_bf, Mv * D));
+    TRY(c->arena.alloc(&c->meanf, Mm));
+    TRY(c->arena.alloc(&c->rstdf, Mm));
+    TRY(c->arena.alloc(&c->lnf, Mm * Dd));
+    TRY(c->arena.alloc(&c->labels, Mm * c->P));
+    TRY(c->arena.alloc(&c->diff, Mm * c->P));
+    TRY(c->arena.alloc(&c->partial, (Mm / 64 + 2) * (c->P / 64 + 2)));
+    TRY(c->arena.alloc(&c->dres_enc, Mv * D));
+    TRY(c->arena.alloc(&c->dres_dec, Md * Dd));
+    TRY(c->arena.alloc(&c->de2d, Mv * Dd));
+    TRY(alloc_work(c->arena, c->w, std::max(Mv * D, Md * Dd), std::max(Mv * I, Md * Id), std::max(B * H * nvis, B * Hd * Ld),
+                   std::max(ln_bwd_workspace_floats_upto((int)Mv, D), ln_bwd_workspace_floats_upto((int)Md, Dd))));
+    TRY(upload_sinusoid(c->pos_enc, L, D));
+    TRY(upload_sinusoid(c->pos_dec, L, Dd));
+    guard.done = true;
     *out = c;
     return BVC_OK;
 }
@@ -356,7 +231,7 @@ int bvc_videomae_forward_dual(bvc_ctx* c, const void* pixels_any, const bvc_pixe
     BVC_REQUIRE(c && pixels_any && mask && params && loss, "forward: null argument");
     BVC_REQUIRE(decode_mask || c->ndec == c->nmask, "forward: the context decodes %d of %d masked tokens and needs a decode mask", c->ndec, c->nmask);
     PixelSrc pixels;
-    TRY(pixel_src(pixels_any, fmt, c->cfg.num_channels, &pixels));
+    TRY(pixel_src("forward", pixels_any, fmt, c->cfg.num_channels, &pixels));
     BVC_REQUIRE(batch >= 1 && batch <= c->max_batch, "forward: batch %d outside [1, %d]", batch, c->max_batch);
     hipStream_t st = (hipStream_t)stream;
     const bvc_videomae_config& cf = c->cfg;
@@ -368,31 +243,20 @@ int bvc_videomae_forward_dual(bvc_ctx* c, const void* pixels_any, const bvc_pixe
     c->batch = B;
     c->params = params;
     c->w.params = params;
-    c->w.wbf = c->wbf;
-    const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
+    c->w.wbf = c->shadow.wbf;
+    const bf16_t* W = c->shadow.wbf;
 
-    // the bf16 copy of the parameters: refreshed here unless the caller vouches that it still matches `params` (bvc_videomae_shadow:
-    // the fused optimisers write it together with the parameters)
-    if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.total, st));
-    c->shadow_valid = false;
+    TRY(c->shadow.refresh(params, st));
     BVC_CHECK_HIP(hipMemsetAsync(c->status, 0, 16, st));
     if (decode_mask) TRY(launch_dual_mask_index(mask, decode_mask, B, Lq, nvis, ndec, c->vis_idx, c->dec_idx, c->status, st));
     else TRY(launch_mask_index(mask, B, Lq, nvis, ndec, c->vis_idx, c->dec_idx, c->status, st));
-    TRY(launch_gather_patches(pixels, c->vis_idx, c->Ape, B, nvis, pg, st));
-    {   // tube patch embedding of the visible tokens + bias + sinusoid (HF:109-124,164-177)
-        GemmProblem p = gemm(c->Ape, (size_t)Mv * c->Kp, c->Kp, c->wbf + L.pe_w, (size_t)D * c->Kp, c->Kp, Mv, D, c->Kp, EPI_POS,
-                             c->enc.act[0].x_in, D);
-        p.bias = params + L.pe_b; p.rowtok = c->vis_idx; p.pos = c->pos_enc;
-        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
-    }
-    for (int i = 0; i < c->enc.nlayers; ++i) {
-        float* xo = i + 1 < c->enc.nlayers ? c->enc.act[i + 1].x_in : c->enc.x_out;
-        TRY(layer_forward(c->w, c->enc, i, L.enc[i], c->enc.act[i].x_in, xo, B, nvis, st, i + 1 < c->enc.nlayers ? &L.enc[i + 1] : nullptr));
-    }
+    // tube patch embedding of the visible tokens + bias + sinusoid
+    TRY(c->front.embed(pixels, c->vis_idx, B, nvis, W + L.pe_w, params + L.pe_b, c->pos_enc, c->enc.act[0].x_in, D, st, "forward"));
+    TRY(stack_forward(c->w, c->enc, L.enc, B, nvis, st, true));
     // encoder -> decoder glue (HF:566-582)
     TRY(launch_gather_rows_bf16(c->enc.x_out, identity_rows(), c->xe_bf, Mv, D, st));
     {
-        GemmProblem p = gemm(c->xe_bf, (size_t)Mv * D, D, c->wbf + L.e2d_w, (size_t)Dd * D, D, Mv, Dd, D, EPI_E2D, c->dec.act[0].x_in, Dd);
+        GemmProblem p = gemm(c->xe_bf, (size_t)Mv * D, D, W + L.e2d_w, (size_t)Dd * D, D, Mv, Dd, D, EPI_E2D, c->dec.act[0].x_in, Dd);
         p.rowtok = c->vis_idx; p.pos = c->pos_dec; p.rin = nvis; p.rout = Ld;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
@@ -400,17 +264,13 @@ int bvc_videomae_forward_dual(bvc_ctx* c, const void* pixels_any, const bvc_pixe
     // the head reads the decoded rows only: the last layer computes nothing else behind its qkv product when the shapes allow (tail mode)
     const LayerTail lt{nvis, ndec};
     c->tail_on = layer_tail_ok(c->w, c->dec, B, nvis, ndec);
-    for (int i = 0; i < c->dec.nlayers; ++i) {
-        const bool last = i + 1 == c->dec.nlayers;
-        float* xo = !last ? c->dec.act[i + 1].x_in : c->dec.x_out;
-        TRY(layer_forward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, xo, B, Ld, st, !last ? &L.dec[i + 1] : nullptr, last && c->tail_on ? &lt : nullptr));
-    }
+    TRY(stack_forward(c->w, c->dec, L.dec, B, Ld, st, true, c->tail_on ? &lt : nullptr));
     // last ndec tokens -> LayerNorm -> head, fused with the pixel-target MSE (HF:497-501,588-664); in tail mode x_out holds just those rows
     const RowMap tail = c->tail_on ? identity_rows() : RowMap{ndec, Ld, nvis};
     TRY(launch_ln_fwd(c->dec.x_out, tail, params + L.norm_w, params + L.norm_b, c->lnf, c->meanf, c->rstdf, Mm, Dd, cf.decoder_norm_eps, st));
-    TRY(launch_labels(pixels, c->dec_idx, c->labels, B, ndec, pg, cf.norm_pix_loss, st));
+    TRY(launch_labels(pixels, c->dec_idx, c->labels, B, ndec, c->front.pg, cf.norm_pix_loss, st));
     {
-        GemmProblem p = gemm(c->lnf, (size_t)Mm * Dd, Dd, c->wbf + L.head_w, (size_t)P * Dd, Dd, Mm, P, Dd, EPI_LOSS, c->diff, P);
+        GemmProblem p = gemm(c->lnf, (size_t)Mm * Dd, Dd, W + L.head_w, (size_t)P * Dd, Dd, Mm, P, Dd, EPI_LOSS, c->diff, P);
         p.bias = params + L.head_b; p.labels = c->labels; p.partial = c->partial; p.C2 = logits;
         c->npartial = gemm_num_tiles(p, -1);
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
@@ -430,9 +290,8 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
     const int B = c->batch, nvis = c->nvis, ndec = c->ndec, Ld = c->Ld;
     const int Mv = B * nvis, Md = B * Ld, Mm = B * ndec;
     const int D = cf.hidden_size, Dd = cf.decoder_hidden_size, P = c->P;
-    const bf16_t* W = c->wbf;
+    const bf16_t* W = c->shadow.wbf;
     const float* params = c->params;
-    auto bucket = [&](int64_t lo, int64_t hi) { if (on_bucket) on_bucket(lo, hi - lo, user); };
     begin_backward(c->w);
 
     BVC_CHECK_HIP(hipMemsetAsync(G, 0, (size_t)L.total * 4, st));
@@ -465,11 +324,8 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
         TRY(launch_ln_bwd(c->w.dln, c->dec.x_out, tail, c->meanf, c->rstdf, params + L.norm_w, c->dres_dec, 0, c->w.dyb[0],
                           G + L.norm_w, G + L.norm_b, c->w.ln_part, Mm, Dd, st));
     }
-    bucket(L.norm_w, L.total);
-    for (int i = c->dec.nlayers - 1; i >= 0; --i) {
-        TRY(layer_backward(c->w, c->dec, i, L.dec[i], c->dec.act[i].x_in, c->dres_dec, G, B, Ld, st, on_bucket, user,
-                           i + 1 == c->dec.nlayers && c->tail_on ? &lt : nullptr));
-    }
+    if (on_bucket) on_bucket(L.norm_w, L.total - L.norm_w, user);
+    TRY(stack_backward(c->w, c->dec, L.dec, c->dres_dec, G, B, Ld, st, on_bucket, user, c->tail_on ? &lt : nullptr));
     // decoder input: mask token, encoder_to_decoder
     TRY(launch_colsum_f32(c->dres_dec, tail, Mm, Dd, G + L.mask_token, st));
     const RowMap headrows{nvis, Ld, 0};
@@ -484,21 +340,11 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
         p.C2 = c->w.dyb[c->w.seq % 3];   // last read (as a dW operand) by backward step seq-3, fenced since
         TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
     }
-    bucket(L.e2d_w, L.dec.front().ln1w);
-    for (int i = c->enc.nlayers - 1; i >= 0; --i) {
-        TRY(layer_backward(c->w, c->enc, i, L.enc[i], c->enc.act[i].x_in, c->dres_enc, G, B, nvis, st, on_bucket, user));
-    }
-    // patch embedding: weight and bias only (pixels need no gradient)
-    {
-        GemmProblem p = gemm(c->w.dyb[c->w.seq % 3], (size_t)Mv * D, D, c->Ape, (size_t)Mv * c->Kp, c->Kp, D, c->Kp, Mv, EPI_F32, G + L.pe_w, c->Kp);
-        p.rowsum = G + L.pe_b;
-        const int tile = plan_dw(&p, 1);
-        TRY(launch_gemm(&p, 1, GEMM_TN, tile, st));
-    }
-    // fence the last side-stream launches (older one first so ranges keep arriving tail-first)
-    TRY(join_side(c->w, c->w.seq & 1, st, on_bucket, user));
-    TRY(join_side(c->w, (c->w.seq + 1) & 1, st, on_bucket, user));
-    bucket(0, L.enc.front().ln1w);
+    if (on_bucket) on_bucket(L.e2d_w, L.dec.front().ln1w - L.e2d_w, user);
+    TRY(stack_backward(c->w, c->enc, L.enc, c->dres_enc, G, B, nvis, st, on_bucket, user));
+    TRY(c->front.embed_backward(c->w, Mv, D, G + L.pe_w, G + L.pe_b, st));
+    TRY(join_both(c->w, st, on_bucket, user));
+    if (on_bucket) on_bucket(0, L.enc.front().ln1w, user);
     return BVC_OK;
 }
 
@@ -516,7 +362,7 @@ static int tail_tap(bvc_ctx* c, float* dst, hipStream_t st) {
     const int B = c->batch, nvis = c->nvis, ndec = c->ndec, Ld = c->Ld, D = s.D, I = s.I, Da = s.Da;
     const size_t Mq = (size_t)B * ndec, Mv = (size_t)B * nvis;
     const float* P = c->params;
-    const bf16_t* W = c->wbf;
+    const bf16_t* W = c->shadow.wbf;
     bf16_t *ctx_v = a.ctx + Mq * Da, *ln2o_v = a.ln2o + Mq * D, *pre_v = a.pre + Mq * I, *act_v = a.act + Mq * I;
     float *lse_v = a.lse + (size_t)B * s.H * ndec, *h_v = a.h + Mq * D, *mean_v = a.mean2 + Mq, *rstd_v = a.rstd2 + Mq, *out_v = s.x_out + Mq * D;
     const size_t full = (size_t)Ld * D * 4, vis = (size_t)nvis * D * 4, dec = (size_t)ndec * D * 4;
@@ -576,13 +422,13 @@ int bvc_videomae_tap(bvc_ctx* c, const char* name, float* dst, int64_t capacity,
 struct bvc_encoder_ctx {
     bvc_videomae_config cfg;
     Layout lay;
-    int max_batch, L, P;
+    int max_batch, L;
     Arena arena;
     Work w;            // parameter views only; no backward scratch is allocated
     Stack st;          // one LayerAct
     float *pos_enc, *xa, *xb, *pooled, *mean, *rstd;
-    bf16_t *wbf, *Ape;
-    int* idx_all;
+    Shadow shadow;           // never vouched: every encode casts
+    PatchFront front;
     int pooled_batch = 0;    // clips whose pre-norm pooled rows and fc_norm statistics the last encode left (0: none)
     DropState drop;          // bvc_videomae_encoder_set_drop: the forward gate of a train-mode module on the forward-only path
     MixState mix;            // bvc_videomae_encoder_set_mix
@@ -602,36 +448,29 @@ int64_t bvc_videomae_encoder_param_numel(const bvc_videomae_config* cfg) {
 int bvc_videomae_encoder_create(const bvc_videomae_config* cfg, int max_batch, bvc_encoder_ctx** out) {
     BVC_REQUIRE(cfg && out && max_batch >= 1, "encoder_create: bad argument");
     TRY(check_config(*cfg));
+    const PatchGeom pg = patch_geom(*cfg);
+    const size_t M = (size_t)max_batch * seq_len(pg);
+    const int D = cfg->hidden_size, I = cfg->intermediate_size, H = cfg->num_attention_heads;
+    BVC_REQUIRE(M * (size_t)std::max(I, patch_dim(pg)) * 2 < 0xffffffffull, "encoder_create: max_batch %d needs operands above 4 GiB", max_batch);
     bvc_encoder_ctx* c = new bvc_encoder_ctx();
+    Making guard{[&] { bvc_videomae_encoder_destroy(c); }};
     c->cfg = *cfg;
     c->lay = make_layout(*cfg);
     c->max_batch = max_batch;
-    const int g = cfg->image_size / cfg->patch_size;
-    c->L = (cfg->num_frames / cfg->tubelet_size) * g * g;
-    c->P = cfg->num_channels * cfg->tubelet_size * cfg->patch_size * cfg->patch_size;
-    const size_t M = (size_t)max_batch * c->L;
-    const int D = cfg->hidden_size, I = cfg->intermediate_size, H = cfg->num_attention_heads;
-    int rc = BVC_OK;
-    auto fail = [&](int r) { bvc_videomae_encoder_destroy(c); return r; };
-    if (M * (size_t)std::max(I, c->P) * 2 >= 0xffffffffull) { set_error("encoder_create: max_batch %d needs operands above 4 GiB", max_batch); return fail(BVC_ERR_INVALID); }
-#define A(expr) if ((rc = (expr)) != BVC_OK) return fail(rc)
-    A(c->arena.alloc(&c->pos_enc, (size_t)c->L * D));
-    A(c->arena.alloc(&c->wbf, (size_t)c->lay.e2d_w));
-    A(c->arena.alloc(&c->idx_all, M));
-    A(c->arena.alloc(&c->Ape, M * c->P));
-    A(alloc_stack(c->arena, c->st, D, I, H, 1, cfg->layer_norm_eps, M, (size_t)max_batch * H * c->L));
-    A(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
-    A(alloc_mix(c->arena, c->mix, max_batch));
-    A(c->arena.alloc(&c->xa, M * D));
-    A(c->arena.alloc(&c->xb, M * D));
-    A(c->arena.alloc(&c->pooled, (size_t)max_batch * D));
-    A(c->arena.alloc(&c->mean, (size_t)max_batch));
-    A(c->arena.alloc(&c->rstd, (size_t)max_batch));
-    A(launch_iota_mod(c->idx_all, (int)M, c->L, nullptr));
-#undef A
-    std::vector<float> tab;
-    sinusoid(tab, c->L, D);
-    if (hipMemcpy(c->pos_enc, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("encoder_create: pos upload failed"); return fail(BVC_ERR_HIP); }
+    c->L = seq_len(pg);
+    TRY(c->arena.alloc(&c->pos_enc, (size_t)c->L * D));
+    TRY(c->shadow.alloc(c->arena, c->lay.e2d_w));
+    TRY(c->front.alloc(c->arena, pg, M, true));
+    TRY(alloc_stack(c->arena, c->st, D, I, H, 1, cfg->layer_norm_eps, M, (size_t)max_batch * H * c->L));
+    TRY(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
+    TRY(alloc_mix(c->arena, c->mix, max_batch));
+    TRY(c->arena.alloc(&c->xa, M * D));
+    TRY(c->arena.alloc(&c->xb, M * D));
+    TRY(c->arena.alloc(&c->pooled, (size_t)max_batch * D));
+    TRY(c->arena.alloc(&c->mean, (size_t)max_batch));
+    TRY(c->arena.alloc(&c->rstd, (size_t)max_batch));
+    TRY(upload_sinusoid(c->pos_enc, c->L, D));
+    guard.done = true;
     *out = c;
     return BVC_OK;
 }
@@ -640,9 +479,6 @@ int bvc_videomae_encode(bvc_encoder_ctx* c, const float* pixels, int batch, cons
                         const float* fc_norm_b, float fc_norm_eps, float* tokens, float* pooled, void* stream) {
     return bvc_videomae_encode_px(c, pixels, nullptr, batch, params, fc_norm_w, fc_norm_b, fc_norm_eps, tokens, pooled, stream);
 }
-
-// the softmax scale a stack passes to its attention launches: the true head's when the heads run zero-padded, the default otherwise
-static float stack_sm_scale(const Stack& s) { return s.hdp != s.hd ? 1.0f / sqrtf((float)s.hd) : 0.f; }
 
 int bvc_videomae_encode_px(bvc_encoder_ctx* c, const void* pixels_any, const bvc_pixel_format* fmt, int batch, const float* params,
                            const float* fc_norm_w, const float* fc_norm_b, float fc_norm_eps, float* tokens, float* pooled,
@@ -657,29 +493,23 @@ int bvc_videomae_encode_ex(bvc_encoder_ctx* c, const void* pixels_any, const bvc
     float* const att = out ? out->attentions : nullptr;        // [L][B][H][N][N]
     BVC_REQUIRE(c && pixels_any && params && (tokens || pooled || hs || att), "encode: null argument");
     PixelSrc pixels;
-    TRY(pixel_src(pixels_any, fmt, c->cfg.num_channels, &pixels));
+    TRY(pixel_src("encode", pixels_any, fmt, c->cfg.num_channels, &pixels));
     BVC_REQUIRE(batch >= 1 && batch <= c->max_batch, "encode: batch %d outside [1, %d]", batch, c->max_batch);
     BVC_REQUIRE((fc_norm_w == nullptr) == (fc_norm_b == nullptr), "encode: fc_norm weight and bias go together");
     hipStream_t st = (hipStream_t)stream;
     const bvc_videomae_config& cf = c->cfg;
     const Layout& L = c->lay;
-    const int B = batch, N = c->L, M = B * N, D = cf.hidden_size, P = c->P;
+    const int B = batch, N = c->L, M = B * N, D = cf.hidden_size;
     c->w.params = params;
-    c->w.wbf = c->wbf;
+    c->w.wbf = c->shadow.wbf;
     c->w.drop = &c->drop;
     TRY(take_drop(c->drop, B, N, "encode"));
-    const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
-    TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
-    bool mixed = false;
-    TRY(gather_for_forward(c->mix, &mixed, pixels, c->idx_all, c->Ape, B, N, pg, "encode", st));
+    TRY(c->shadow.refresh(params, st));
     const size_t slot = (size_t)M * D;                         // one hidden state
     float* x = hs ? hs : c->xa;                                // given hidden_states, slot 0 is the embedding output
     float* y = c->xb;
-    {
-        GemmProblem p = gemm(c->Ape, (size_t)M * P, P, c->wbf + L.pe_w, (size_t)D * P, P, M, D, P, EPI_POS, x, D);
-        p.bias = params + L.pe_b; p.rowtok = c->idx_all; p.pos = c->pos_enc;
-        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
-    }
+    bool mixed = false;
+    TRY(c->front.embed(pixels, c->front.idx_all, B, N, c->shadow.wbf + L.pe_w, params + L.pe_b, c->pos_enc, x, D, st, "encode", &c->mix, &mixed));
     const int nl = (int)L.enc.size();
     for (int i = 0; i < nl; ++i) {
         // the last layer writes straight into the caller's buffer; with hidden_states, layer i reads slot i and writes slot i + 1
@@ -736,16 +566,15 @@ int bvc_videomae_encoder_fc_norm_backward(bvc_encoder_ctx* c, const float* dpool
 struct bvc_cls_ctx {
     bvc_videomae_config cfg;
     Layout lay;
-    int max_batch, L, P;
+    int max_batch, L;
     Arena arena;
     Work w;
     Stack enc;         // num_hidden_layers LayerActs
     float *pos_enc, *pooled_pre, *mean, *rstd, *fcw, *dres;
-    bf16_t *wbf, *Ape;
-    int* idx_all;
+    Shadow shadow;               // bvc_videomae_cls_shadow
+    PatchFront front;
     int batch = 0;
     bool have_forward = false;
-    bool shadow_valid = false;   // as bvc_ctx::shadow_valid
     DropState drop;              // bvc_videomae_cls_set_drop
     MixState mix;                // bvc_videomae_cls_set_mix
 };
@@ -761,50 +590,35 @@ int bvc_videomae_cls_create(const bvc_videomae_config* cfg, int max_batch, bvc_c
     BVC_REQUIRE(cfg && out, "cls_create: null argument");
     TRY(check_config(*cfg));
     BVC_REQUIRE(max_batch >= 1, "cls_create: max_batch must be >= 1");
-    const int g = cfg->image_size / cfg->patch_size;
-    const size_t L = (size_t)(cfg->num_frames / cfg->tubelet_size) * g * g;
-    const size_t P = (size_t)cfg->num_channels * cfg->tubelet_size * cfg->patch_size * cfg->patch_size;
+    const PatchGeom pg = patch_geom(*cfg);
+    const size_t L = seq_len(pg), P = patch_dim(pg);
     const int D = cfg->hidden_size, I = cfg->intermediate_size, H = cfg->num_attention_heads;
     const size_t Da = (size_t)H * attn_width(D / H);
-    {   // every bf16 operand travels with a 32-bit byte extent: refuse before allocating anything (the widest is fc1's output, or
-        // the qkv product's when the heads are padded; VideoMAE-B: 1568 x 3072 per clip, 4 GiB at 446 clips)
-        const size_t w = std::max(std::max(3 * Da, (size_t)I), P);
-        const size_t per_clip = L * w * 2, bytes = (size_t)max_batch * per_clip;
-        if (bytes >= 0xFFFFFFF0ull) {
-            set_error("cls_create: max_batch %d exceeds the 4 GiB operand extent: %zu tokens x %zu bf16 columns are %.2f GiB; at most %zu clips",
-                      max_batch, (size_t)max_batch * L, w, bytes / 1073741824.0, (size_t)(0xFFFFFFEFull / per_clip));
-            return BVC_ERR_INVALID;
-        }
-    }
+    // refuse before allocating anything: the widest operand is fc1's output, or the qkv product's when the heads are padded
+    // (VideoMAE-B: 1568 x 3072 per clip, 4 GiB at 446 clips)
+    TRY(refuse_operand_extent("cls_create", max_batch, L, std::max(std::max(3 * Da, (size_t)I), P), nullptr));
     bvc_cls_ctx* c = new bvc_cls_ctx();
+    Making guard{[&] { bvc_videomae_cls_destroy(c); }};
     c->cfg = *cfg;
     c->lay = make_layout(*cfg);
     c->max_batch = max_batch;
     c->L = (int)L;
-    c->P = (int)P;
     const size_t M = (size_t)max_batch * L;
-    int rc = BVC_OK;
-    auto fail = [&](int r) { bvc_videomae_cls_destroy(c); return r; };
-#define A(expr) if ((rc = (expr)) != BVC_OK) return fail(rc)
-    A(c->arena.alloc(&c->pos_enc, L * D));
-    A(c->arena.alloc(&c->wbf, (size_t)c->lay.e2d_w));
-    A(c->arena.alloc(&c->idx_all, M));
-    A(c->arena.alloc(&c->Ape, M * P));
-    A(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, M, (size_t)max_batch * H * L));
-    A(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
-    A(alloc_mix(c->arena, c->mix, max_batch));
-    A(c->arena.alloc(&c->pooled_pre, (size_t)max_batch * D));
-    A(c->arena.alloc(&c->mean, (size_t)max_batch));
-    A(c->arena.alloc(&c->rstd, (size_t)max_batch));
-    A(c->arena.alloc(&c->fcw, (size_t)D));
-    A(c->arena.alloc(&c->dres, M * D));
-    A(alloc_work(c->arena, c->w, M * std::max((size_t)D, (size_t)c->enc.Da), M * I, (size_t)max_batch * H * L,
-                 ln_bwd_workspace_floats_upto((int)M, D)));
-    A(launch_iota_mod(c->idx_all, (int)M, c->L, nullptr));
-#undef A
-    std::vector<float> tab;
-    sinusoid(tab, c->L, D);
-    if (hipMemcpy(c->pos_enc, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("cls_create: pos upload failed"); return fail(BVC_ERR_HIP); }
+    TRY(c->arena.alloc(&c->pos_enc, L * D));
+    TRY(c->shadow.alloc(c->arena, c->lay.e2d_w));
+    TRY(c->front.alloc(c->arena, pg, M, true));
+    TRY(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, M, (size_t)max_batch * H * L));
+    TRY(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
+    TRY(alloc_mix(c->arena, c->mix, max_batch));
+    TRY(c->arena.alloc(&c->pooled_pre, (size_t)max_batch * D));
+    TRY(c->arena.alloc(&c->mean, (size_t)max_batch));
+    TRY(c->arena.alloc(&c->rstd, (size_t)max_batch));
+    TRY(c->arena.alloc(&c->fcw, (size_t)D));
+    TRY(c->arena.alloc(&c->dres, M * D));
+    TRY(alloc_work(c->arena, c->w, M * std::max((size_t)D, (size_t)c->enc.Da), M * I, (size_t)max_batch * H * L,
+                   ln_bwd_workspace_floats_upto((int)M, D)));
+    TRY(upload_sinusoid(c->pos_enc, c->L, D));
+    guard.done = true;
     *out = c;
     return BVC_OK;
 }
@@ -814,31 +628,22 @@ int bvc_videomae_cls_forward_px(bvc_cls_ctx* c, const void* pixels_any, const bv
                                 void* stream) {
     BVC_REQUIRE(c && pixels_any && params && fc_norm_w && fc_norm_b && pooled, "cls_forward: null argument");
     PixelSrc pixels;
-    TRY(pixel_src(pixels_any, fmt, c->cfg.num_channels, &pixels));
+    TRY(pixel_src("cls_forward", pixels_any, fmt, c->cfg.num_channels, &pixels));
     BVC_REQUIRE(batch >= 1 && batch <= c->max_batch, "cls_forward: batch %d outside [1, %d]", batch, c->max_batch);
     hipStream_t st = (hipStream_t)stream;
-    const bvc_videomae_config& cf = c->cfg;
     const Layout& L = c->lay;
-    const int B = batch, N = c->L, M = B * N, D = cf.hidden_size, P = c->P;
+    const int B = batch, N = c->L, M = B * N, D = c->cfg.hidden_size;
     c->have_forward = false;
     c->batch = B;
     c->w.params = params;
-    c->w.wbf = c->wbf;
+    c->w.wbf = c->shadow.wbf;
     c->w.drop = &c->drop;
     TRY(take_drop(c->drop, B, N, "cls_forward"));
-    const PatchGeom pg{cf.num_frames, cf.num_channels, cf.image_size, cf.image_size, cf.tubelet_size, cf.patch_size};
-    if (!c->shadow_valid) TRY(launch_cast_bf16(params, c->wbf, (size_t)L.e2d_w, st));
-    c->shadow_valid = false;
+    TRY(c->shadow.refresh(params, st));
     bool mixed = false;
-    TRY(gather_for_forward(c->mix, &mixed, pixels, c->idx_all, c->Ape, B, N, pg, "cls_forward", st));
-    {
-        GemmProblem p = gemm(c->Ape, (size_t)M * P, P, c->wbf + L.pe_w, (size_t)D * P, P, M, D, P, EPI_POS, c->enc.act[0].x_in, D);
-        p.bias = params + L.pe_b; p.rowtok = c->idx_all; p.pos = c->pos_enc;
-        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
-    }
-    const int nl = c->enc.nlayers;
-    for (int i = 0; i < nl; ++i)
-        TRY(layer_forward(c->w, c->enc, i, L.enc[i], c->enc.act[i].x_in, i + 1 < nl ? c->enc.act[i + 1].x_in : c->enc.x_out, B, N, st));
+    TRY(c->front.embed(pixels, c->front.idx_all, B, N, c->shadow.wbf + L.pe_w, params + L.pe_b, c->pos_enc, c->enc.act[0].x_in, D, st,
+                       "cls_forward", &c->mix, &mixed));
+    TRY(stack_forward(c->w, c->enc, L.enc, B, N, st, false));     // unchained, as the inference context runs its layers
     TRY(launch_token_mean(c->enc.x_out, B, N, D, c->pooled_pre, st));
     TRY(launch_ln_fwd(c->pooled_pre, identity_rows(), fc_norm_w, fc_norm_b, nullptr, c->mean, c->rstd, B, D, fc_norm_eps, st, pooled));
     BVC_CHECK_HIP(hipMemcpyAsync(c->fcw, fc_norm_w, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
@@ -865,18 +670,9 @@ int bvc_videomae_cls_backward(bvc_cls_ctx* c, const float* dpooled, float* G, fl
     Gate gtop;     // (the first bf16 copy feeds the last layer's MLP branch: gated here when that context has a gate on)
     TRY(launch_fcnorm_bwd_bcast(dpooled, c->pooled_pre, c->mean, c->rstd, c->fcw, c->dres, c->w.dyb[c->w.seq % 3], dfc_norm_w, dfc_norm_b,
                                 B, N, D, st, top_gate(c->drop, gtop)));
-    for (int i = c->enc.nlayers - 1; i >= 0; --i)
-        TRY(layer_backward(c->w, c->enc, i, L.enc[i], c->enc.act[i].x_in, c->dres, G, B, N, st, on_bucket, user));
-    // patch embedding: weight and bias over all B * L tokens (pixels need no gradient)
-    {
-        GemmProblem p = gemm(c->w.dyb[c->w.seq % 3], (size_t)M * D, D, c->Ape, (size_t)M * c->P, c->P, D, c->P, M, EPI_F32, G + L.pe_w, c->P);
-        p.rowsum = G + L.pe_b;
-        const int tile = plan_dw(&p, 1);
-        TRY(launch_gemm(&p, 1, GEMM_TN, tile, st));
-    }
-    // fence the last side-stream launches (older one first so ranges keep arriving tail-first)
-    TRY(join_side(c->w, c->w.seq & 1, st, on_bucket, user));
-    TRY(join_side(c->w, (c->w.seq + 1) & 1, st, on_bucket, user));
+    TRY(stack_backward(c->w, c->enc, L.enc, c->dres, G, B, N, st, on_bucket, user));
+    TRY(c->front.embed_backward(c->w, M, D, G + L.pe_w, G + L.pe_b, st));
+    TRY(join_both(c->w, st, on_bucket, user));
     if (on_bucket) on_bucket(0, L.enc.front().ln1w, user);
     return BVC_OK;
 }
@@ -911,277 +707,12 @@ int bvc_videomae_cls_set_mix(bvc_cls_ctx* c, const bvc_clip_mix* mix_dev, int sa
 
 int bvc_videomae_cls_shadow(bvc_cls_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
     BVC_REQUIRE(c, "videomae_cls_shadow: null context");
-    if (shadow_bf16) *shadow_bf16 = c->wbf;
-    if (numel) *numel = (int64_t)c->lay.e2d_w;
-    if (valid >= 0) c->shadow_valid = valid != 0;
-    return BVC_OK;
+    return c->shadow.query(valid, shadow_bf16, numel);
 }
 
-// ------------------------------------------------------------------ operator-level entry points
-int bvc_op_gemm(const bvc_gemm_desc* problems, int count, int layout, int tile_cfg, int stages, void* stream) {
-    BVC_REQUIRE(problems, "op_gemm: null problems");
-    BVC_REQUIRE(layout >= 0 && layout <= 2, "op_gemm: bad layout %d", layout);
-    return launch_gemm(problems, count, (GemmLayout)layout, tile_cfg, (hipStream_t)stream, stages);
-}
-static int op_gate(const bvc_branch_drop* drop, int layer, int branch, int M, Gate* g) {
-    BVC_REQUIRE(drop && layer >= 0 && layer < (1 << 22) && (branch == 0 || branch == 1), "gate: null description, or layer / branch out of range");
-    BVC_REQUIRE(drop->hidden_p >= 0.f && drop->hidden_p < 1.f && drop->rows_per_sample >= 1, "gate: hidden_p outside [0, 1) or rows_per_sample < 1");
-    const int samples = (M + drop->rows_per_sample - 1) / drop->rows_per_sample;
-    *g = make_gate(drop->hidden_p, drop->seed, drop->offset,
-                   drop->path_scale ? drop->path_scale + ((size_t)layer * 2 + branch) * samples : nullptr, drop->rows_per_sample, layer, branch);
-    return BVC_OK;
-}
-int bvc_op_gemm_gate(const bvc_gemm_desc* problem, const bvc_branch_drop* drop, int layer, int branch, int tile_cfg, void* stream) {
-    BVC_REQUIRE(problem, "op_gemm_gate: null problem");
-    Gate g;
-    TRY(op_gate(drop, layer, branch, problem->M, &g));
-    return launch_gemm_gate(*problem, g, tile_cfg, (hipStream_t)stream);
-}
-int bvc_op_gemm_gate_kernel(const bvc_gemm_desc* problem, int tile_cfg, char* name, int name_cap) {
-    BVC_REQUIRE(problem && name && name_cap > 0, "op_gemm_gate_kernel: null argument");
-    DryRun& d = dry_run();
-    d.on = true;
-    d.name[0] = 0;
-    const int rc = launch_gemm_gate(*problem, make_gate(0.f, 0, 0, nullptr, 1, 0, 0), tile_cfg, nullptr);
-    d.on = false;
-    if (rc == BVC_OK) snprintf(name, name_cap, "%s", d.name);
-    return rc;
-}
-int bvc_op_dropout_mask(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_dev, void* stream) {
-    BVC_REQUIRE(out_dev && M >= 1 && N >= 1 && layer >= 0 && layer < (1 << 22) && (branch == 0 || branch == 1) && p >= 0.f && p < 1.f,
-                "op_dropout_mask: bad argument");
-    return launch_dropout_mask(make_gate(p, seed, offset, nullptr, 1, layer, branch), (size_t)M * N, out_dev, (hipStream_t)stream);
-}
-int bvc_dropout_mask_host(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_host) {
-    BVC_REQUIRE(out_host && M >= 1 && N >= 1 && layer >= 0 && layer < (1 << 22) && (branch == 0 || branch == 1) && p >= 0.f && p < 1.f,
-                "dropout_mask_host: bad argument");
-    dropout_mask_host(make_gate(p, seed, offset, nullptr, 1, layer, branch), (size_t)M * N, out_host);
-    return BVC_OK;
-}
-int bvc_op_layernorm_bwd_gate(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dres,
-                              int accumulate, void* dres_bf16, float* dgamma, float* dbeta, float* workspace, int M, int D,
-                              const bvc_branch_drop* drop, int layer, int branch, void* stream) {
-    Gate g;
-    TRY(op_gate(drop, layer, branch, M, &g));
-    return launch_ln_bwd((const bf16_t*)dy, x, identity_rows(), mean, rstd, gamma, dres, accumulate, (bf16_t*)dres_bf16, dgamma, dbeta,
-                         workspace, M, D, (hipStream_t)stream, &g);
-}
-int bvc_op_gemm_kernel(const bvc_gemm_desc* problems, int count, int layout, int tile_cfg, int stages, char* name, int name_cap) {
-    BVC_REQUIRE(problems && name && name_cap > 0, "op_gemm_kernel: null argument");
-    BVC_REQUIRE(layout >= 0 && layout <= 2, "op_gemm_kernel: bad layout %d", layout);
-    DryRun& d = dry_run();
-    d.on = true;
-    d.name[0] = 0;
-    const int rc = launch_gemm(problems, count, (GemmLayout)layout, tile_cfg, nullptr, stages);
-    d.on = false;
-    if (rc == BVC_OK) snprintf(name, name_cap, "%s", d.name);
-    return rc;
-}
-int64_t bvc_deterministic_workspace_bytes(void) { return (int64_t)det_scratch_bytes(); }
-int bvc_deterministic_workspace_release(void) { return det_scratch_release(); }
-int bvc_op_gemm_plan_dw(bvc_gemm_desc* problems, int count) {
-    BVC_REQUIRE(problems && count >= 1 && count <= 4, "op_gemm_plan_dw: bad argument");
-    return plan_dw(problems, count);
-}
-int bvc_op_gemm_num_tiles(const bvc_gemm_desc* problem, int tile_cfg) {
-    if (!problem) return BVC_ERR_INVALID;
-    return gemm_num_tiles(*problem, tile_cfg);
-}
-int bvc_op_attention_fwd(const void* qkv, void* ctx_out, float* lse, int B, int N, int H, int head_dim, void* stream) {
-    BVC_REQUIRE(qkv && ctx_out && lse, "op_attention_fwd: null argument");
-    return launch_attn_fwd((const bf16_t*)qkv, (bf16_t*)ctx_out, lse, B, N, H, head_dim, (hipStream_t)stream);
-}
-int bvc_op_attention_bwd(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta, void* dqkv,
-                         int B, int N, int H, int head_dim, void* stream) {
-    BVC_REQUIRE(qkv && ctx_in && dctx && lse && delta && dqkv, "op_attention_bwd: null argument");
-    return launch_attn_bwd((const bf16_t*)qkv, (const bf16_t*)ctx_in, (const bf16_t*)dctx, lse, delta, (bf16_t*)dqkv, B, N, H, head_dim,
-                           (hipStream_t)stream);
-}
-int bvc_op_attention_bwd_part(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta, void* dqkv,
-                              int B, int N, int H, int head_dim, int part, void* stream) {
-    BVC_REQUIRE(qkv && ctx_in && dctx && lse && delta && dqkv, "op_attention_bwd_part: null argument");
-    BVC_REQUIRE(part == 1 || part == 2, "op_attention_bwd_part: part is 1 (dQ + delta) or 2 (dK, dV)");
-    return launch_attn_bwd((const bf16_t*)qkv, (const bf16_t*)ctx_in, (const bf16_t*)dctx, lse, delta, (bf16_t*)dqkv, B, N, H, head_dim,
-                           (hipStream_t)stream, 0.f, part);
-}
-int bvc_op_attention_width(int head_dim) {
-    BVC_REQUIRE(head_dim > 0 && head_dim <= 128 && head_dim % 8 == 0, "op_attention_width: head_dim %d unsupported", head_dim);
-    return attn_width(head_dim);
-}
-int bvc_op_attention_fwd_scaled(const void* qkv, void* ctx_out, float* lse, int B, int N, int H, int head_dim, float softmax_scale,
-                                void* stream) {
-    BVC_REQUIRE(qkv && ctx_out && lse && softmax_scale >= 0.f, "op_attention_fwd_scaled: bad argument");
-    return launch_attn_fwd((const bf16_t*)qkv, (bf16_t*)ctx_out, lse, B, N, H, head_dim, (hipStream_t)stream, softmax_scale);
-}
-int bvc_op_attention_bwd_scaled(const void* qkv, const void* ctx_in, const void* dctx, const float* lse, float* delta, void* dqkv,
-                                int B, int N, int H, int head_dim, float softmax_scale, void* stream) {
-    BVC_REQUIRE(qkv && ctx_in && dctx && lse && delta && dqkv && softmax_scale >= 0.f, "op_attention_bwd_scaled: bad argument");
-    return launch_attn_bwd((const bf16_t*)qkv, (const bf16_t*)ctx_in, (const bf16_t*)dctx, lse, delta, (bf16_t*)dqkv, B, N, H, head_dim,
-                           (hipStream_t)stream, softmax_scale);
-}
-int bvc_op_attention_probs(const void* qkv, const float* lse, float* probs, int B, int N, int H, int head_dim, float softmax_scale,
-                           void* stream) {
-    BVC_REQUIRE(qkv && lse && probs && softmax_scale >= 0.f, "op_attention_probs: bad argument");
-    return launch_attn_probs((const bf16_t*)qkv, lse, probs, B, N, H, head_dim, (hipStream_t)stream, softmax_scale);
-}
-int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y,
-                         float* mean, float* rstd, int M, int D, float eps, void* stream) {
-    BVC_REQUIRE(x && gamma && beta && y && mean && rstd, "op_layernorm_fwd: null argument");
-    return launch_ln_fwd(x, RowMap{rin, rout, roff}, gamma, beta, (bf16_t*)y, mean, rstd, M, D, eps, (hipStream_t)stream);
-}
-int bvc_op_layernorm_bwd(const void* dy, const float* x, int rin, int rout, int roff, const float* mean, const float* rstd,
-                         const float* gamma, float* dres, int accumulate, void* dres_bf16, float* dgamma, float* dbeta,
-                         float* workspace, int M, int D, void* stream) {
-    BVC_REQUIRE(dy && x && mean && rstd && gamma && dres && dgamma && dbeta && workspace, "op_layernorm_bwd: null argument");
-    return launch_ln_bwd((const bf16_t*)dy, x, RowMap{rin, rout, roff}, mean, rstd, gamma, dres, accumulate, (bf16_t*)dres_bf16,
-                         dgamma, dbeta, workspace, M, D, (hipStream_t)stream);
-}
-int64_t bvc_op_layernorm_bwd_workspace(int M, int D) { return (int64_t)ln_bwd_workspace_floats(M, D); }
-int bvc_op_colsum_f32(const float* X, int rin, int rout, int roff, int M, int D, float* out, void* stream) {
-    BVC_REQUIRE(X && out && M > 0 && D > 0, "op_colsum_f32: bad argument");
-    return launch_colsum_f32(X, RowMap{rin, rout, roff}, M, D, out, (hipStream_t)stream);
-}
-int bvc_op_colsum_bf16(const void* X, int M, int N, int ld, float alpha, const float* alpha_dev, float* out, void* stream) {
-    BVC_REQUIRE(X && out, "op_colsum_bf16: null argument");
-    return launch_colsum_bf16_scaled((const bf16_t*)X, M, N, ld, alpha, alpha_dev, out, (hipStream_t)stream);
-}
-int bvc_op_sgd_step(float* params, float* grads, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
-                    float weight_decay, int nesterov, int first_step, int maximize, const float* grad_scale,
-                    const float* found_inf, int write_unscaled_grads, void* bf16_shadow, void* stream) {
-    BVC_REQUIRE(params && grads && n >= 0, "op_sgd_step: bad argument");
-    return launch_sgd_step(params, grads, momentum_buf, (size_t)n, lr, momentum, dampening, weight_decay, nesterov, first_step,
-                           maximize, grad_scale, found_inf, write_unscaled_grads, (bf16_t*)bf16_shadow, (hipStream_t)stream);
-}
-int bvc_op_adam_prepare(float* state3, double lr, double beta1, double beta2, const float* found_inf, void* stream) {
-    BVC_REQUIRE(state3, "op_adam_prepare: null state");
-    return launch_adam_prep(state3, lr, beta1, beta2, found_inf, (hipStream_t)stream);
-}
-int bvc_op_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
-                     double eps, double weight_decay, int decoupled, int maximize, const float* state3, const float* grad_scale,
-                     const float* found_inf, int write_unscaled_grads, void* bf16_shadow, void* stream) {
-    BVC_REQUIRE(params && grads && exp_avg && exp_avg_sq && state3 && n >= 0, "op_adam_step: bad argument");
-    return launch_adam_step(params, grads, exp_avg, exp_avg_sq, (size_t)n, lr, beta1, beta2, eps, weight_decay, decoupled, maximize,
-                            state3, grad_scale, found_inf, write_unscaled_grads, (bf16_t*)bf16_shadow, (hipStream_t)stream);
-}
-int bvc_op_row_ln_selected(int tokens, int width, int mlp_width, int heads) {
-    if (tokens <= 0 || width <= 0 || heads <= 0 || width % heads != 0) return 0;
-    Stack s;
-    s.D = width; s.I = mlp_width; s.H = heads; s.nlayers = 0; s.eps = 0.f; s.x_out = nullptr;
-    s.hd = width / heads; s.hdp = attn_width(s.hd); s.Da = heads * s.hdp;
-    return fuse_row_ln(s, tokens) ? 1 : 0;
-}
-int bvc_op_sgd_step_segments(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,
-                             const int32_t* blk_seg, int nseg, const bvc_sgd_groups* groups, const float* grad_scale, const float* found_inf,
-                             int write_unscaled_grads, void* bf16_shadow, void* stream) {
-    BVC_REQUIRE(params && grads && n >= 0, "op_sgd_step_segments: bad argument");
-    return launch_sgd_step_segments(params, grads, momentum_buf, n, seg_start, seg_group, blk_seg, nseg, groups, grad_scale, found_inf,
-                                    write_unscaled_grads, (bf16_t*)bf16_shadow, (hipStream_t)stream);
-}
-int bvc_op_adam_step_segments(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const int64_t* seg_start,
-                              const int32_t* seg_group, const int32_t* blk_seg, int nseg, const bvc_adam_groups* groups, float* state,
-                              double* hyper_scratch, const float* grad_scale, const float* found_inf, int write_unscaled_grads,
-                              void* bf16_shadow, void* stream) {
-    BVC_REQUIRE(params && grads && exp_avg && exp_avg_sq && n >= 0, "op_adam_step_segments: bad argument");
-    return launch_adam_step_segments(params, grads, exp_avg, exp_avg_sq, n, seg_start, seg_group, blk_seg, nseg, groups, state, hyper_scratch,
-                                     grad_scale, found_inf, write_unscaled_grads, (bf16_t*)bf16_shadow, (hipStream_t)stream);
-}
-int bvc_op_sgd_step_table(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,
-                          const int32_t* blk_seg, int nseg, int ngroups, const float* lr, const float* momentum, const float* dampening,
-                          const float* weight_decay, const int32_t* nesterov, const int32_t* first_step, const int32_t* maximize,
-                          float* group_table, const float* grad_scale, const float* found_inf, int write_unscaled_grads,
-                          void* bf16_shadow, void* stream) {
-    BVC_REQUIRE(params && grads && n >= 0, "op_sgd_step_table: bad argument");
-    return launch_sgd_step_table(params, grads, momentum_buf, n, seg_start, seg_group, blk_seg, nseg, ngroups, lr, momentum, dampening,
-                                 weight_decay, nesterov, first_step, maximize, group_table, grad_scale, found_inf, write_unscaled_grads,
-                                 (bf16_t*)bf16_shadow, (hipStream_t)stream);
-}
-int bvc_op_adam_step_table(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const int64_t* seg_start,
-                           const int32_t* seg_group, const int32_t* blk_seg, int nseg, int ngroups, const double* lr, const double* beta1,
-                           const double* beta2, const double* eps, const double* weight_decay, const int32_t* decoupled,
-                           const int32_t* maximize, float* state, float* group_table, const float* grad_scale, const float* found_inf,
-                           int write_unscaled_grads, void* bf16_shadow, void* stream) {
-    BVC_REQUIRE(params && grads && exp_avg && exp_avg_sq && n >= 0, "op_adam_step_table: bad argument");
-    return launch_adam_step_table(params, grads, exp_avg, exp_avg_sq, n, seg_start, seg_group, blk_seg, nseg, ngroups, lr, beta1, beta2, eps,
-                                  weight_decay, decoupled, maximize, state, group_table, grad_scale, found_inf, write_unscaled_grads,
-                                  (bf16_t*)bf16_shadow, (hipStream_t)stream);
-}
 int bvc_videomae_shadow(bvc_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {
     BVC_REQUIRE(c, "videomae_shadow: null context");
-    if (shadow_bf16) *shadow_bf16 = c->wbf;
-    if (numel) *numel = (int64_t)c->lay.total;
-    if (valid >= 0) c->shadow_valid = valid != 0;
-    return BVC_OK;
-}
-int bvc_op_nonfinite_check(const float* x, int64_t n, float* found_inf, void* stream) {
-    BVC_REQUIRE(x && found_inf && n >= 0, "op_nonfinite_check: bad argument");
-    return launch_nonfinite_check(x, (size_t)n, found_inf, (hipStream_t)stream);
-}
-int bvc_op_grad_norm_item_cap(void) { return BVC_GRAD_NORM_ITEM_CAP; }
-int bvc_op_grad_norm_chain(void) { return grad_norm_chain(); }
-int bvc_grad_norm_items_host(const int64_t* seg_start, const int32_t* seg_group, int nseg, bvc_norm_item* items, int64_t items_cap,
-                             int64_t* seg_first_item, int64_t* nitems) {
-    BVC_REQUIRE(nseg >= 0 && nitems && (nseg == 0 || (seg_start && seg_group)) && (items == nullptr || items_cap >= 0),
-                "grad_norm_items_host: bad argument");
-    return grad_norm_items_host(seg_start, seg_group, nseg, items, items_cap, seg_first_item, nitems);
-}
-int bvc_op_grad_sqnorm_items(const float* x, const bvc_norm_item* items, int64_t nitems, const int64_t* seg_first_item, int nseg,
-                             double* item_partial, float* seg_sq, float* total_sq, int as_norm, float* found_inf, void* stream) {
-    BVC_REQUIRE(x && total_sq && nitems >= 0, "op_grad_sqnorm_items: bad argument");
-    return launch_grad_sqnorm_items(x, items, nitems, seg_first_item, nseg, item_partial, seg_sq, total_sq, as_norm, found_inf,
-                                    (hipStream_t)stream);
-}
-int bvc_op_clip_finalize(const float* sq, int nranges, float max_norm, const float* grad_scale, float* out3, void* stream) {
-    BVC_REQUIRE(out3 && nranges >= 0 && (nranges == 0 || sq) && !(max_norm < 0.f) && max_norm == max_norm, "op_clip_finalize: bad argument");
-    return launch_clip_finalize(sq, nranges, max_norm, grad_scale, out3, (hipStream_t)stream);
-}
-int bvc_op_scale_by_dev(float* x, int64_t n, const float* coef, void* stream) {
-    BVC_REQUIRE(x && coef && n >= 0 && ((uintptr_t)x % 4) == 0, "op_scale_by_dev: bad argument");
-    return launch_scale_by_dev(x, (size_t)n, coef, (hipStream_t)stream);
-}
-int bvc_op_row_normalize(const float* f, void* fn_bf16, float* inv_norm, int n, int p, float eps, void* stream) {
-    BVC_REQUIRE(f && fn_bf16 && inv_norm, "op_row_normalize: null argument");
-    return launch_row_normalize(f, (bf16_t*)fn_bf16, inv_norm, n, p, eps, (hipStream_t)stream);
-}
-int bvc_op_row_normalize_bwd(const float* f, const float* inv_norm, const float* dfn, float* df, int n, int p, void* stream) {
-    BVC_REQUIRE(f && inv_norm && dfn && df, "op_row_normalize_bwd: null argument");
-    return launch_row_normalize_bwd(f, inv_norm, dfn, df, n, p, (hipStream_t)stream);
-}
-int bvc_op_nce_finalize(const float* partial, int ntiles, float inv_temperature, int64_t npos, float* loss, float* stats, void* stream) {
-    BVC_REQUIRE(partial && loss && stats && ntiles > 0 && npos > 0, "op_nce_finalize: bad argument");
-    return launch_nce_finalize(partial, ntiles, inv_temperature, (double)npos, loss, stats, (hipStream_t)stream);
-}
-int bvc_op_cast_bf16(const float* in, void* out, int64_t n, void* stream) {
-    BVC_REQUIRE(in && out && n >= 0, "op_cast_bf16: bad argument");
-    return launch_cast_bf16(in, (bf16_t*)out, (size_t)n, (hipStream_t)stream);
-}
-int bvc_op_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, void* stream) {
-    BVC_REQUIRE(mask && vis_idx && msk_idx && status, "op_mask_index: null argument");
-    return launch_mask_index(mask, B, L, nvis, nmask, vis_idx, msk_idx, status, (hipStream_t)stream);
-}
-int bvc_op_dual_mask_index(const uint8_t* mask, const uint8_t* decode_mask, int B, int L, int nvis, int ndec, int* vis_idx, int* dec_idx,
-                           int* status, void* stream) {
-    BVC_REQUIRE(mask && decode_mask && vis_idx && dec_idx && status, "op_dual_mask_index: null argument");
-    BVC_REQUIRE(B >= 1 && L >= 1 && nvis >= 1 && nvis < L && ndec >= 1 && ndec <= L - nvis, "op_dual_mask_index: bad counts (L %d, nvis %d, ndec %d)", L, nvis, ndec);
-    return launch_dual_mask_index(mask, decode_mask, B, L, nvis, ndec, vis_idx, dec_idx, status, (hipStream_t)stream);
-}
-int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A, int B, int nvis, int T, int C, int H, int W, int ts,
-                          int ps, void* stream) {
-    BVC_REQUIRE(clip && vis_idx && A, "op_gather_patches: null argument");
-    return launch_gather_patches(pixels_f32(clip), vis_idx, (bf16_t*)A, B, nvis, PatchGeom{T, C, H, W, ts, ps}, (hipStream_t)stream);
-}
-int bvc_op_gather_patches_mix(const void* clip, const bvc_pixel_format* fmt, const int* idx, void* A, const bvc_clip_mix* mix, int B, int n,
-                              int T, int C, int H, int W, int ts, int ps, void* stream) {
-    BVC_REQUIRE(clip && idx && A && mix, "op_gather_patches_mix: null argument");
-    BVC_REQUIRE(T >= 1 && C >= 1 && H >= 1 && W >= 1 && ts >= 1 && ps >= 1 && T % ts == 0 && H % ps == 0 && W % ps == 0,
-                "op_gather_patches_mix: bad geometry");
-    PixelSrc px;
-    TRY(pixel_src(clip, fmt, C, &px));
-    return launch_gather_patches_mix(px, idx, (bf16_t*)A, B, n, PatchGeom{T, C, H, W, ts, ps}, mix, (hipStream_t)stream);
-}
-int bvc_op_pixel_labels(const float* clip, const int* msk_idx, float* labels, int B, int nmask, int T, int C, int H, int W, int ts,
-                        int ps, int norm_pix, void* stream) {
-    BVC_REQUIRE(clip && msk_idx && labels, "op_pixel_labels: null argument");
-    return launch_labels(pixels_f32(clip), msk_idx, labels, B, nmask, PatchGeom{T, C, H, W, ts, ps}, norm_pix, (hipStream_t)stream);
+    return c->shadow.query(valid, shadow_bf16, numel);
 }
 
 }  // extern "C"

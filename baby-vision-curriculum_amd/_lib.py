@@ -201,6 +201,9 @@ SYMBOLS = {
                                           c_void_p, c_int, c_int, ctypes.POINTER(BranchDropC), c_int, c_int, c_void_p]),
     "bvc_op_dropout_mask": (c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "bvc_dropout_mask_host": (c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "bvc_op_clip_transform_workspace": (c_int64, [c_int, c_int, c_int]),
+    "bvc_op_clip_transform": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bvc_clip_transform_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "bvc_videomae_cls_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_encoder_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_cls_set_mix": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

@@ -299,6 +299,57 @@ int bvc_op_dropout_mask(uint64_t seed, uint64_t offset, int layer, int branch, i
 int bvc_dropout_mask_host(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Clip transforms on uint8 frames: resize, crop, flip, colour jitter and grayscale, between the upload of the loader's frames and
+ * the model.  Replaces, frame for frame, what the reference's loaders run on the host through torchvision / PIL:
+ * Resize + CenterCrop (pretraining/generative/homeview.py:227-231) and RandomResizedCrop, RandomApply([ColorJitter]), RandomGrayscale,
+ * RandomHorizontalFlip (pretraining/predictive/homeview.py:118-178, pretraining/contrastive/homeview.py:120-181).  The host draws one
+ * bvc_frame_aug per OUTPUT frame; the library applies the table.
+ *   src              index of the source frame ([F_src][3][Hs][Ws] uint8): several entries may name one frame (two views, repeats)
+ *   x0, y0, w, h     region of the source frame
+ *   Hr, Wr           size the region is resized to: antialiased bilinear (triangle filter of support max(1, w / Wr), pixel centres at
+ *                    i + 0.5, taps clipped to the region and renormalised), a horizontal pass rounded half-up to uint8 and then a
+ *                    vertical pass rounded half-up to uint8, with the weights in the fixed point of torch's uint8 path: bit for
+ *                    bit what F.interpolate(uint8, mode="bilinear", antialias=True) gives on the region (PIL's Image.resize(BILINEAR)
+ *                    does the same at a finer weight precision); a region of the resized size is copied bit for bit
+ *   oy, ox           where the Ho x Wo output window sits in the resized image
+ *                    (RandomResizedCrop: region = the crop box, (Hr, Wr) = (Ho, Wo), window at 0;  Resize + CenterCrop: region = the
+ *                    whole frame, short side -> S, window centred)
+ *   flip             non-zero mirrors the output columns
+ *   nops, order      number of ColorJitter stages (0 .. 4) and their order: stage i is op (order >> 4 i) & 15, 0 = brightness,
+ *                    1 = contrast, 2 = saturation, 3 = hue; each op at most once
+ *   factor[op]       the op's factor: the blend ratio of brightness / contrast / saturation (>= 0), the hue shift in [-0.5, 0.5]
+ *   gray             non-zero: a grayscale stage (three equal channels) after the jitter stages
+ * Every colour stage is f32 arithmetic on the previous stage's uint8 values, rounded as torchvision's tensor functions round uint8
+ * images: blend ratio * a + (1 - ratio) * b, clamped and truncated (b = 0, the frame's mean gray, the pixel's gray); gray =
+ * trunc(0.2989 r + 0.587 g + 0.114 b); hue through float HSV and back with * (255 + 1 - 1e-3), truncated.  The contrast mean is the
+ * mean of the truncated gray of the whole output frame as it stands when that stage runs, from an integer sum: the same bits on every
+ * run and in either deterministic mode.
+ * bvc_op_clip_transform: src_dev / table_dev / out_dev ([F_out][3][Ho][Wo] uint8, i.e. [B][T][C][H][W]) are device memory;
+ * table_host is the same table in host memory (the host drew it), read during the call only: the entries are validated there, without
+ * a device sync, and it tells the call whether any frame needs the second pass.  workspace_dev holds
+ * bvc_op_clip_transform_workspace bytes, 4-byte aligned (per-frame filter precisions, per-tile gray sums).  Two launches for a table
+ * without contrast stages (the precisions; resize + the colour stages), three otherwise; no atomics.  BVC_ERR_INVALID with a message for channels != 3, an empty region or
+ * one outside the source, a window outside the resized image, a shrink factor above BVC_AUG_MAX_SCALE per axis, a resized edge above 16384, an unknown op or a
+ * factor out of range.
+ * bvc_clip_transform_host: the same arithmetic compiled for the host (csrc/augment.h), on host memory; needs no GPU. */
+#define BVC_AUG_MAX_SCALE 16
+typedef struct bvc_frame_aug {
+    int32_t src;
+    int32_t x0, y0, w, h;
+    int32_t Hr, Wr;
+    int32_t oy, ox;
+    int32_t flip;
+    int32_t nops, order;
+    float factor[4];
+    int32_t gray;
+} bvc_frame_aug; /* 68 bytes */
+int64_t bvc_op_clip_transform_workspace(int F_out, int Ho, int Wo);
+int bvc_op_clip_transform(const uint8_t* src_dev, int F_src, int channels, int Hs, int Ws, const bvc_frame_aug* table_host,
+                          const bvc_frame_aug* table_dev, int F_out, int Ho, int Wo, uint8_t* out_dev, void* workspace_dev, void* stream);
+int bvc_clip_transform_host(const uint8_t* src, int F_src, int channels, int Hs, int Ws, const bvc_frame_aug* table, int F_out, int Ho,
+                            int Wo, uint8_t* out);
+
+/* ------------------------------------------------------------------------------------------------
  * JEPA encoder and predictor (pretraining/predictive/vision_transformer.py).  Same conventions as above: flat f32
  * parameter / gradient buffers whose entries carry the reference's state-dict keys (pos_embed, patch_embed.proj.*,
  * blocks.N.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}.*, norm.* / mask_token, predictor_pos_embed,

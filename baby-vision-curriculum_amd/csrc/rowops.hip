@@ -201,19 +201,31 @@ __global__ __launch_bounds__(256) void ln_bwd_gate_kernel(const bf16_t* __restri
     ln_bwd_body<RPB, LPR, NC, true>(dy, x, rm, mean, rstd, gamma, dres, accumulate, dres_bf, part, M, D, gate, 0);
 }
 
-// dgamma[c] += sum_b part[b][0][c], dbeta[c] += sum_b part[b][1][c]; grid (ceil(2D/256), ceil(nblk/16))
+// dgamma[c] += sum_b part[b][0][c], dbeta[c] += sum_b part[b][1][c]; grid (ceil(2D/256), ceil(nblk/ROWS))
+// ROWS = 16: one chain of 16 partial rows per workgroup, then one atomic.  ROWS = 64 (more than kLnReduceWide partial rows): four such
+// chains added pairwise, then one atomic - with 16 rows per workgroup the 2048 partial rows of a large LayerNorm ended in a chain of
+// 128 f32 atomics per column, whose rounding error (3 - 4 x that of torch's reduction, varying with the arrival order) sat at the
+// bar of tests/test_gpu_rowops.py; at most 32 atomics leave it at about half of that
+constexpr int kLnReduceWide = 256;
+template <int ROWS>
 __global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __restrict__ part, int nblk, int D,
                                                               float* __restrict__ dgamma, float* __restrict__ dbeta) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= 2 * D) return;
-    const int b0 = blockIdx.y * 16, b1 = min(nblk, b0 + 16);
-    float v[16];
+    const int b0 = blockIdx.y * ROWS, b1 = min(nblk, b0 + ROWS);
+    float s[ROWS / 16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = b0 + i < b1 ? part[(size_t)(b0 + i) * 2 * D + c] : 0.f;   // 16 loads in flight
-    float s = 0.f;
+    for (int j = 0; j < ROWS / 16; ++j) {
+        float v[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) s += v[i];
-    atomicAdd(c < D ? dgamma + c : dbeta + (c - D), s);
+        for (int i = 0; i < 16; ++i) v[i] = b0 + 16 * j + i < b1 ? part[(size_t)(b0 + 16 * j + i) * 2 * D + c] : 0.f;   // 16 loads in flight
+        s[j] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[j] += v[i];
+    }
+    float t = s[0];
+    if constexpr (ROWS == 64) t = (s[0] + s[1]) + (s[2] + s[3]);
+    atomicAdd(c < D ? dgamma + c : dbeta + (c - D), t);
 }
 
 // Deterministic mode (options().deterministic): column c of nrows partial rows of W floats, added in row order onto its output -
@@ -329,9 +341,20 @@ __device__ __forceinline__ void colsum_f32_body(const float* __restrict__ X, Row
     const int col = (blockIdx.x * 64 + lane) * 4;
     f32x4 acc = {0, 0, 0, 0};
     const int r0 = blockIdx.y * RB, r1 = min(M, r0 + RB);
-    if (col < D)
-        for (int m = r0 + wave; m < r1; m += 4)
+    if (col < D) {
+        // four partial sums per lane, added pairwise at the end: chains of 16 rows instead of one of 64 (a serial f32 sum of 64 rows
+        // measured 4.2 x the error of torch's sum at M = 256), and four loads in flight
+        f32x4 a1 = {0, 0, 0, 0}, a2 = {0, 0, 0, 0}, a3 = {0, 0, 0, 0};
+        int m = r0 + wave;
+        for (; m + 12 < r1; m += 16) {
             acc += *reinterpret_cast<const f32x4*>(X + (size_t)map_row(m, rm) * D + col);
+            a1 += *reinterpret_cast<const f32x4*>(X + (size_t)map_row(m + 4, rm) * D + col);
+            a2 += *reinterpret_cast<const f32x4*>(X + (size_t)map_row(m + 8, rm) * D + col);
+            a3 += *reinterpret_cast<const f32x4*>(X + (size_t)map_row(m + 12, rm) * D + col);
+        }
+        for (; m < r1; m += 4) acc += *reinterpret_cast<const f32x4*>(X + (size_t)map_row(m, rm) * D + col);
+        acc = (acc + a1) + (a2 + a3);
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e) red[wave][lane * 4 + e] = acc[e];
     __syncthreads();
@@ -1798,7 +1821,10 @@ int launch_ln_param_reduce(const float* part, int nblk, int D, float* dgamma, fl
         }
         return launch_det_rows_reduce(part, nblk, 2 * D, D, dgamma, dbeta, mid, s);
     }
-    hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * D + 255) / 256, (nblk + 15) / 16), dim3(256), 0, s, part, nblk, D, dgamma, dbeta);
+    if (nblk > kLnReduceWide)
+        hipLaunchKernelGGL(ln_param_reduce_kernel<64>, dim3((2 * D + 255) / 256, (nblk + 63) / 64), dim3(256), 0, s, part, nblk, D, dgamma, dbeta);
+    else
+        hipLaunchKernelGGL(ln_param_reduce_kernel<16>, dim3((2 * D + 255) / 256, (nblk + 15) / 16), dim3(256), 0, s, part, nblk, D, dgamma, dbeta);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

@@ -122,11 +122,14 @@ int param_info(const ParamTable& t, int index, char* name, int name_cap, int64_t
 
 int refuse_operand_extent(const char* who, int max_batch, size_t tokens_per_clip, size_t bf16_columns, const char* side_name) {
     const size_t per_clip = tokens_per_clip * bf16_columns * 2, bytes = (size_t)max_batch * per_clip;
-    if (bytes < 0xFFFFFFF0ull) return BVC_OK;
+    // (a weight-gradient product walks its token rows 64 at a time: the up to 63 rows past the last token must keep their 32-bit byte
+    //  offsets below 2^32 as well, or they would wrap into the operand instead of reading as zero - launch_gemm refuses such a product)
+    const size_t limit = 0x100000000ull - operand_tail_bytes(bf16_columns);
+    if (bytes <= limit) return BVC_OK;
     char side[32] = "";
     if (side_name) snprintf(side, sizeof(side), "the %s's ", side_name);
     set_error("%s: max_batch %d exceeds the 4 GiB operand extent: %s%zu tokens x %zu bf16 columns are %.2f GiB; at most %zu clips", who, max_batch,
-              side, (size_t)max_batch * tokens_per_clip, bf16_columns, bytes / 1073741824.0, (size_t)(0xFFFFFFEFull / per_clip));
+              side, (size_t)max_batch * tokens_per_clip, bf16_columns, bytes / 1073741824.0, limit / per_clip);
     return BVC_ERR_INVALID;
 }
 

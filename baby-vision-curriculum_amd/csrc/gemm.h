@@ -69,6 +69,14 @@ int det_scratch_release();
 struct DryRun { bool on = false; char name[160] = ""; };
 DryRun& dry_run();
 
+// A TN product walks its K rows (of ld elements) 64 at a time; the rows past K in the last step read as zero only because their byte
+// offsets lie past a_bytes / b_bytes.  The kernels form those offsets in 32 bits (gemm_tile.h stage_tile), so roundup64(K) rows plus one
+// tile of columns must end below 2^32 bytes, or the surplus rows wrap to small offsets INSIDE the operand and real data joins the sum.
+// launch_gemm refuses a product outside tn_tail_ok; the contexts keep every token count they accept inside it (operand_tail_bytes
+// is what the up to 63 surplus rows and the columns add to a [tokens][columns] bf16 operand).
+constexpr size_t operand_tail_bytes(size_t bf16_columns) { return 64 * bf16_columns * 2 + 1024; }
+constexpr bool tn_tail_ok(int K, int ld) { return K % 64 == 0 || ((size_t)K + 63) / 64 * 64 * (size_t)ld * 2 + 1024 <= 0x100000000ull; }
+
 // Launch 1..4 independent problems of the same layout as ONE grid (grouped GEMM) on `stream`.
 // tile_cfg: -1 = pick from the tile count; 0 = 128x128, 1 = 128x64, 2 = 64x64.
 // stages: -1 = pick from the grid size; 2..4 = LDS ring depth (K-steps of LDS-DMA in flight + 1).

@@ -510,6 +510,10 @@ int launch_gemm(const GemmProblem* probs, int nprob, GemmLayout layout, int tile
         BVC_REQUIRE(p.lda % 8 == 0 && p.ldb % 8 == 0 && p.ldc % 8 == 0, "launch_gemm: leading dims must be multiples of 8");
         if (layout != GEMM_TN) BVC_REQUIRE(p.K % 64 == 0, "launch_gemm: K=%d must be a multiple of 64 for k-contiguous operands", p.K);
         if (layout == GEMM_TN) BVC_REQUIRE(p.M % 8 == 0, "launch_gemm: TN needs M %% 8 == 0 (M=%d)", p.M);
+        if (layout == GEMM_TN)
+            BVC_REQUIRE(tn_tail_ok(p.K, p.lda) && tn_tail_ok(p.K, p.ldb),
+                        "launch_gemm: TN with K=%d (no multiple of 64), lda=%d, ldb=%d: the 32-bit byte offsets of the rows past K in the last K step "
+                        "would wrap past 4 GiB into the operand instead of reading as zero", p.K, p.lda, p.ldb);
         BVC_REQUIRE(p.split_k >= 1, "launch_gemm: split_k must be >= 1");
         if (p.rowsum) BVC_REQUIRE(layout == GEMM_TN, "launch_gemm: rowsum (bias gradient) is fused into TN products only");
         if (p.split_k > 1)

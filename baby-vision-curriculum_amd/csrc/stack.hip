@@ -72,7 +72,8 @@ int alloc_stack(Arena& a, Stack& s, int D, int I, int H, int nlayers, float eps,
     // operand extents travel as 32-bit byte counts (bvc_gemm_desc.a_bytes / b_bytes, buffer descriptors): the widest bf16
     // activation of a layer has to stay below 4 GiB (VideoMAE-base decoder: ~890 clips per GPU; from 2 GiB on - 445 clips - the
     // 256-row persistent kernel, which marks dropped loads with offset bit 31, hands the product to the 128 x 128 kernels)
-    BVC_REQUIRE(M * std::max<size_t>(3 * Da, (size_t)I) * 2 < 0xFFFFFFF0ull,
+    // (... and the last 64-row step of a weight gradient over fewer tokens than M must not wrap either: gemm.h tn_tail_ok)
+    BVC_REQUIRE(M * std::max<size_t>(3 * Da, (size_t)I) * 2 + operand_tail_bytes(std::max<size_t>(3 * Da, (size_t)I)) <= 0x100000000ull,
                 "stack: %zu tokens x %zu columns of bf16 exceed the 4 GiB operand extent; use a smaller per-GPU batch", M, std::max<size_t>(3 * Da, (size_t)I));
     if (s.hdp != s.hd) {
         TRY(a.alloc(&s.wqkv_pad, 3 * Da * D));

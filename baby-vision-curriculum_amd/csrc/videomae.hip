@@ -451,7 +451,7 @@ int bvc_videomae_encoder_create(const bvc_videomae_config* cfg, int max_batch, b
     const PatchGeom pg = patch_geom(*cfg);
     const size_t M = (size_t)max_batch * seq_len(pg);
     const int D = cfg->hidden_size, I = cfg->intermediate_size, H = cfg->num_attention_heads;
-    BVC_REQUIRE(M * (size_t)std::max(I, patch_dim(pg)) * 2 < 0xffffffffull, "encoder_create: max_batch %d needs operands above 4 GiB", max_batch);
+    BVC_REQUIRE(M * (size_t)std::max(I, patch_dim(pg)) * 2 + operand_tail_bytes((size_t)std::max(I, patch_dim(pg))) <= 0x100000000ull, "encoder_create: max_batch %d needs operands above 4 GiB", max_batch);
     bvc_encoder_ctx* c = new bvc_encoder_ctx();
     Making guard{[&] { bvc_videomae_encoder_destroy(c); }};
     c->cfg = *cfg;

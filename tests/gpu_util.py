@@ -9,7 +9,8 @@ import __graft_entry__ as ge
 bvc = ge.load_package()
 L = bvc._lib
 NT, NN, TN = 0, 1, 2
-EPI = dict(F32=0, BF16=1, GELU=2, RESID=3, POS=4, E2D=5, LOSS=6, DGELU=7, F32_BF16=8, RESID_LN=13, DLN=14)
+EPI = dict(F32=0, BF16=1, GELU=2, RESID=3, POS=4, E2D=5, LOSS=6, DGELU=7, F32_BF16=8, RESID_LN=13, DLN=14,
+           RELU=9, DRELU=10, NCE=11, NCE_BWD=12, RESID_GATE=15)
 
 
 def stream():
@@ -55,6 +56,15 @@ def gemm_desc(A, B, M, N, K, epi, C, ldc=None, lda=None, ldb=None, alpha=1.0, al
 def run_gemm(descs, layout, tile_cfg=-1, stages=-1):
     arr = (L.GemmDesc * len(descs))(*descs)
     L.check(L.lib().bvc_op_gemm(arr, len(descs), layout, tile_cfg, stages, stream()), "bvc_op_gemm")
+
+
+def gemm_kernel_name(descs, layout, tile_cfg=-1, stages=-1):
+    """The instantiation bvc_op_gemm would run for these problems, as rocprofv3 names it (bvc_op_gemm_kernel; nothing is launched)."""
+    descs = list(descs) if isinstance(descs, (list, tuple)) else [descs]
+    arr = (L.GemmDesc * len(descs))(*descs)
+    buf = ctypes.create_string_buffer(160)
+    L.check(L.lib().bvc_op_gemm_kernel(arr, len(descs), layout, tile_cfg, stages, buf, 160), "bvc_op_gemm_kernel")
+    return buf.value.decode()
 
 
 def rel_err(a, b):

@@ -204,6 +204,10 @@ SYMBOLS = {
     "bvc_op_clip_transform_workspace": (c_int64, [c_int, c_int, c_int]),
     "bvc_op_clip_transform": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "bvc_clip_transform_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "bvc_aug_blur_weights": (c_int, [c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "bvc_op_clip_post_workspace": (c_int64, [c_int, c_int, c_int]),
+    "bvc_op_clip_post": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bvc_clip_post_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "bvc_videomae_cls_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_encoder_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_cls_set_mix": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

@@ -1,4 +1,4 @@
-// Clip transforms (include/bvc.h, bvc_frame_aug): the arithmetic that the kernels of augment.hip and the host twin share.
+// Clip transforms (include/bvc.h, bvc_frame_aug and bvc_frame_post): the arithmetic that the kernels of augment.hip and the host twins share.
 //
 // Geometry, per output frame: region (x0, y0, w, h) of the source frame -> antialiased bilinear resize to (Hr, Wr) -> the Ho x Wo
 // window at (oy, ox) -> optional mirror of the columns.  The resize is separable and runs as torch's upsample_bilinear2d_aa and PIL's
@@ -292,6 +292,118 @@ inline void clip_transform_host(const uint8_t* src, int F_src, int Hs, int Ws, c
                 }
                 const int jj = e.flip ? Wo - 1 - j : j;
                 for (int c = 0; c < 3; ++c) of[((size_t)c * Ho + r) * Wo + jj] = (uint8_t)p[c];
+            }
+    }
+}
+
+// ---------------------------------------------------------------- post stage: blur, gray, rotation (bvc_frame_post)
+// Blur is Pillow's GaussianBlur: three box passes along the rows, then three along the columns, every pass rounded to uint8, taps
+// beyond the frame reading the edge value of that pass's input.  One pass, in uint32 (the largest value is 255 * 2^24 + 2^23):
+//     out[x] = (ww * sum_{|i| <= r} in[x + i] + fw * (in[x - r - 1] + in[x + r + 1]) + 2^23) >> 24
+// Rotation is PIL's Image.rotate(NEAREST, expand=False, fillcolor=0): output pixel (x, y) copies in[yin][xin],
+//     xin = (a2 + a1 y + a0 x) >> 16,  yin = (a5 + a4 y + a3 x) >> 16     (arithmetic shifts), and is 0 when that lies outside.
+typedef bvc_frame_post Post;
+constexpr int kMaxBoxRadius = 3;        // what BVC_AUG_MAX_BLUR_RADIUS gives
+constexpr int kMaxRotEdge = 4096;       // with the coefficient bounds below every intermediate of the map stays inside int32
+constexpr int kMaxRotLinear = 65537, kMaxRotOffset = 1 << 30;
+
+// Pillow's _gaussian_blur_radius and the weights of ImagingLineBoxBlur8, with their types: f32 except where Pillow's own expression
+// is evaluated in f64 (the square root and the floor), and an f32 division for ww.
+inline int blur_weights(float radius, int32_t* r, uint32_t* ww, uint32_t* fw) {
+    if (!(radius >= 0.f) || radius > BVC_AUG_MAX_BLUR_RADIUS) return -1;
+    const float sigma2 = radius * radius / 3;
+    const float L = (float)sqrt(12.0 * sigma2 + 1.0);
+    const float l = (float)floor((L - 1.0) / 2.0);
+    float a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2);
+    a /= 6 * (sigma2 - (l + 1) * (l + 1));
+    const float fr = l + a;
+    const int ri = (int)fr;
+    const uint32_t w = (uint32_t)((float)(1 << 24) / (fr * 2 + 1));
+    *r = ri;
+    *ww = w;
+    *fw = ((1u << 24) - (uint32_t)(2 * ri + 1) * w) / 2;
+    return 0;
+}
+
+// An entry whose blur cannot leave uint32 or the halo: the radius forced into [-1, 3], weights above 2^24 in total mean "no blur".
+// The identity on entries that invalid_post() accepts.  rot[] needs no clamp: every gather tests its source index first.
+AUG_HD Post post_sanitize(Post p) {
+    p.blur_r = p.blur_r < -1 ? -1 : (p.blur_r > kMaxBoxRadius ? kMaxBoxRadius : p.blur_r);
+    if (p.blur_r >= 0 && (uint64_t)(2 * p.blur_r + 1) * p.blur_ww + 2 * (uint64_t)p.blur_fw > (1u << 24)) p.blur_r = -1;
+    return p;
+}
+
+inline bool invalid_post(const Post& p, int f, int H, int W, char* msg, size_t cap) {
+#define AUG_REFUSE(cond, ...) do { if (cond) { snprintf(msg, cap, __VA_ARGS__); return true; } } while (0)
+    AUG_REFUSE(p.blur_r < -1 || p.blur_r > kMaxBoxRadius, "clip_post: frame %d has blur_r %d (-1 .. %d)", f, p.blur_r, kMaxBoxRadius);
+    AUG_REFUSE(p.blur_r >= 0 && (uint64_t)(2 * p.blur_r + 1) * p.blur_ww + 2 * (uint64_t)p.blur_fw > (1u << 24),
+               "clip_post: frame %d: blur weights (%d x %u + 2 x %u) exceed 2^24", f, 2 * p.blur_r + 1, p.blur_ww, p.blur_fw);
+    if (p.rotate) {
+        AUG_REFUSE(H > kMaxRotEdge || W > kMaxRotEdge, "clip_post: frame %d rotates a %d x %d frame (edges up to %d)", f, W, H, kMaxRotEdge);
+        for (int i = 0; i < 6; ++i) {
+            const int64_t v = p.rot[i] < 0 ? -(int64_t)p.rot[i] : (int64_t)p.rot[i];
+            AUG_REFUSE(v > (i % 3 == 2 ? kMaxRotOffset : kMaxRotLinear), "clip_post: frame %d: rot[%d] = %d out of range (|a| <= %d)", f, i,
+                       p.rot[i], i % 3 == 2 ? kMaxRotOffset : kMaxRotLinear);
+        }
+    }
+#undef AUG_REFUSE
+    return false;
+}
+
+// source pixel of output pixel (x, y); false = outside the frame.  Unsigned arithmetic: an entry that no call accepts wraps
+// instead of overflowing, and the range test makes any result safe.
+AUG_HD bool rot_source(const int32_t* a, int x, int y, int H, int W, int* xin, int* yin) {
+    const int32_t xi = (int32_t)((uint32_t)a[2] + (uint32_t)a[1] * (uint32_t)y + (uint32_t)a[0] * (uint32_t)x) >> 16;
+    const int32_t yi = (int32_t)((uint32_t)a[5] + (uint32_t)a[4] * (uint32_t)y + (uint32_t)a[3] * (uint32_t)x) >> 16;
+    *xin = xi;
+    *yin = yi;
+    return xi >= 0 && xi < W && yi >= 0 && yi < H;
+}
+
+AUG_HD uint32_t box_u8(uint32_t inner, uint32_t far, uint32_t ww, uint32_t fw) { return (ww * inner + fw * far + (1u << 23)) >> 24; }
+
+// one box pass over n samples `stride` apart
+inline void box_line_host(const uint8_t* in, uint8_t* out, int n, size_t stride, int r, uint32_t ww, uint32_t fw) {
+    auto at = [&](int x) { return (uint32_t)in[(size_t)(x < 0 ? 0 : (x > n - 1 ? n - 1 : x)) * stride]; };
+    for (int x = 0; x < n; ++x) {
+        uint32_t inner = 0;
+        for (int i = -r; i <= r; ++i) inner += at(x + i);
+        out[(size_t)x * stride] = (uint8_t)box_u8(inner, at(x - r - 1) + at(x + r + 1), ww, fw);
+    }
+}
+
+// The post stage on host memory, whole frames at a time: blur, then gray, then rotation.
+inline void clip_post_host(const uint8_t* in, const Post* table, int F, int H, int W, uint8_t* out) {
+    const size_t plane = (size_t)H * W;
+    std::vector<uint8_t> a(3 * plane), b(3 * plane);
+    for (int f = 0; f < F; ++f) {
+        const Post p = post_sanitize(table[f]);
+        const uint8_t* inf = in + (size_t)f * 3 * plane;
+        uint8_t* of = out + (size_t)f * 3 * plane;
+        for (size_t i = 0; i < 3 * plane; ++i) a[i] = inf[i];
+        if (p.blur_r >= 0) {
+            for (int pass = 0; pass < 3; ++pass) {
+                for (int c = 0; c < 3; ++c)
+                    for (int y = 0; y < H; ++y) box_line_host(&a[c * plane + (size_t)y * W], &b[c * plane + (size_t)y * W], W, 1, p.blur_r, p.blur_ww, p.blur_fw);
+                a.swap(b);
+            }
+            for (int pass = 0; pass < 3; ++pass) {
+                for (int c = 0; c < 3; ++c)
+                    for (int x = 0; x < W; ++x) box_line_host(&a[c * plane + x], &b[c * plane + x], H, (size_t)W, p.blur_r, p.blur_ww, p.blur_fw);
+                a.swap(b);
+            }
+        }
+        if (p.gray)
+            for (size_t i = 0; i < plane; ++i) {
+                int px[3] = {a[i], a[plane + i], a[2 * plane + i]};
+                to_gray(px);
+                a[i] = a[plane + i] = a[2 * plane + i] = (uint8_t)px[0];
+            }
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) {
+                int xin = x, yin = y;
+                const bool inside = p.rotate ? rot_source(p.rot, x, y, H, W, &xin, &yin) : true;
+                for (int c = 0; c < 3; ++c) of[c * plane + (size_t)y * W + x] = inside ? a[c * plane + (size_t)yin * W + xin] : (uint8_t)0;
             }
     }
 }

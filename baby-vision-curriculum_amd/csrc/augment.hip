@@ -1,4 +1,5 @@
-// Clip transforms on uint8 frames (include/bvc.h, bvc_frame_aug; arithmetic in augment.h): resize + crop + flip + colour jitter.
+// Clip transforms on uint8 frames (include/bvc.h, bvc_frame_aug; arithmetic in augment.h): resize + crop + flip + colour jitter, and
+// the post stage on their output (bvc_frame_post): blur, gray, rotation - its two kernels are described where they stand, below.
 //
 // clip_precision_kernel  one workgroup per output frame: the fixed-point precision of its two axes (the largest tap weight over the
 //                      whole resized axis decides it) into the head of the workspace.
@@ -208,6 +209,263 @@ static int check_call(const char* who, const void* src, int F_src, int channels,
     return BVC_OK;
 }
 
+// ---------------------------------------------------------------- post stage (bvc_frame_post)
+// clip_blur_kernel    one workgroup per 32 x 64 tile of one frame, three channels.  The tile plus a halo of 3 (r + 1) pixels (rounded up
+//                     to whole words along the rows) sits in LDS as REPLICATE-PADDED words of four pixels: positions beyond the frame
+//                     hold the frame's edge value, and every pass computes a position beyond the frame as its nearest position inside,
+//                     so the padding is again the edge value of the next pass's input - the per-pass clamp against the frame, with no
+//                     clamp in the inner loops.  Six passes ping-pong between two images; a row pass builds four outputs from three
+//                     words, a column pass from 2 r + 3 words of one column with two 16-bit sums per register.  Each pass is exact
+//                     r + 1 pixels further inside the region than its input, hence the halo.  Gray, then the store, whole words
+//                     where the planes allow.  A frame without blur has no halo and no pass: its workgroups copy (or gray) the tile.
+// clip_rotate_kernel  a gather: four output pixels of a plane per thread, three channels, the map stepped from pixel to pixel,
+//                     whole-word stores where the planes allow; frames that do not rotate are copied.
+constexpr int kBlurW = 64, kBlurH = 32;              // output tile
+constexpr int kBlurHalo = 3 * (kMaxBoxRadius + 1);   // 12: three passes per direction
+constexpr int kBlurDw = (kBlurW + 2 * kBlurHalo) / 4, kBlurRows = kBlurH + 2 * kBlurHalo;      // 22 words x 56 rows per channel
+static_assert(kBlurHalo % 4 == 0 && kBlurW % 4 == 0, "the padded region is made of whole words");
+
+// One pass's rounding with 24-bit multiplies (full rate; the 32-bit one is not).  The kernel runs the passes only for ww < 2^24 (ww = 2^24
+// is the identity: fw = 0 there), an accepted fw is at most 2^23 and a sum of taps at most 7 x 255; the products fit 32 bits.
+__device__ __forceinline__ uint32_t box24(uint32_t inner, uint32_t far, uint32_t ww, uint32_t fw) {
+    return (__umul24(ww, inner) + __umul24(fw, far) + (1u << 23)) >> 24;
+}
+// four outputs of a row pass from the words left of, at and right of them
+template <int R>
+__device__ __forceinline__ uint32_t box4_row(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t ww, uint32_t fw) {
+    uint32_t b[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        b[k] = (w0 >> (8 * k)) & 255u; b[4 + k] = (w1 >> (8 * k)) & 255u; b[8 + k] = (w2 >> (8 * k)) & 255u;
+    }
+    uint32_t o = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t inner = 0;
+#pragma unroll
+        for (int i = -R; i <= R; ++i) inner += b[4 + j + i];
+        o |= box24(inner, b[4 + j - R - 1] + b[4 + j + R + 1], ww, fw) << (8 * j);
+    }
+    return o;
+}
+// the same four outputs one by one from the bytes of the row, each centred on its nearest column inside the frame [xlo, xhi]
+// (region columns); every index is also held inside the row of `n` bytes
+template <int R>
+__device__ __forceinline__ uint32_t box4_row_edge(const uint8_t* row, int x0, int xlo, int xhi, int n, uint32_t ww, uint32_t fw) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int xc = min(max(x0 + j, xlo), xhi);
+        uint32_t inner = 0;
+#pragma unroll
+        for (int i = -R; i <= R; ++i) inner += row[min(max(xc + i, 0), n - 1)];
+        const uint32_t far = (uint32_t)row[min(max(xc - R - 1, 0), n - 1)] + (uint32_t)row[min(max(xc + R + 1, 0), n - 1)];
+        o |= box24(inner, far, ww, fw) << (8 * j);
+    }
+    return o;
+}
+// four outputs of a column pass: rows yc - R - 1 .. yc + R + 1 of one word column (`col` = its word in row 0, rows kBlurDw words apart)
+template <int R>
+__device__ __forceinline__ uint32_t box4_col(const uint32_t* col, int yc, int rows, uint32_t ww, uint32_t fw) {
+    uint32_t in_e = 0, in_o = 0, far_e = 0, far_o = 0;       // bytes 0 | 2 and bytes 1 | 3 as two 16-bit sums (at most 7 x 255)
+#pragma unroll
+    for (int i = -R - 1; i <= R + 1; ++i) {
+        const uint32_t w = col[min(max(yc + i, 0), rows - 1) * kBlurDw];
+        if (i == -R - 1 || i == R + 1) { far_e += w & 0x00FF00FFu; far_o += (w >> 8) & 0x00FF00FFu; }
+        else { in_e += w & 0x00FF00FFu; in_o += (w >> 8) & 0x00FF00FFu; }
+    }
+    return box24(in_e & 0xFFFFu, far_e & 0xFFFFu, ww, fw) | (box24(in_o & 0xFFFFu, far_o & 0xFFFFu, ww, fw) << 8) |
+           (box24(in_e >> 16, far_e >> 16, ww, fw) << 16) | (box24(in_o >> 16, far_o >> 16, ww, fw) << 24);
+}
+
+typedef uint32_t BlurImage[3][kBlurRows][kBlurDw];
+
+// word t + 256 of a plane of NDW words per row from word t, without a division
+template <int NDW>
+__device__ __forceinline__ void next_word(int& ry, int& d) {
+    d += 256 % NDW;
+    ry += 256 / NDW;
+    if (d >= NDW) { d -= NDW; ++ry; }
+}
+
+// One tile at box radius R (-1: no blur, no halo, no pass), so that the region's size divides by constants: load the padded region,
+// run the six passes (they start from img[0] and end there), gray, store.
+template <int R>
+__device__ __forceinline__ void blur_tile(BlurImage* img, const uint8_t* __restrict__ inf, uint8_t* __restrict__ of, int H, int W, int r0,
+                                          int c0, uint32_t ww, uint32_t fw, int gray, int vec, int tid) {
+    constexpr int hal = 3 * (R + 1), hal4 = (hal + 3) & ~3, dw0 = hal4 / 4;
+    constexpr int rows = kBlurH + 2 * hal, ndw = (kBlurW + 2 * hal4) / 4, tdw = kBlurW / 4;
+    static_assert(rows <= kBlurRows && ndw <= kBlurDw, "the region fits the image");
+    const int y_org = r0 - hal, x_org = c0 - hal4;            // frame position of the region's first row and column
+    const int xlo = -x_org, xhi = W - 1 - x_org, ylo = -y_org, yhi = H - 1 - y_org;      // the frame in region columns and rows
+    const size_t plane = (size_t)H * W;
+
+    // a thread's words of one plane are (ry, d) = (t / ndw, t % ndw) for t = tid, tid + 256, ...; every task covers the three channels
+    const int ry_first = tid / ndw, d_first = tid % ndw;
+    for (int ry = ry_first, d = d_first; ry < rows; next_word<ndw>(ry, d)) {
+        const int y = min(max(y_org + ry, 0), H - 1), x = x_org + 4 * d;
+        const uint8_t* src = inf + (size_t)y * W;
+        uint32_t v[3];
+        if (vec && x >= 0 && x + 3 < W) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = *reinterpret_cast<const uint32_t*>(src + (size_t)c * plane + x);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                v[c] = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[c] |= (uint32_t)src[(size_t)c * plane + min(max(x + k, 0), W - 1)] << (8 * k);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) img[0][c][ry][d] = v[c];
+    }
+    __syncthreads();
+    if constexpr (R >= 0) {
+        int cur = 0;
+        for (int pass = 0; pass < 3; ++pass) {
+            for (int ry = ry_first, d = d_first; ry < rows; next_word<ndw>(ry, d)) {
+                const bool inside = 4 * d >= xlo && 4 * d + 3 <= xhi;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const uint32_t* row = img[cur][c][ry];
+                    uint32_t o;
+                    if (inside) o = box4_row<R>(row[max(d - 1, 0)], row[d], row[min(d + 1, ndw - 1)], ww, fw);
+                    else o = box4_row_edge<R>(reinterpret_cast<const uint8_t*>(row), 4 * d, xlo, xhi, 4 * ndw, ww, fw);
+                    img[cur ^ 1][c][ry][d] = o;
+                }
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        // a column pass is exact R + 1 rows further inside than its input: only those rows are computed (and read by the next)
+        for (int pass = 0; pass < 3; ++pass) {
+            const int lo = (pass + 1) * (R + 1), n = (rows - 2 * lo) * tdw;
+            for (int t = tid; t < 3 * n; t += 256) {
+                const int c = (t >= n) + (t >= 2 * n), rem = t - c * n, ry = lo + rem / tdw, d = dw0 + rem % tdw;
+                img[cur ^ 1][c][ry][d] = box4_col<R>(&img[cur][c][0][d], min(max(ry, ylo), yhi), rows, ww, fw);
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+    }
+    for (int t = tid; t < kBlurH * tdw; t += 256) {
+        const int ry = t / tdw, dd = t % tdw;
+        const int y = r0 + ry, x = c0 + 4 * dd;
+        if (y >= H || x >= W) continue;
+        uint32_t w[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) w[c] = img[0][c][hal + ry][dw0 + dd];
+        if (gray) {
+            uint32_t g = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int px[3] = {(int)((w[0] >> (8 * k)) & 255u), (int)((w[1] >> (8 * k)) & 255u), (int)((w[2] >> (8 * k)) & 255u)};
+                g |= (uint32_t)gray_u8(px) << (8 * k);
+            }
+            w[0] = w[1] = w[2] = g;
+        }
+        if (vec) {          // W is a multiple of 4: the word lies inside the row
+#pragma unroll
+            for (int c = 0; c < 3; ++c) *reinterpret_cast<uint32_t*>(of + (size_t)c * plane + (size_t)y * W + x) = w[c];
+        } else {
+            const int n = min(4, W - x);
+            for (int c = 0; c < 3; ++c)
+                for (int k = 0; k < n; ++k) of[(size_t)c * plane + (size_t)y * W + x + k] = (uint8_t)(w[c] >> (8 * k));
+        }
+    }
+}
+
+// `vec`: every plane of `in` and `out` starts on a 4-byte boundary and W is a multiple of 4
+__global__ __launch_bounds__(256) void clip_blur_kernel(const uint8_t* __restrict__ in, const Post* __restrict__ table, int H, int W,
+                                                        uint8_t* __restrict__ out, int tiles_x, int tiles, int vec) {
+    __shared__ BlurImage img[2];
+    const int tid = threadIdx.x;
+    const int f = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const int r0 = (tile / tiles_x) * kBlurH, c0 = (tile % tiles_x) * kBlurW;
+    const Post p = post_sanitize(table[f]);
+    // -1 .. 3, the same in every thread of the workgroup; ww = 2^24 leaves fw = 0: every pass is the identity, as no blur is
+    const int r = p.blur_ww >= (1u << 24) ? -1 : p.blur_r;
+    const uint8_t* inf = in + (size_t)f * 3 * H * W;
+    uint8_t* of = out + (size_t)f * 3 * H * W;
+    switch (r) {
+        case 0: blur_tile<0>(img, inf, of, H, W, r0, c0, p.blur_ww, p.blur_fw, p.gray, vec, tid); break;
+        case 1: blur_tile<1>(img, inf, of, H, W, r0, c0, p.blur_ww, p.blur_fw, p.gray, vec, tid); break;
+        case 2: blur_tile<2>(img, inf, of, H, W, r0, c0, p.blur_ww, p.blur_fw, p.gray, vec, tid); break;
+        case 3: blur_tile<3>(img, inf, of, H, W, r0, c0, p.blur_ww, p.blur_fw, p.gray, vec, tid); break;
+        default: blur_tile<-1>(img, inf, of, H, W, r0, c0, 0u, 0u, p.gray, vec, tid); break;
+    }
+}
+
+// pixels 4 q .. 4 q + 3 of a frame's plane per thread; `vec` = the planes of `out` are 4-byte aligned and a multiple of 4 long
+__global__ __launch_bounds__(256) void clip_rotate_kernel(const uint8_t* __restrict__ in, const Post* __restrict__ table, int H, int W,
+                                                          uint8_t* __restrict__ out, int chunks, int vec) {
+    const int f = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+    const int plane = H * W;
+    const int q = (chunk * 256 + threadIdx.x) * 4;
+    if (q >= plane) return;
+    const Post p = table[f];
+    const uint8_t* inf = in + (size_t)f * 3 * plane;
+    uint8_t* of = out + (size_t)f * 3 * plane;
+    const int n = min(4, plane - q);
+    uint32_t w[3] = {0, 0, 0};
+    int y = q / W, x = q - y * W;
+    // rot_source's two sums, stepped: a0 and a3 per pixel, a1 and a4 per row, in the same wrapping arithmetic (so the same bits)
+    uint32_t row_x = (uint32_t)p.rot[2] + (uint32_t)p.rot[1] * (uint32_t)y, row_y = (uint32_t)p.rot[5] + (uint32_t)p.rot[4] * (uint32_t)y;
+    uint32_t sx = row_x + (uint32_t)p.rot[0] * (uint32_t)x, sy = row_y + (uint32_t)p.rot[3] * (uint32_t)x;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i < n) {
+            const int xin = p.rotate ? (int32_t)sx >> 16 : x, yin = p.rotate ? (int32_t)sy >> 16 : y;
+            if (xin >= 0 && xin < W && yin >= 0 && yin < H) {
+                const uint8_t* s = inf + (size_t)yin * W + xin;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) w[c] |= (uint32_t)s[(size_t)c * plane] << (8 * i);
+            }
+            sx += (uint32_t)p.rot[0]; sy += (uint32_t)p.rot[3];
+            if (++x == W) {
+                x = 0; ++y;
+                row_x += (uint32_t)p.rot[1]; row_y += (uint32_t)p.rot[4];
+                sx = row_x; sy = row_y;
+            }
+        }
+    }
+    if (vec) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<uint32_t*>(of + (size_t)c * plane + q) = w[c];
+    } else {
+        for (int c = 0; c < 3; ++c)
+            for (int i = 0; i < n; ++i) of[(size_t)c * plane + q + i] = (uint8_t)(w[c] >> (8 * i));
+    }
+}
+
+static int blur_tiles(int H, int W) { return ((H + kBlurH - 1) / kBlurH) * ((W + kBlurW - 1) / kBlurW); }
+
+static bool ranges_overlap(const void* a, const void* b, size_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + n && y < x + n;
+}
+
+// what the table asks for; refuses what the kernels would have to clamp
+static int check_post(const char* who, const void* in, const Post* table, int F, int H, int W, const void* out, bool* blur, bool* rotate) {
+    BVC_REQUIRE(in && table && out, "%s: null argument", who);
+    BVC_REQUIRE(F >= 1 && H >= 1 && W >= 1, "%s: empty input", who);
+    BVC_REQUIRE((int64_t)H * W <= (1 << 24), "%s: frame too large", who);
+    BVC_REQUIRE((int64_t)F * ((int64_t)H * W / 1024 + 1 + blur_tiles(H, W)) < (1ll << 30), "%s: too many frames", who);
+    BVC_REQUIRE(!ranges_overlap(in, out, (size_t)F * 3 * H * W), "%s: in and out overlap", who);
+    *blur = *rotate = false;
+    char msg[512];
+    for (int f = 0; f < F; ++f) {
+        if (invalid_post(table[f], f, H, W, msg, sizeof(msg))) {
+            set_error("%s", msg);
+            return BVC_ERR_INVALID;
+        }
+        if (table[f].blur_r >= 0 || table[f].gray) *blur = true;
+        if (table[f].rotate) *rotate = true;
+    }
+    return BVC_OK;
+}
+
 }  // namespace aug
 }  // namespace bvc
 
@@ -251,6 +509,60 @@ int bvc_clip_transform_host(const uint8_t* src, int F_src, int channels, int Hs,
     const int rc = aug::check_call("clip_transform_host", src, F_src, channels, Hs, Ws, table, F_out, Ho, Wo, out, &second);
     if (rc != BVC_OK) return rc;
     aug::clip_transform_host(src, F_src, Hs, Ws, table, F_out, Ho, Wo, out);
+    return BVC_OK;
+}
+
+int bvc_aug_blur_weights(float radius, int32_t* r, uint32_t* ww, uint32_t* fw) {
+    BVC_REQUIRE(r && ww && fw, "aug_blur_weights: null argument");
+    BVC_REQUIRE(aug::blur_weights(radius, r, ww, fw) == 0, "aug_blur_weights: radius %g outside [0, %g]", (double)radius,
+                (double)BVC_AUG_MAX_BLUR_RADIUS);
+    return BVC_OK;
+}
+
+int64_t bvc_op_clip_post_workspace(int F, int H, int W) {
+    if (F < 1 || H < 1 || W < 1) return 0;
+    return (int64_t)F * 3 * H * W;      // the frames between the blur and the rotation kernel
+}
+
+int bvc_op_clip_post(const uint8_t* in_dev, const bvc_frame_post* table_host, const bvc_frame_post* table_dev, int F, int H, int W,
+                     uint8_t* out_dev, void* workspace_dev, void* stream) {
+    bool blur = false, rotate = false;
+    BVC_REQUIRE(table_dev, "op_clip_post: null device table");
+    const int rc = aug::check_post("op_clip_post", in_dev, table_host, F, H, W, out_dev, &blur, &rotate);
+    if (rc != BVC_OK) return rc;
+    const size_t bytes = (size_t)F * 3 * H * W;
+    if (!blur && !rotate) {      // the identity everywhere: one copy
+        BVC_CHECK_HIP(hipMemcpyAsync(out_dev, in_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return BVC_OK;
+    }
+    uint8_t* mid = (uint8_t*)workspace_dev;
+    if (blur && rotate)
+        BVC_REQUIRE(mid && !aug::ranges_overlap(mid, in_dev, bytes) && !aug::ranges_overlap(mid, out_dev, bytes),
+                    "op_clip_post: blur and rotation in one call need a workspace that overlaps neither in nor out");
+    if (blur) {
+        uint8_t* dst = rotate ? mid : out_dev;
+        const int tiles_x = (W + aug::kBlurW - 1) / aug::kBlurW, tiles = aug::blur_tiles(H, W);
+        const int vec = W % 4 == 0 && ((uintptr_t)in_dev % 4) == 0 && ((uintptr_t)dst % 4) == 0;
+        hipLaunchKernelGGL(aug::clip_blur_kernel, dim3((unsigned)(F * tiles)), dim3(256), 0, (hipStream_t)stream, in_dev, table_dev, H, W, dst,
+                           tiles_x, tiles, vec);
+        BVC_CHECK_HIP(hipGetLastError());
+    }
+    if (rotate) {
+        const uint8_t* src = blur ? mid : in_dev;
+        const int plane = H * W, chunks = (plane + 1023) / 1024;
+        const int vec = plane % 4 == 0 && ((uintptr_t)out_dev % 4) == 0;
+        hipLaunchKernelGGL(aug::clip_rotate_kernel, dim3((unsigned)(F * chunks)), dim3(256), 0, (hipStream_t)stream, src, table_dev, H, W,
+                           out_dev, chunks, vec);
+        BVC_CHECK_HIP(hipGetLastError());
+    }
+    return BVC_OK;
+}
+
+int bvc_clip_post_host(const uint8_t* in, const bvc_frame_post* table, int F, int H, int W, uint8_t* out) {
+    bool blur = false, rotate = false;
+    const int rc = aug::check_post("clip_post_host", in, table, F, H, W, out, &blur, &rotate);
+    if (rc != BVC_OK) return rc;
+    aug::clip_post_host(in, table, F, H, W, out);
     return BVC_OK;
 }
 

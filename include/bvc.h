@@ -348,6 +348,46 @@ int bvc_op_clip_transform(const uint8_t* src_dev, int F_src, int channels, int H
                           const bvc_frame_aug* table_dev, int F_out, int Ho, int Wo, uint8_t* out_dev, void* workspace_dev, void* stream);
 int bvc_clip_transform_host(const uint8_t* src, int F_src, int channels, int Hs, int Ws, const bvc_frame_aug* table, int F_out, int Ho,
                             int Wo, uint8_t* out);
+/* The post stage: the two remaining transforms of the reference's _get_transform, on the uint8 frames [F][3][H][W] that the stage above
+ * produced.  'b' GaussianBlur(p = 0.5), i.e. PIL's ImageFilter.GaussianBlur(radius ~ U(0.1, 2.0)), and 'o' RandomHorizontalFlip +
+ * RandomRotation((-90, 90)), i.e. PIL's Image.rotate(angle, NEAREST, expand=False, fillcolor=0); the flip stays in bvc_frame_aug
+ * (it commutes bit for bit with a symmetric integer blur and with pointwise colour).  One bvc_frame_post per frame; per frame the order
+ * is blur, gray, rotation (the reference's b, g, o).  Everything is integer arithmetic (the gray is the stage above's), restated from
+ * Pillow: the device, the host twin and PIL give the same bytes.
+ *   blur_r           integer box radius, -1 = no blur.  Pillow approximates the Gaussian by three box passes along the rows and then
+ *                    three along the columns, every pass rounded to uint8, taps beyond the frame reading the edge value of that
+ *                    pass's input:  out[x] = (ww * sum_{|i| <= r} in[x + i] + fw * (in[x - r - 1] + in[x + r + 1]) + 2^23) >> 24
+ *   blur_ww, blur_fw the 8.24 fixed-point weights of the box and of its two far taps; bvc_aug_blur_weights (host only) derives
+ *                    (r, ww, fw) from the Gaussian radius as Pillow does, types included (f32, the square root and the floor in f64, an
+ *                    f32 division for ww); it refuses a negative radius, a NaN and a radius above BVC_AUG_MAX_BLUR_RADIUS.  Radius 0 is
+ *                    ww = 2^24, fw = 0: the identity
+ *   gray             non-zero: the grayscale stage of the stage above (trunc(0.2989 r + 0.587 g + 0.114 b)), applied AFTER the blur
+ *   rotate, rot[6]   non-zero: output pixel (x, y) copies in[yin][xin] with xin = (a2 + a1 y + a0 x) >> 16 and yin = (a5 + a4 y + a3 x)
+ *                    >> 16 (arithmetic shifts) when that lies inside the frame, and is 0 otherwise; a0 .. a5 is the inverse affine map
+ *                    in 16.16 fixed point as Pillow's affine_fixed builds it (bvc.augment.rotation_coeffs)
+ * bvc_op_clip_post: in_dev / table_dev / out_dev / workspace_dev are device memory, table_host is the same table in host memory, read
+ * during the call only: it is validated there, without a device sync, and tells the call what to launch.  At most two launches: the
+ * blur kernel when some frame blurs or turns gray (frames that do neither are copied through by their workgroups), the rotation
+ * kernel when some frame rotates (the others are copied); with both the frames pass through workspace_dev
+ * (bvc_op_clip_post_workspace bytes, needed only then).  A table that is the identity everywhere is served by one device-to-device
+ * copy.  No atomics: nothing for the deterministic mode to switch.  BVC_ERR_INVALID with a message for blur_r outside [-1, 3], weights
+ * with (2 r + 1) ww + 2 fw > 2^24, a rotating frame with an edge above 4096, |a0|, |a1|, |a3|, |a4| > 65537 or |a2|, |a5| > 2^30 (the
+ * bounds keep every intermediate inside int32), and in / out that overlap.  The kernels do not trust the device copy of the table: they
+ * clamp blur_r, take over-weight entries as "no blur" and test every gather's source index.
+ * bvc_clip_post_host: the same arithmetic compiled for the host (csrc/augment.h), on host memory; needs no GPU. */
+typedef struct bvc_frame_post {
+    int32_t blur_r;
+    uint32_t blur_ww, blur_fw;
+    int32_t gray;
+    int32_t rotate;
+    int32_t rot[6];
+} bvc_frame_post; /* 44 bytes */
+#define BVC_AUG_MAX_BLUR_RADIUS 4.0f /* Gaussian radius; gives blur_r <= 3 */
+int bvc_aug_blur_weights(float radius, int32_t* r, uint32_t* ww, uint32_t* fw);
+int64_t bvc_op_clip_post_workspace(int F, int H, int W);
+int bvc_op_clip_post(const uint8_t* in_dev, const bvc_frame_post* table_host, const bvc_frame_post* table_dev, int F, int H, int W,
+                     uint8_t* out_dev, void* workspace_dev, void* stream);
+int bvc_clip_post_host(const uint8_t* in, const bvc_frame_post* table, int F, int H, int W, uint8_t* out);
 
 /* ------------------------------------------------------------------------------------------------
  * JEPA encoder and predictor (pretraining/predictive/vision_transformer.py).  Same conventions as above: flat f32

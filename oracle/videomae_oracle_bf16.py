@@ -52,7 +52,9 @@ BUILD = Policy()                         # the operand policy of libbvc_hip.so (
 
 
 def _r(t, on=True):
-    return t.to(torch.bfloat16).float() if on else t
+    """Round to bf16 and return in the input's dtype: f32 in, f32 out (the policy step); f64 in, f64 out (the float64-carried twin of
+    tests/model_rows_ref.py: the same operand roundings, every product / LayerNorm / softmax / loss in float64)."""
+    return t.to(torch.bfloat16).to(t.dtype) if on else t
 
 
 class _Linear(torch.autograd.Function):
@@ -170,8 +172,13 @@ def _layer(x, p, prefix, heads, eps, pol, taps, tapname):
 
 
 def forward(cfg: vo.OracleConfig, p: "Dict[str, torch.Tensor]", pixel_values, bool_masked_pos, pol: Policy = BUILD,
-            taps: Optional[dict] = None):
-    """`videomae_oracle.forward` with the operand policy `pol`.  Returns (loss, logits, labels)."""
+            taps: Optional[dict] = None, bool_decode_pos=None):
+    """`videomae_oracle.forward` with the operand policy `pol`.  Returns (loss, logits, labels).
+
+    `bool_decode_pos` ([B, L] bool, a subset of the mask with one count per clip; None: the mask itself) selects the masked tokens
+    the decoder reconstructs, as in tests/dual_mask_ref.py: mask-token rows, logits and targets exist for those only.
+    The arithmetic runs in the dtype of `p` and `pixel_values`: float32 is the policy step, float64 the float64-carried twin."""
+    dec = bool_masked_pos if bool_decode_pos is None else bool_decode_pos
     B, T, C, H, W = pixel_values.shape
     D, Dd, L = cfg.hidden_size, cfg.decoder_hidden_size, cfg.seq_len
     ts, ps = cfg.tubelet_size, cfg.patch_size
@@ -189,7 +196,7 @@ def forward(cfg: vo.OracleConfig, p: "Dict[str, torch.Tensor]", pixel_values, bo
     x = linear(x, p["encoder_to_decoder.weight"], None, pol)
     pos = vo.sinusoid_table(L, Dd)[None].expand(B, -1, -1)
     pos_vis = pos[~bool_masked_pos].reshape(B, -1, Dd)
-    pos_msk = pos[bool_masked_pos].reshape(B, -1, Dd)
+    pos_msk = pos[dec].reshape(B, -1, Dd)
     x = torch.cat([x + pos_vis, p["mask_token"] + pos_msk], dim=1)
     if taps is not None:
         taps["x_full"] = x
@@ -200,8 +207,8 @@ def forward(cfg: vo.OracleConfig, p: "Dict[str, torch.Tensor]", pixel_values, bo
     x = F.layer_norm(x, (Dd,), p["decoder.norm.weight"], p["decoder.norm.bias"], cfg.decoder_norm_eps)
     logits = linear(x, p["decoder.head.weight"], p["decoder.head.bias"], pol)
     with torch.no_grad():
-        labels = vo.pixel_labels(cfg, pixel_values, bool_masked_pos)
-    loss = F.mse_loss(logits.float(), labels)
+        labels = vo.pixel_labels(cfg, pixel_values, dec)
+    loss = F.mse_loss(logits, labels)
     if taps is not None:
         taps["logits"] = logits
         taps["labels"] = labels
@@ -209,10 +216,10 @@ def forward(cfg: vo.OracleConfig, p: "Dict[str, torch.Tensor]", pixel_values, bo
 
 
 def step(cfg: vo.OracleConfig, params, pixel_values, bool_masked_pos, pol: Policy = BUILD, grad_scale: float = 1.0,
-         taps: Optional[dict] = None):
-    """Forward + backward under `pol`; gradients are f32 (multiplied by `grad_scale`, like `videomae_oracle.step`)."""
+         taps: Optional[dict] = None, bool_decode_pos=None):
+    """Forward + backward under `pol`; gradients come in the parameters' dtype (multiplied by `grad_scale`, like `videomae_oracle.step`)."""
     p = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
-    loss, _, _ = forward(cfg, p, pixel_values, bool_masked_pos, pol, taps)
+    loss, _, _ = forward(cfg, p, pixel_values, bool_masked_pos, pol, taps, bool_decode_pos)
     (loss * grad_scale).backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in p.items()}
     return loss.detach(), grads

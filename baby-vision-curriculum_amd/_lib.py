@@ -250,6 +250,13 @@ SYMBOLS = {
                                       [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bvc_op_adam_step_table": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 +
                                        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    # (params, grads, state arrays, n, seg_start, seg_group, blk_seg, nseg, items, nitems, seg_first_item, ngroups, 7 hyper-parameter
+    #  arrays, [state,] group_table, item_partial, seg_stats, grad_scale, found_inf, write_unscaled_grads, bf16_shadow, stream)
+    "bvc_op_lars_step_table": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p,
+                                       c_int] + [c_void_p] * 7 + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "bvc_op_lamb_step_table": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                       c_void_p, c_int] + [c_void_p] * 7 +
+                                      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bvc_op_nonfinite_check": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "bvc_op_grad_norm_item_cap": (c_int, []),
     "bvc_op_grad_norm_chain": (c_int, []),

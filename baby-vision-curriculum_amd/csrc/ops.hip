@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "context.h"
+#include "optim_layerwise.h"
 
 namespace bvc {
 static thread_local char g_err[1024] = "";
@@ -261,6 +262,28 @@ int bvc_op_clip_finalize(const float* sq, int nranges, float max_norm, const flo
 int bvc_op_scale_by_dev(float* x, int64_t n, const float* coef, void* stream) {
     BVC_REQUIRE(x && coef && n >= 0 && ((uintptr_t)x % 4) == 0, "op_scale_by_dev: bad argument");
     return launch_scale_by_dev(x, (size_t)n, coef, (hipStream_t)stream);
+}
+int bvc_op_lars_step_table(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,
+                           const int32_t* blk_seg, int nseg, const bvc_norm_item* items, int64_t nitems, const int64_t* seg_first_item,
+                           int ngroups, const float* lr, const float* momentum, const float* weight_decay, const float* trust_coefficient,
+                           const int32_t* nesterov, const int32_t* adapt, const int32_t* maximize, float* group_table, double* item_partial,
+                           float* seg_stats, const float* grad_scale, float* found_inf, int write_unscaled_grads, void* bf16_shadow,
+                           void* stream) {
+    BVC_REQUIRE(params && grads && n >= 0, "op_lars_step_table: bad argument");
+    return launch_lars_step_table(params, grads, momentum_buf, n, seg_start, seg_group, blk_seg, nseg, items, nitems, seg_first_item, ngroups,
+                                  lr, momentum, weight_decay, trust_coefficient, nesterov, adapt, maximize, group_table, item_partial,
+                                  seg_stats, grad_scale, found_inf, write_unscaled_grads, (bf16_t*)bf16_shadow, (hipStream_t)stream);
+}
+int bvc_op_lamb_step_table(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const int64_t* seg_start,
+                           const int32_t* seg_group, const int32_t* blk_seg, int nseg, const bvc_norm_item* items, int64_t nitems,
+                           const int64_t* seg_first_item, int ngroups, const double* lr, const double* beta1, const double* beta2,
+                           const double* eps, const double* weight_decay, const int32_t* adapt, const int32_t* maximize, float* state,
+                           float* group_table, double* item_partial, float* seg_stats, const float* grad_scale, const float* found_inf,
+                           int write_unscaled_grads, void* bf16_shadow, void* stream) {
+    BVC_REQUIRE(params && grads && exp_avg && exp_avg_sq && n >= 0, "op_lamb_step_table: bad argument");
+    return launch_lamb_step_table(params, grads, exp_avg, exp_avg_sq, n, seg_start, seg_group, blk_seg, nseg, items, nitems, seg_first_item,
+                                  ngroups, lr, beta1, beta2, eps, weight_decay, adapt, maximize, state, group_table, item_partial, seg_stats,
+                                  grad_scale, found_inf, write_unscaled_grads, (bf16_t*)bf16_shadow, (hipStream_t)stream);
 }
 int bvc_op_row_normalize(const float* f, void* fn_bf16, float* inv_norm, int n, int p, float eps, void* stream) {
     BVC_REQUIRE(f && fn_bf16 && inv_norm, "op_row_normalize: null argument");

@@ -28,6 +28,13 @@ device, and the step calls are handed the address of the last where they were ha
 thereby clip too.  ``optimizer.grad_norm`` / ``optimizer.clip_coef`` are 0-d device views of the last step's values.  Immediate forms:
 ``clip_grad_norm_`` (torch's signature) and ``grad_norms(module)`` (per-parameter norms in one launch pair).  DESIGN.md
 "Gradient-norm clipping".
+
+``LARS`` and ``LAMB`` scale every parameter tensor's update by a ratio of norms (``adaptive_param_groups`` makes the usual two groups:
+1-D tensors and biases neither decay nor adapt).  The segment table has one segment per tensor and the gradient-norm work list cuts
+it into items, so a step is one library call per flat module (``bvc_op_lars_step_table`` / ``bvc_op_lamb_step_table``: a pass that
+leaves per-item sums of squares, a per-segment reduction to ``{||w||, ||d||, ratio}``, the apply pass), for any number of groups; runs
+of parameters outside flat buffers go through the same entry points.  ``optimizer.trust_ratios()`` gives the last step's ratios as
+0-d device views.  DESIGN.md "Layer-wise trust ratios".
 """
 import ctypes
 
@@ -84,6 +91,7 @@ class _Plan:
         firsts = torch.arange(nblk, dtype=torch.int64, device=dev) * 1024
         self.blk_seg = (torch.searchsorted(self.seg_start, firsts, right=True) - 1).to(torch.int32)
         self.state = None      # optimiser-specific flat state
+        self.lw = None         # LARS / LAMB: the _Range of this table (work list, group table, partials, seg_stats)
 
 
 def _build_plans(param_groups):
@@ -258,12 +266,14 @@ class SGD(torch.optim.Optimizer):
         self._runs = {}   # group index -> (key, runs) for parameters outside flat buffers
         self._plans = None   # (key, plans, loose)
 
+    _make_plans = staticmethod(_choose_plans)      # (LARS / LAMB below: table plans for any number of groups)
+
     def _get_plans(self):
         key = _plans_key(self.param_groups)
         if self._plans is not None and self._plans[0] != key and _plans_still_valid(self._plans, key):
             self._plans = (key, self._plans[1], self._plans[2])
         if self._plans is None or self._plans[0] != key:
-            plans, loose = _choose_plans(self.param_groups)
+            plans, loose = self._make_plans(self.param_groups)
             self._plans = (key, plans, loose)
             self._runs = {}
         return self._plans[1], self._plans[2]
@@ -510,7 +520,7 @@ class Adam(torch.optim.Optimizer):
 
     _contiguous_runs = staticmethod(SGD._contiguous_runs)
     _group_runs = SGD._group_runs
-    _get_plans = SGD._get_plans
+    _get_plans, _make_plans = SGD._get_plans, staticmethod(_choose_plans)
     _clip_device, _clip_buffers, _grad_sq, _clip_scale = SGD._clip_device, SGD._clip_buffers, SGD._grad_sq, SGD._clip_scale
     grad_norm, clip_coef = SGD.grad_norm, SGD.clip_coef
 
@@ -638,6 +648,285 @@ class AdamW(Adam):
                  max_grad_norm=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                          max_grad_norm=max_grad_norm)
+
+
+# ---------------------------------------------------------------------------------------------- layer-wise trust ratios: LARS, LAMB
+class _Range:
+    """What one call of ``bvc_op_lars_step_table`` / ``bvc_op_lamb_step_table`` works on: a segment table with one segment per
+    parameter tensor (a flat module's, or that of a run of parameters outside flat buffers), its work list, and the device buffers
+    the caller owns: the group table, the f64 item partials and ``seg_stats`` [nseg][3] = {||w||, ||d|| or ||u||, ratio}."""
+
+    def __init__(self, opt, starts, groups, ngroups, device, tables=None):
+        self.n, self.nseg, self.ngroups = int(starts[-1]), len(groups), ngroups
+        if tables is None:
+            seg_start = torch.tensor(starts, dtype=torch.int64, device=device)
+            firsts = torch.arange((self.n + 1023) // 1024, dtype=torch.int64, device=device) * 1024
+            tables = (seg_start, torch.tensor(groups, dtype=torch.int32, device=device),
+                      (torch.searchsorted(seg_start, firsts, right=True) - 1).to(torch.int32))
+        self.seg_start, self.seg_group, self.blk_seg = tables
+        raw, first = _work_list_raw(starts, groups)
+        self.nitems = raw.shape[0]
+        self.items, self.first = raw.to(device), first.to(device)
+        self.table = opt._zeros(8 * ngroups, torch.float32, device)
+        self.partial = opt._zeros(2 * max(self.nitems, 1), torch.float64, device)
+        self.stats = opt._zeros(3 * self.nseg, torch.float32, device).view(self.nseg, 3)
+        self.stats[:, 2] = 1.0
+        self.owned = [s for s, g in enumerate(groups) if g >= 0]      # the segment of the k-th parameter in address order
+        self.host = None       # the ctypes arrays the hyper-parameters are handed over in
+
+
+def _views_alias(flat, views):
+    """True if the per-parameter state tensors `views` are, in order, the consecutive stretches of `flat`.  Gradients of parameters
+    outside flat buffers are fresh allocations every step, so memory-adjacent runs can join and part from one step to the next: the
+    flat state a run's first parameter kept from an earlier grouping is only good while the per-parameter views still point into it."""
+    at = flat.data_ptr()
+    for v in views:
+        if v is None or v.data_ptr() != at:
+            return False
+        at += 4 * v.numel()
+    return True
+
+
+class _LayerwiseOptimizer(torch.optim.Optimizer):
+    """What LARS and LAMB share: one library call per flat module and per run of parameters outside flat buffers, through the
+    segment-table entry points for ANY number of groups (there is no by-value twin); the plan cache, the GradScaler protocol and
+    ``max_grad_norm`` of the other optimisers; ``trust_ratios()``."""
+    _step_supports_amp_scaling = True
+    _make_plans = staticmethod(_build_table_plans)
+    _contiguous_runs = staticmethod(SGD._contiguous_runs)
+    _group_runs, _get_plans = SGD._group_runs, SGD._get_plans
+    _clip_device, _clip_buffers, _grad_sq, _clip_scale = SGD._clip_device, SGD._clip_buffers, SGD._grad_sq, SGD._clip_scale
+    grad_norm, clip_coef = SGD.grad_norm, SGD.clip_coef
+
+    @staticmethod
+    def _zeros(n, dtype, device):
+        """Every device buffer the step kernels write is allocated here (tests put guard bands around them)."""
+        return torch.zeros(n, dtype=dtype, device=device)
+
+    def _setup(self, max_grad_norm):
+        self.max_grad_norm = _checked_max_grad_norm(max_grad_norm)
+        self._clip = None
+        self._runs = {}
+        self._plans = None
+
+    def load_state_dict(self, state_dict):
+        """As SGD.load_state_dict: the cached flat state is dropped, the next step adopts the loaded per-parameter tensors."""
+        super().load_state_dict(state_dict)
+        self._plans = None
+        self._runs = {}
+
+    def state_dict(self):
+        # shallow copies, as SGD.state_dict: the live per-parameter dicts keep their flat state
+        sd = super().state_dict()
+        sd["state"] = {k: {n: v for n, v in st.items() if not n.startswith("_flat_")} for k, st in sd["state"].items()}
+        return sd
+
+    def _plan_range(self, plan):
+        if plan.lw is None:
+            plan.lw = _Range(self, plan.starts, plan.groups, len(self.param_groups), plan.module._flat.device,
+                             (plan.seg_start, plan.seg_group, plan.blk_seg))
+        return plan.lw
+
+    def _run_range(self, run):
+        """The table of a run outside flat buffers: one segment per parameter, all of group 0 of a one-group table."""
+        st = self.state[run[0]]
+        sizes = tuple(p.numel() for p in run)
+        R = st.get("_flat_range")
+        if R is None or R.sizes != sizes:
+            starts = [0]
+            for k in sizes:
+                starts.append(starts[-1] + k)
+            R = st["_flat_range"] = _Range(self, starts, [0] * len(sizes), 1, run[0].device)
+            R.sizes = sizes
+        return R
+
+    def trust_ratios(self):
+        """``{parameter: 0-d device view of the trust ratio the last step applied to it}`` (1 before the first step, for a group with
+        ``adapt=False`` and where the rule falls back: a zero tensor, a zero update).  No sync; the views alias ``seg_stats``."""
+        out = {}
+        plans, loose = self._get_plans()
+        for plan in plans:
+            R = self._plan_range(plan)
+            for s, (_off, p, _gi) in zip(R.owned, plan.items):
+                out[p] = R.stats[s, 2]
+        for gi, ps in loose.items():
+            for run in self._group_runs(gi, ps):
+                R = self._run_range(run)
+                for s, p in enumerate(run):
+                    out[p] = R.stats[s, 2]
+        return out
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        grad_scale = getattr(self, "grad_scale", None)
+        found_inf = getattr(self, "found_inf", None)
+        gs = grad_scale.data_ptr() if grad_scale is not None else None
+        fi = found_inf.data_ptr() if found_inf is not None else None
+        L = _lib.lib()
+        stream = _lib.current_stream_ptr()
+        plans, loose = self._get_plans()
+        if self.max_grad_norm is not None:
+            gs = self._clip_scale(L, stream, grad_scale, gs)
+        everyone = range(len(self.param_groups))
+        for plan in plans:
+            self._launch(L, self._plan_range(plan), plan.base, plan.gbase, everyone, self._plan_state(plan), gs, fi, stream)
+        for gi, ps in loose.items():
+            for run in self._group_runs(gi, ps):
+                self._launch(L, self._run_range(run), run[0].data_ptr(), run[0].grad.data_ptr(), (gi,), self._run_state(gi, run), gs, fi,
+                             stream)
+        return loss
+
+
+class LARS(_LayerwiseOptimizer):
+    """Layer-wise adaptive rate scaling in the form of SimCLR's and MAE's LARS, per parameter tensor ``w`` with gradient ``g``::
+
+        d = g + weight_decay * w
+        q = trust_coefficient * ||w|| / ||d||   if adapt and ||w|| > 0 and ||d|| > 0, else 1
+        buf = momentum * buf + q * d ;  w -= lr * (q * d + momentum * buf  if nesterov else  buf)
+
+    ``adapt`` is a per-group key (default True); with ``adapt=False`` a group is plain momentum SGD - what biases and norm parameters
+    get (``adaptive_param_groups``).  State: ``momentum_buffer`` per parameter, views of one flat buffer per flat module.  One
+    ``bvc_op_lars_step_table`` call per flat module and step (include/bvc.h "Layer-wise trust ratios")."""
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, trust_coefficient=0.001, nesterov=False, *, maximize=False,
+                 max_grad_norm=None):
+        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0 or trust_coefficient < 0.0:
+            raise ValueError("invalid hyper-parameter")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum")
+        self._setup(max_grad_norm)
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, trust_coefficient=trust_coefficient,
+                                      nesterov=nesterov, adapt=True, maximize=maximize))
+
+    def _plan_state(self, plan):
+        """One flat momentum buffer per flat module; the per-parameter ``momentum_buffer`` entries are views into it."""
+        if not any(g["momentum"] != 0 for g in self.param_groups):
+            return None
+        if plan.state is None:
+            flat = self._zeros(plan.n, torch.float32, plan.module._flat.device)
+            for off, p, _gi in plan.items:
+                st, k = self.state[p], p.numel()
+                if st.get("momentum_buffer") is not None:      # after load_state_dict: adopt the loaded buffer
+                    flat[off:off + k].copy_(st["momentum_buffer"].reshape(-1))
+                st["momentum_buffer"] = flat[off:off + k].view(p.shape)
+            plan.state = flat
+        return plan.state
+
+    def _run_state(self, gi, run):
+        if self.param_groups[gi]["momentum"] == 0:
+            return None
+        st, n = self.state[run[0]], sum(p.numel() for p in run)
+        flat = st.get("_flat_momentum")
+        if flat is None or flat.numel() != n or not _views_alias(flat, [self.state[p].get("momentum_buffer") for p in run]):
+            flat, o = self._zeros(n, torch.float32, run[0].device), 0
+            for p in run:
+                k = p.numel()
+                if self.state[p].get("momentum_buffer") is not None:
+                    flat[o:o + k].copy_(self.state[p]["momentum_buffer"].reshape(-1))
+                self.state[p]["momentum_buffer"] = flat[o:o + k].view(p.shape)
+                o += k
+            st["_flat_momentum"] = flat
+        return flat
+
+    def _launch(self, L, R, base, gbase, gids, buf, gs, fi, stream):
+        if R.host is None:
+            R.host = {n: (ctypes.c_float * R.ngroups)() for n in ("lr", "momentum", "weight_decay", "trust_coefficient")}
+            R.host.update({n: (ctypes.c_int32 * R.ngroups)() for n in ("nesterov", "adapt", "maximize")})
+        H = R.host
+        for j, gi in enumerate(gids):
+            g = self.param_groups[gi]
+            H["lr"][j], H["momentum"][j], H["weight_decay"][j] = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
+            H["trust_coefficient"][j] = float(g["trust_coefficient"])
+            H["nesterov"][j], H["adapt"][j], H["maximize"][j] = int(g["nesterov"]), int(g.get("adapt", True)), int(g["maximize"])
+        _lib.check(L.bvc_op_lars_step_table(
+            base, gbase, buf.data_ptr() if buf is not None else None, R.n, R.seg_start.data_ptr(), R.seg_group.data_ptr(),
+            R.blk_seg.data_ptr(), R.nseg, R.items.data_ptr() if R.nitems else None, R.nitems, R.first.data_ptr(), R.ngroups, H["lr"],
+            H["momentum"], H["weight_decay"], H["trust_coefficient"], H["nesterov"], H["adapt"], H["maximize"], R.table.data_ptr(),
+            R.partial.data_ptr(), R.stats.data_ptr(), gs, fi, 1, _flat.shadow_for(base, R.n), stream), "bvc_op_lars_step_table")
+
+
+class LAMB(_LayerwiseOptimizer):
+    """LAMB (You et al. 2020) with bias correction, per parameter tensor ``w`` with gradient ``g``::
+
+        m = b1 m + (1 - b1) g ;  v = b2 v + (1 - b2) g*g
+        u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + weight_decay * w
+        r = ||w|| / ||u||   if adapt and ||w|| > 0 and ||u|| > 0, else 1 ;  w -= lr * r * u
+
+    ``adapt`` is a per-group key (default True); with ``adapt=False`` a group is AdamW.  State as ``bvc.optim.Adam``: ``step`` (one
+    count per group, on the device: a step GradScaler skips does not advance it), ``exp_avg``, ``exp_avg_sq``.  One
+    ``bvc_op_lamb_step_table`` call per flat module and step."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, *, maximize=False, max_grad_norm=None):
+        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError("invalid hyper-parameter")
+        self._setup(max_grad_norm)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adapt=True, maximize=maximize))
+
+    def _adopt(self, params_at, n, ngroups, device):
+        """Flat exp_avg / exp_avg_sq over `n` elements and 3 step scalars per group, {step, 1 / (1 - b1^step), 1 / sqrt(1 - b2^step)};
+        loaded per-parameter state is adopted (a group shares one step count), the per-parameter entries become views."""
+        m, v = self._zeros(n, torch.float32, device), self._zeros(n, torch.float32, device)
+        state = self._zeros(3 * ngroups, torch.float32, device)
+        for off, p, row in params_at:
+            st, k = self.state[p], p.numel()
+            if "exp_avg" in st:
+                m[off:off + k].copy_(st["exp_avg"].reshape(-1))
+                v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
+                state[3 * row] = float(st["step"])
+            st["exp_avg"], st["exp_avg_sq"] = m[off:off + k].view(p.shape), v[off:off + k].view(p.shape)
+            st["step"] = state[3 * row]
+        return m, v, state
+
+    def _plan_state(self, plan):
+        if plan.state is None:
+            plan.state = self._adopt(plan.items, plan.n, len(self.param_groups), plan.module._flat.device)
+        return plan.state
+
+    def _run_state(self, gi, run):
+        st, n = self.state[run[0]], sum(p.numel() for p in run)
+        flat = st.get("_flat_lamb")
+        if (flat is None or flat[0].numel() != n or not _views_alias(flat[0], [self.state[p].get("exp_avg") for p in run])
+                or any(self.state[p]["step"].data_ptr() != flat[2].data_ptr() for p in run)):
+            at, o = [], 0
+            for p in run:
+                at.append((o, p, 0))
+                o += p.numel()
+            flat = st["_flat_lamb"] = self._adopt(at, n, 1, run[0].device)
+        return flat
+
+    def _launch(self, L, R, base, gbase, gids, flat, gs, fi, stream):
+        if R.host is None:
+            R.host = {n: (ctypes.c_double * R.ngroups)() for n in ("lr", "beta1", "beta2", "eps", "weight_decay")}
+            R.host.update({n: (ctypes.c_int32 * R.ngroups)() for n in ("adapt", "maximize")})
+        H = R.host
+        for j, gi in enumerate(gids):
+            g = self.param_groups[gi]
+            H["lr"][j], H["beta1"][j], H["beta2"][j] = float(g["lr"]), float(g["betas"][0]), float(g["betas"][1])
+            H["eps"][j], H["weight_decay"][j] = float(g["eps"]), float(g["weight_decay"])
+            H["adapt"][j], H["maximize"][j] = int(g.get("adapt", True)), int(g["maximize"])
+        m, v, state = flat
+        _lib.check(L.bvc_op_lamb_step_table(
+            base, gbase, m.data_ptr(), v.data_ptr(), R.n, R.seg_start.data_ptr(), R.seg_group.data_ptr(), R.blk_seg.data_ptr(), R.nseg,
+            R.items.data_ptr() if R.nitems else None, R.nitems, R.first.data_ptr(), R.ngroups, H["lr"], H["beta1"], H["beta2"], H["eps"],
+            H["weight_decay"], H["adapt"], H["maximize"], state.data_ptr(), R.table.data_ptr(), R.partial.data_ptr(), R.stats.data_ptr(),
+            gs, fi, 1, _flat.shadow_for(base, R.n), stream), "bvc_op_lamb_step_table")
+
+
+def adaptive_param_groups(model, weight_decay, no_adapt=()):
+    """The usual LARS / LAMB exclusion as two parameter groups: 1-D tensors, ``*.bias`` and the names in ``no_adapt`` get
+    ``weight_decay=0, adapt=False`` (group ``no_adapt``: plain momentum SGD / AdamW), the rest the given decay and ``adapt=True``
+    (group ``adapt``).  Parameters with ``requires_grad=False`` are left out."""
+    skip = set(no_adapt)
+    adapted, plain = [], []
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            (plain if p.ndim <= 1 or name.endswith(".bias") or name in skip else adapted).append(p)
+    return [{"name": "adapt", "params": adapted, "weight_decay": weight_decay, "adapt": True},
+            {"name": "no_adapt", "params": plain, "weight_decay": 0.0, "adapt": False}]
 
 
 # ---------------------------------------------------------------------------------------------- layer-wise learning-rate decay

@@ -690,6 +690,46 @@ int bvc_op_grad_sqnorm_items(const float* x, const bvc_norm_item* items, int64_t
                              double* item_partial, float* seg_sq, float* total_sq, int as_norm, float* found_inf, void* stream);
 int bvc_op_clip_finalize(const float* sq, int nranges, float max_norm, const float* grad_scale, float* out3, void* stream);
 int bvc_op_scale_by_dev(float* x, int64_t n, const float* coef, void* stream);
+/* Layer-wise trust ratios: LARS (the form of SimCLR's and MAE's LARS) and LAMB (You et al. 2020, with bias correction) over a flat f32
+ * range, one trust ratio per SEGMENT of the segment table above (one segment per parameter tensor; a plain contiguous tensor is a
+ * table of one segment).  Per tensor w with gradient g (g already divided by *grad_scale and negated under maximize):
+ *   LARS:  d = g + weight_decay w;  q = trust_coefficient ||w|| / ||d|| if adapt and ||w|| > 0 and ||d|| > 0, else 1;  d = q d;
+ *          buf = momentum buf + d;  w -= lr (nesterov ? d + momentum buf : buf)
+ *   LAMB:  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + weight_decay w;
+ *          r = ||w|| / ||u|| if adapt and ||w|| > 0 and ||u|| > 0, else 1;  w -= lr r u
+ * These two entry points are the only path, for any number of groups (1..BVC_OPT_TABLE_MAX_GROUPS); the hyper-parameters are plain
+ * host arrays of `ngroups` entries, read before the call returns.  Each call makes its whole launch sequence on `stream`, with no
+ * host synchronisation, no allocation and no copy from host memory that has to outlive the call:
+ *   1. one writer launch per BVC_OPT_TABLE_CHUNK groups: the groups' rows of group_table (as kernel arguments); for LAMB also the
+ *      groups' step scalars in `state` (advanced unless *found_inf != 0),
+ *   2. one workgroup per item of the work list (bvc_grad_norm_items_host of the same table): LARS reads w and g once and forms d,
+ *      LAMB updates exp_avg / exp_avg_sq in place (and writes the unscaled g back) and forms u; either leaves the item's
+ *      sum w^2 and sum d^2 (sum u^2) in item_partial as f64 (a thread adds at most bvc_op_grad_norm_chain() squares serially in f32),
+ *   3. one workgroup per segment: the partials of the segment's items added in f64 in a fixed order -> seg_stats[s] =
+ *      {||w||, ||d|| or ||u||, ratio}; a segment no group owns gets {0, 0, 1},
+ *   4. one launch over the whole range in 1024-element blocks (blk_seg as above): LARS applies momentum and the step, LAMB recomputes
+ *      u from the updated moments with the device function step 2 used - the applied update is the one whose norm was taken - and
+ *      both write the parameters and, where given, their bf16 shadow.
+ * No atomics: the same bits on every run.  Every launch returns at once when *found_inf != 0, so a step GradScaler skips writes
+ * nothing: not the parameters, the state, the step counts, seg_stats or the shadow.  The LARS item pass also SETS *found_inf (where
+ * found_inf is not NULL) when a gradient element inside an item is Inf or NaN, as bvc_op_grad_sqnorm_items does.
+ * Caller-owned device buffers: group_table f32 [8 ngroups] (16-byte aligned; contents need not survive between calls), item_partial
+ * f64 [2 max(nitems, 1)] (scratch), seg_stats f32 [3 nseg] (the last step's values; read it whenever the stream allows), momentum_buf
+ * / exp_avg / exp_avg_sq f32 [n], state f32 [3 ngroups] = {step count, 1 / (1 - b1^step), 1 / sqrt(1 - b2^step)} per group.  params,
+ * grads and the state arrays are 16-byte aligned.  momentum_buf may be NULL when every group's momentum is 0.  grad_scale, found_inf,
+ * write_unscaled_grads and bf16_shadow mean what they mean for bvc_op_sgd_step_table / bvc_op_adam_step_table. */
+int bvc_op_lars_step_table(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,
+                           const int32_t* blk_seg, int nseg, const bvc_norm_item* items, int64_t nitems, const int64_t* seg_first_item,
+                           int ngroups, const float* lr, const float* momentum, const float* weight_decay, const float* trust_coefficient,
+                           const int32_t* nesterov, const int32_t* adapt, const int32_t* maximize, float* group_table, double* item_partial,
+                           float* seg_stats, const float* grad_scale, float* found_inf, int write_unscaled_grads, void* bf16_shadow,
+                           void* stream);
+int bvc_op_lamb_step_table(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const int64_t* seg_start,
+                           const int32_t* seg_group, const int32_t* blk_seg, int nseg, const bvc_norm_item* items, int64_t nitems,
+                           const int64_t* seg_first_item, int ngroups, const double* lr, const double* beta1, const double* beta2,
+                           const double* eps, const double* weight_decay, const int32_t* adapt, const int32_t* maximize, float* state,
+                           float* group_table, double* item_partial, float* seg_stats, const float* grad_scale, const float* found_inf,
+                           int write_unscaled_grads, void* bf16_shadow, void* stream);
 /* boolean mask -> ascending visible / masked token lists (the order x[~mask] / x[mask] produce, HF:121,578-579) */
 int bvc_op_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, int* vis_idx, int* msk_idx, int* status, void* stream);
 /* the same with a decode mask: the visible list and the ascending list of the ndec decoded tokens per clip; *status |= 1 when a clip's

@@ -228,6 +228,9 @@ SYMBOLS = {
                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "bvc_op_layernorm_bwd_workspace": (c_int64, [c_int, c_int]),
     "bvc_op_colsum_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_dec_first_selected": (c_int, [c_int, c_int]),
+    "bvc_op_dec_slot": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "bvc_op_first_reduce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_colsum_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bvc_op_cast_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "bvc_op_row_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
@@ -344,7 +347,7 @@ def check(rc, what=""):
 
 
 def set_option(name, value):
-    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1, "head_pad" 0 / 1, "dec_tail" 0 / 1, "deterministic" 0 / 1 (what
+    """bvc_set_option (include/bvc.h): "gemm8" -1 / 0 / 1, "dw_overlap" 0 / 1, "row_ln" -1 / 0 / 1, "head_pad" 0 / 1, "dec_tail" 0 / 1, "dec_first" -1 / 0 / 1, "deterministic" 0 / 1 (what
     bvc.use_deterministic_algorithms and torch.use_deterministic_algorithms switch; the library's raw flag - the next library call
     after either of those changes resets it to their OR).  Returns the previous value."""
     old = lib().bvc_get_option(name.encode())

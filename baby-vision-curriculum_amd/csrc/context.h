@@ -50,10 +50,11 @@ struct PatchFront {
 };
 
 // every layer of a stack on its own activations.  chain_ln: layer i's fc2 epilogue may produce layer i + 1's first LayerNorm
-// (layer_forward's `next`); last: tail mode of the last layer
-int stack_forward(Work& w, Stack& s, const std::vector<LayerOff>& off, int B, int N, hipStream_t st, bool chain_ln, const LayerTail* last = nullptr);
+// (layer_forward's `next`); last: tail mode of the last layer; first: first mode of layer 0
+int stack_forward(Work& w, Stack& s, const std::vector<LayerOff>& off, int B, int N, hipStream_t st, bool chain_ln, const LayerTail* last = nullptr,
+                  const LayerFirst* first = nullptr);
 int stack_backward(Work& w, Stack& s, const std::vector<LayerOff>& off, float* dres, float* G, int B, int N, hipStream_t st,
-                   bvc_bucket_fn on_bucket, void* user, const LayerTail* last = nullptr);
+                   bvc_bucket_fn on_bucket, void* user, const LayerTail* last = nullptr, const LayerFirst* first = nullptr);
 // fence the last side-stream launches of a backward (older one first so ranges keep arriving tail-first)
 int join_both(Work& w, hipStream_t st, bvc_bucket_fn on_bucket, void* user);
 

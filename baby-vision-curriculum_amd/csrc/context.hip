@@ -90,19 +90,20 @@ int PatchFront::embed_backward(Work& w, int M, int D, float* gw, float* gb, hipS
     return launch_gemm(&p, 1, GEMM_TN, tile, st);
 }
 
-int stack_forward(Work& w, Stack& s, const std::vector<LayerOff>& off, int B, int N, hipStream_t st, bool chain_ln, const LayerTail* last) {
+int stack_forward(Work& w, Stack& s, const std::vector<LayerOff>& off, int B, int N, hipStream_t st, bool chain_ln, const LayerTail* last,
+                  const LayerFirst* first) {
     for (int i = 0; i < s.nlayers; ++i) {
         const bool end = i + 1 == s.nlayers;
         TRY(layer_forward(w, s, i, off[i], s.act[i].x_in, end ? s.x_out : s.act[i + 1].x_in, B, N, st, chain_ln && !end ? &off[i + 1] : nullptr,
-                          end ? last : nullptr));
+                          end ? last : nullptr, i == 0 ? first : nullptr));
     }
     return BVC_OK;
 }
 
 int stack_backward(Work& w, Stack& s, const std::vector<LayerOff>& off, float* dres, float* G, int B, int N, hipStream_t st,
-                   bvc_bucket_fn on_bucket, void* user, const LayerTail* last) {
+                   bvc_bucket_fn on_bucket, void* user, const LayerTail* last, const LayerFirst* first) {
     for (int i = s.nlayers - 1; i >= 0; --i)
-        TRY(layer_backward(w, s, i, off[i], s.act[i].x_in, dres, G, B, N, st, on_bucket, user, i + 1 == s.nlayers ? last : nullptr));
+        TRY(layer_backward(w, s, i, off[i], s.act[i].x_in, dres, G, B, N, st, on_bucket, user, i + 1 == s.nlayers ? last : nullptr, i == 0 ? first : nullptr));
     return BVC_OK;
 }
 

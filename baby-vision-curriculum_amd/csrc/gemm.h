@@ -52,7 +52,9 @@ constexpr int kMaxGroup = 4;
 //               before the in-place attention instantiations; 0 (default) = in place.  Read when a stack is allocated (A/B only)
 //   dec_tail:   1 (default) = the last decoder layer of the VideoMAE pre-training step runs everything behind its qkv product on the decoded
 //               rows only (stack.h LayerTail) when the shapes allow; 0 = on all rows, as before that mode existed (A/B)
-struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; int deterministic = 0; int head_pad = 0; int dec_tail = 1; };
+//   dec_first:  the first decoder layer of the VideoMAE pre-training step computes LayerNorm 1 and qkv of the mask rows once per position
+//               (stack.h LayerFirst): -1 (default) = the measured gate, 1 = whenever the shapes allow, 0 = never (A/B)
+struct Options { int gemm8 = 0; int dw_overlap = 0; int row_ln = 0; int row_stagger = 1; int deterministic = 0; int head_pad = 0; int dec_tail = 1; int dec_first = -1; };
 Options& options();
 
 // Workspace of the deterministic mode: library-owned, grow-only, one buffer per (device, stream) - kernels on one stream use it in

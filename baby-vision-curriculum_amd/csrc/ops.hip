@@ -34,6 +34,7 @@ int bvc_set_option(const char* name, int value) {
     else if (!strcmp(name, "deterministic")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: deterministic takes 0 / 1"); options().deterministic = value; }
     else if (!strcmp(name, "head_pad")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: head_pad takes 0 / 1"); options().head_pad = value; }
     else if (!strcmp(name, "dec_tail")) { BVC_REQUIRE(value == 0 || value == 1, "set_option: dec_tail takes 0 / 1"); options().dec_tail = value; }
+    else if (!strcmp(name, "dec_first")) { BVC_REQUIRE(value >= -1 && value <= 1, "set_option: dec_first takes -1 / 0 / 1"); options().dec_first = value; }
     else BVC_REQUIRE(false, "set_option: unknown option '%s'", name);
     return BVC_OK;
 }
@@ -45,6 +46,7 @@ int bvc_get_option(const char* name) {
     if (name && !strcmp(name, "deterministic")) return options().deterministic;
     if (name && !strcmp(name, "head_pad")) return options().head_pad;
     if (name && !strcmp(name, "dec_tail")) return options().dec_tail;
+    if (name && !strcmp(name, "dec_first")) return options().dec_first;
     bvc::set_error("get_option: unknown option '%s'", name ? name : "(null)");
     return BVC_ERR_INVALID;
 }
@@ -202,6 +204,14 @@ int bvc_op_row_ln_selected(int tokens, int width, int mlp_width, int heads) {
     s.hd = width / heads; s.hdp = attn_width(s.hd); s.Da = heads * s.hdp;
     return fuse_row_ln(s, tokens) ? 1 : 0;
 }
+int bvc_op_dec_first_selected(int clips, int decoder_layers) {
+    if (clips <= 0 || decoder_layers <= 0) return 0;
+    Work w;
+    Stack s;
+    s.D = 384; s.I = 1536; s.H = 6; s.nlayers = decoder_layers; s.eps = 0.f; s.x_out = nullptr;
+    s.hd = 64; s.hdp = attn_width(s.hd); s.Da = s.H * s.hdp;
+    return layer_first_ok(w, s, clips, 1, 1) ? 1 : 0;
+}
 int bvc_op_sgd_step_segments(float* params, float* grads, float* momentum_buf, int64_t n, const int64_t* seg_start, const int32_t* seg_group,
                              const int32_t* blk_seg, int nseg, const bvc_sgd_groups* groups, const float* grad_scale, const float* found_inf,
                              int write_unscaled_grads, void* bf16_shadow, void* stream) {
@@ -310,6 +320,15 @@ int bvc_op_dual_mask_index(const uint8_t* mask, const uint8_t* decode_mask, int 
     BVC_REQUIRE(mask && decode_mask && vis_idx && dec_idx && status, "op_dual_mask_index: null argument");
     BVC_REQUIRE(B >= 1 && L >= 1 && nvis >= 1 && nvis < L && ndec >= 1 && ndec <= L - nvis, "op_dual_mask_index: bad counts (L %d, nvis %d, ndec %d)", L, nvis, ndec);
     return launch_dual_mask_index(mask, decode_mask, B, L, nvis, ndec, vis_idx, dec_idx, status, (hipStream_t)stream);
+}
+int bvc_op_dec_slot(const int* dec_idx, int* dec_slot, int B, int L, int ndec, void* stream) {
+    BVC_REQUIRE(dec_idx && dec_slot && B >= 1 && L >= 1 && ndec >= 1 && ndec <= L, "op_dec_slot: bad argument");
+    return launch_dec_slot(dec_idx, dec_slot, B, L, ndec, (hipStream_t)stream);
+}
+int bvc_op_first_reduce(const void* dqkv, const int* dec_slot, int B, int L, int Ld, int nvis, int W, float* S, void* hi_bf16, void* lo_bf16,
+                        void* stream) {
+    BVC_REQUIRE(dqkv && dec_slot, "op_first_reduce: null argument");
+    return launch_first_reduce((const bf16_t*)dqkv, dec_slot, B, L, Ld, nvis, W, S, (bf16_t*)hi_bf16, (bf16_t*)lo_bf16, (hipStream_t)stream);
 }
 int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A, int B, int nvis, int T, int C, int H, int W, int ts,
                           int ps, void* stream) {

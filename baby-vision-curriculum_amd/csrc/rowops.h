@@ -68,6 +68,19 @@ int launch_poison_on_status(float* x, size_t count, const int* status, hipStream
 int launch_labels(PixelSrc clip, const int* dec_idx, float* labels, int B, int ndec, PatchGeom pg, int norm_pix, hipStream_t s);
 int launch_fill_masked(float* xfull, const float* mask_token, const float* pos, const int* dec_idx, int B, int Ld, int nvis,
                        int ndec, int D, hipStream_t s);
+// The first decoder layer by position (stack.h LayerFirst):
+// dec_slot [B][L] = the slot of position p among clip b's decoded rows (dec_idx [B][ndec]), -1 where the clip does not decode p
+int launch_dec_slot(const int* dec_idx, int* dec_slot, int B, int L, int ndec, hipStream_t s);
+// full-layout qkv (bf16, W columns) from the compact visible rows and the table rows t2[dec_idx]; the f32 mask rows of x_full from t0[dec_idx]
+int launch_first_assemble(const bf16_t* qkv_vis, const bf16_t* t2, const float* t0, const int* dec_idx, bf16_t* qkv, float* xfull, int B,
+                          int nvis, int ndec, int W, int D, hipStream_t s);
+// S[p][:] = sum over clips, ascending, of dqkv[b][nvis + dec_slot[b][p]][:] in f32 (no atomics, the same bits on every run); outputs S
+// (f32 [L][W]) and / or its bf16 pair hi + lo
+int launch_first_reduce(const bf16_t* dqkv, const int* dec_slot, int B, int L, int Ld, int nvis, int W, float* S, bf16_t* hi, bf16_t* lo,
+                        hipStream_t s);
+int launch_gather_rows_copy_bf16(const bf16_t* in, RowMap rm, bf16_t* out, int M, int W, hipStream_t s);
+// hi + lo = a + b (b may be null) as a bf16 pair, n elements each: hi = bf16(a + b), lo = bf16(a + b - hi)
+int launch_pair_split(const float* a, const float* b, bf16_t* hi, bf16_t* lo, size_t n, hipStream_t s);
 int launch_sgd_step(float* p, float* g, float* buf, size_t n, float lr, float momentum, float dampening, float wd, int nesterov,
                     int first, int maximize, const float* grad_scale, const float* found_inf, int write_grad, bf16_t* shadow,
                     hipStream_t s);

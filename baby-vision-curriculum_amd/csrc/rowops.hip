@@ -885,6 +885,105 @@ __global__ void fill_masked_kernel(float* __restrict__ xfull, const float* __res
     reinterpret_cast<f32x4*>(xfull + ((size_t)b * Ld + nvis + j) * D)[c] = mt + pe;
 }
 
+// ============================================================================ first decoder layer by position (stack.h LayerFirst)
+// dec_slot[b][p] = j where dec_idx[b][j] == p; the caller fills dec_slot with -1 first (positions clip b does not decode keep it)
+__global__ void dec_slot_kernel(const int* __restrict__ dec_idx, int* __restrict__ dec_slot, int B, int L, int ndec) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * ndec) return;
+    const int b = (int)(i / ndec), p = dec_idx[i];
+    if ((unsigned)p < (unsigned)L) dec_slot[(size_t)b * L + p] = (int)(i % ndec);
+}
+
+// qkv[b][r][:] = r < nvis ? qkv_vis[b][r][:] : t2[dec_idx[b][r - nvis]][:]  (bf16, W columns, 16 bytes per item), and
+// x_full[b][nvis + j][:] = t0[dec_idx[b][j]][:]                             (f32, D columns: what fill_masked_kernel writes)
+__global__ void first_assemble_kernel(const bf16_t* __restrict__ qkv_vis, const bf16_t* __restrict__ t2, const float* __restrict__ t0,
+                                      const int* __restrict__ dec_idx, bf16_t* __restrict__ qkv, float* __restrict__ xfull, int B,
+                                      int nvis, int ndec, int W, int D) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int wch = W >> 3, dch = D >> 2, Ld = nvis + ndec;
+    const size_t n1 = (size_t)B * Ld * wch;
+    if (i < n1) {
+        const size_t row = i / wch;
+        const int c = (int)(i % wch), b = (int)(row / Ld), r = (int)(row % Ld);
+        const bf16_t* src = r < nvis ? qkv_vis + ((size_t)b * nvis + r) * W : t2 + (size_t)dec_idx[(size_t)b * ndec + (r - nvis)] * W;
+        reinterpret_cast<uint4*>(qkv + row * W)[c] = reinterpret_cast<const uint4*>(src)[c];
+        return;
+    }
+    const size_t j = i - n1;
+    if (j >= (size_t)B * ndec * dch) return;
+    const size_t m = j / dch;
+    const int c = (int)(j % dch), b = (int)(m / ndec), jj = (int)(m % ndec);
+    reinterpret_cast<f32x4*>(xfull + ((size_t)b * Ld + nvis + jj) * D)[c] = reinterpret_cast<const f32x4*>(t0 + (size_t)dec_idx[m] * D)[c];
+}
+
+// S[p][c] = sum over the clips b = 0 .. B-1, in that order, of dqkv[b][nvis + dec_slot[b][p]][c] (clips with slot -1 add nothing), f32.
+// One wave per (position, 512 columns), 16 bytes per lane and clip; eight clips' rows are in flight before they are added, in clip
+// order.  Outputs (each optional): S as f32, and its bf16 pair hi = bf16(S), lo = bf16(S - hi).
+constexpr int kFirstReduceClips = 8;
+__global__ __launch_bounds__(64) void first_reduce_kernel(const bf16_t* __restrict__ dqkv, const int* __restrict__ dec_slot, int B, int L,
+                                                          int Ld, int nvis, int W, float* __restrict__ S, bf16_t* __restrict__ hi,
+                                                          bf16_t* __restrict__ lo) {
+    const int p = blockIdx.x, col = (blockIdx.y * 64 + threadIdx.x) * 8;
+    if (col >= W) return;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int b0 = 0; b0 < B; b0 += kFirstReduceClips) {
+        uint4 v[kFirstReduceClips];
+#pragma unroll
+        for (int u = 0; u < kFirstReduceClips; ++u) {
+            const int b = b0 + u;
+            const int slot = b < B ? dec_slot[(size_t)b * L + p] : -1;
+            v[u] = slot >= 0 ? *reinterpret_cast<const uint4*>(dqkv + ((size_t)b * Ld + nvis + slot) * W + col) : uint4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int u = 0; u < kFirstReduceClips; ++u) {
+            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[2 * e] += __uint_as_float(w[e] << 16);
+                acc[2 * e + 1] += __uint_as_float(w[e] & 0xffff0000u);
+            }
+        }
+    }
+    const size_t o = (size_t)p * W + col;
+    if (S) {
+        *reinterpret_cast<f32x4*>(S + o) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+        *reinterpret_cast<f32x4*>(S + o + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    }
+    if (hi) {
+        uint32_t h[4], l[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            h[e] = pack2bf(acc[2 * e], acc[2 * e + 1]);
+            l[e] = pack2bf(acc[2 * e] - __uint_as_float(h[e] << 16), acc[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u));
+        }
+        *reinterpret_cast<uint4*>(hi + o) = uint4{h[0], h[1], h[2], h[3]};
+        *reinterpret_cast<uint4*>(lo + o) = uint4{l[0], l[1], l[2], l[3]};
+    }
+}
+
+// out bf16 [M][W] = in bf16 [map_row(m)][W]
+__global__ void gather_rows_copy_bf16_kernel(const bf16_t* __restrict__ in, RowMap rm, bf16_t* __restrict__ out, int M, int W) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // 16-byte item
+    const int nch = W >> 3;
+    if (i >= (size_t)M * nch) return;
+    const int m = (int)(i / nch), c = (int)(i % nch);
+    reinterpret_cast<uint4*>(out + (size_t)m * W)[c] = reinterpret_cast<const uint4*>(in + (size_t)map_row(m, rm) * W)[c];
+}
+
+// v = a + b (b may be null; n float4 items each) as a bf16 pair: hi = bf16(v), lo = bf16(v - hi)
+__global__ void pair_split_kernel(const float* __restrict__ a, const float* __restrict__ b, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo,
+                                  size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // float4 item
+    if (i >= n) return;
+    f32x4 v = reinterpret_cast<const f32x4*>(a)[i];
+    if (b) v += reinterpret_cast<const f32x4*>(b)[i];
+    const uint32_t h0 = pack2bf(v[0], v[1]), h1 = pack2bf(v[2], v[3]);
+    const uint32_t l0 = pack2bf(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xffff0000u));
+    const uint32_t l1 = pack2bf(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xffff0000u));
+    reinterpret_cast<uint2*>(hi)[i] = uint2{h0, h1};
+    reinterpret_cast<uint2*>(lo)[i] = uint2{l0, l1};
+}
+
 // loss = sum(partials) / count, fixed summation order; NaN if the mask index kernel flagged a bad mask
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ partial, int n, double count,
                                                             const int* __restrict__ status, float* __restrict__ loss) {
@@ -2005,6 +2104,45 @@ int launch_labels(PixelSrc clip, const int* dec_idx, float* labels, int B, int n
 int launch_fill_masked(float* xfull, const float* mask_token, const float* pos, const int* dec_idx, int B, int Ld, int nvis,
                        int ndec, int D, hipStream_t s) {
     hipLaunchKernelGGL(fill_masked_kernel, dim3(blocks_for((size_t)B * ndec * (D / 4))), dim3(256), 0, s, xfull, mask_token, pos, dec_idx, B, Ld, nvis, ndec, D);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_dec_slot(const int* dec_idx, int* dec_slot, int B, int L, int ndec, hipStream_t s) {
+    BVC_CHECK_HIP(hipMemsetAsync(dec_slot, 0xff, (size_t)B * L * sizeof(int), s));
+    hipLaunchKernelGGL(dec_slot_kernel, dim3(blocks_for((size_t)B * ndec)), dim3(256), 0, s, dec_idx, dec_slot, B, L, ndec);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_first_assemble(const bf16_t* qkv_vis, const bf16_t* t2, const float* t0, const int* dec_idx, bf16_t* qkv, float* xfull, int B,
+                          int nvis, int ndec, int W, int D, hipStream_t s) {
+    BVC_REQUIRE(W % 8 == 0 && D % 4 == 0, "first_assemble: W must be a multiple of 8, D of 4");
+    const size_t items = (size_t)B * (nvis + ndec) * (W / 8) + (size_t)B * ndec * (D / 4);
+    hipLaunchKernelGGL(first_assemble_kernel, dim3(blocks_for(items)), dim3(256), 0, s, qkv_vis, t2, t0, dec_idx, qkv, xfull, B, nvis, ndec, W, D);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_first_reduce(const bf16_t* dqkv, const int* dec_slot, int B, int L, int Ld, int nvis, int W, float* S, bf16_t* hi, bf16_t* lo,
+                        hipStream_t s) {
+    BVC_REQUIRE(B >= 1 && L >= 1 && W >= 8 && W % 8 == 0 && nvis >= 0 && Ld > nvis, "first_reduce: bad shape (B %d, L %d, Ld %d, nvis %d, W %d)", B, L, Ld, nvis, W);
+    BVC_REQUIRE((hi == nullptr) == (lo == nullptr) && (S || hi), "first_reduce: no output, or half of the bf16 pair");
+    hipLaunchKernelGGL(first_reduce_kernel, dim3(L, (W + 511) / 512), dim3(64), 0, s, dqkv, dec_slot, B, L, Ld, nvis, W, S, hi, lo);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_gather_rows_copy_bf16(const bf16_t* in, RowMap rm, bf16_t* out, int M, int W, hipStream_t s) {
+    BVC_REQUIRE(W % 8 == 0, "gather_rows_copy_bf16: W must be a multiple of 8");
+    hipLaunchKernelGGL(gather_rows_copy_bf16_kernel, dim3(blocks_for((size_t)M * (W / 8))), dim3(256), 0, s, in, rm, out, M, W);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_pair_split(const float* a, const float* b, bf16_t* hi, bf16_t* lo, size_t n, hipStream_t s) {
+    BVC_REQUIRE(n % 4 == 0 && n > 0, "pair_split: the element count must be a positive multiple of 4");
+    hipLaunchKernelGGL(pair_split_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, s, a, b, hi, lo, n / 4);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

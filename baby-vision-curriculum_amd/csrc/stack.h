@@ -118,6 +118,34 @@ struct LayerTail { int nvis, ndec; };
 // may this stack's last layer run in tail mode for B clips of nvis + ndec rows (options, shapes, gate)?
 bool layer_tail_ok(const Work& w, const Stack& s, int B, int nvis, int ndec);
 
+// First mode of a FIRST layer whose trailing `ndec` rows of every clip enter as token + pos[p] (the VideoMAE decoder: mask_token + the
+// sinusoid of the row's position p, one of L): such a row's first LayerNorm and qkv row depend on p alone.  With a LayerFirst,
+// layer_forward computes them once per position (T1 = LN1(t0), T2 = T1 Wqkv^T + b: L rows), runs LayerNorm 1 and the qkv product of the
+// B * nvis visible rows compact, and assembles the full-layout qkv the attention kernels read (and the f32 mask rows of x_in, the residual
+// input of proj).  layer_backward sums dqkv over the clips that decode a position (S, f32, clips in ascending order) and derives the mask
+// rows' share of dWqkv, dbqkv, LayerNorm 1's dgamma / dbeta and d token from S, T1 and the per-position statistics - LayerNorm's backward
+// is linear in its incoming gradient once xhat and rstd are fixed; S and S Wqkv travel as bf16 hi + lo pairs, so the by-position
+// products carry no rounding the per-row ones did not.  The visible rows take the unfused path (dX qkv, then the LayerNorm backward
+// through a row map; where the stack's LayerNorms run in the epilogues, which hand the backward an unrounded dX, as a pair too).  The mask rows of dres are left as the residual gradient that reaches LayerNorm 1: the caller's column sum over them
+// plus what layer_backward adds to `dtoken` is the token's gradient.  Buffers (owned by the caller):
+struct LayerFirst {
+    int nvis, ndec, L;
+    const int* dec_idx;     // [B][ndec] position of every decoded row
+    const int* dec_slot;    // [B][L]    slot of position p among clip b's decoded rows, or -1
+    const float* t0;        // f32 [2 L][D]  token + pos[p], the L rows twice (the hi and the lo half of a pair meet the same statistics)
+    float *tmean, *trstd;   // f32 [2 L]
+    bf16_t* ln1c;           // bf16 [B nvis + 2 L][D]    LayerNorm 1 of the visible rows, compact, then T1 twice
+    bf16_t* qc;             // bf16 [B nvis + 2 L][3 D]  forward: qkv of the visible rows, then T2; backward: their dqkv, then S hi, S lo
+    float *xt, *dt;         // f32 [2 L][D]  S Wqkv (hi rows, lo rows); the LayerNorm backward of the table rows
+    bf16_t* dyt;            // bf16 [2 L][D] xt's two halves added, as a pair
+    float* part;            // ln_bwd_workspace_floats_upto(2 L, D)
+    float* xv;              // f32 [B nvis][D]     dX qkv of the visible rows when the layer's LayerNorms run in the epilogues (f32 there too)
+    bf16_t* dyv;            // bf16 [2 B nvis][D]  ... as a pair
+    float* dtoken;          // f32 [D] gradient of the token (set for the backward)
+};
+// may this stack's first layer run in first mode for B clips (options, shapes, the measured gate)?
+bool layer_first_ok(const Work& w, const Stack& s, int B, int nvis, int ndec);
+
 LayerOff add_layer_params(ParamTable& t, const std::string& prefix, int64_t d, int64_t inter, bool hf_names);
 int alloc_stack(Arena& a, Stack& s, int D, int I, int H, int nlayers, float eps, size_t M, size_t BHN);
 // MD = max tokens x width, MI = max tokens x intermediate, over every stack that will use this scratch
@@ -133,8 +161,9 @@ void begin_backward(Work& w);
 // layer's fc2 epilogue), nullptr for the last layer or when the caller reuses one set of activations
 // tail: see LayerTail (the caller asks layer_tail_ok first and passes the same descriptor to the layer's backward); x_out then holds
 // the B * ndec decoded rows only
+// first: see LayerFirst (layer 0 only; the caller asks layer_first_ok first and passes the same descriptor to the layer's backward)
 int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* x_out, int B, int N, hipStream_t st,
-                  const LayerOff* next = nullptr, const LayerTail* tail = nullptr);
+                  const LayerOff* next = nullptr, const LayerTail* tail = nullptr, const LayerFirst* first = nullptr);
 // Do the LayerNorms of this stack run inside the epilogues of the 384-wide products next to them (gemm8.hip, EPI_RESID_LN / EPI_DLN)?
 bool fuse_row_ln(const Stack& s, int M);
 // bvc_*_set_drop: validates the public description and copies path_scale ([nlayers][2][samples], device) into the context's buffer
@@ -149,6 +178,6 @@ inline const Gate* top_gate(const DropState& d, Gate& store) {
     return &store;
 }
 int layer_backward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* dres, float* G, int B, int N,
-                   hipStream_t st, bvc_bucket_fn on_bucket, void* user, const LayerTail* tail = nullptr);
+                   hipStream_t st, bvc_bucket_fn on_bucket, void* user, const LayerTail* tail = nullptr, const LayerFirst* first = nullptr);
 
 }  // namespace bvc

@@ -184,6 +184,39 @@ int plan_dw(GemmProblem* g, int n) {
             // (up to 24 splits since round 4: the head's 12 tiles x 21 = 252 units, 498 vs 564 us with 16 splits at 256 clips -
             //  profiles/r04_o_head_dw_splits.txt; an atomic pass over its 2.4 MB of outputs per split is noise)
             const int smax = std::max(1, std::min(24, ksteps / (g8 > 0 ? 2 : 16)));
+            // Members whose K ranges differ by 2 x and more (first mode: the qkv member contracts over the visible rows and the
+            // position tables, a ninth of the others' rows at the benchmark's shape) get splits of their own: every unit about
+            // as long as the longest member's, so that the short member's tiles do not hold a CU for a fraction of the launch
+            // while the split is chosen for them.  s_i = ceil(K tiles_i / unit length); the unit length is the longest member's
+            // K tiles over sp, sp chosen by the same cost as below.  The walk and the deterministic reduce take splits per problem.
+            int kmax = 0;
+            for (int i = 0; i < n; ++i) kmax = std::max(kmax, (g[i].K + 63) / 64);
+            if (kmax >= 2 * ksteps) {
+                const int per_min = g8 > 0 ? 2 : 16;
+                int best_sp = 0;
+                double best_cost = 1e300;
+                for (int sp = 1; sp <= std::max(1, std::min(24, kmax / per_min)); ++sp) {
+                    const int len = (kmax + sp - 1) / sp;
+                    int units = 0, longest = 0;
+                    for (int i = 0; i < n; ++i) {
+                        const int kt = (g[i].K + 63) / 64;
+                        const int si = std::max(1, std::min((kt + len - 1) / len, std::max(1, kt / per_min)));
+                        units += ((g[i].M + 127) / 128) * ((g[i].N + 383) / 384) * si;
+                        longest = std::max(longest, (kt + si - 1) / si);
+                    }
+                    const int rounds = (units + 255) / 256;
+                    const double cost = (double)rounds * longest + 4.0 * rounds;
+                    if (cost < best_cost * 0.999) { best_cost = cost; best_sp = sp; }
+                }
+                const int len = (kmax + best_sp - 1) / best_sp;
+                int units = 0;
+                for (int i = 0; i < n; ++i) {
+                    const int kt = (g[i].K + 63) / 64;
+                    g[i].split_k = std::max(1, std::min((kt + len - 1) / len, std::max(1, kt / per_min)));
+                    units += ((g[i].M + 127) / 128) * ((g[i].N + 383) / 384) * g[i].split_k;
+                }
+                if (units >= (g8 > 0 ? 1 : 160)) return 12;
+            }
             int best = 1;
             double best_cost = 1e300;
             for (int sp = 1; sp <= smax; ++sp) {
@@ -262,6 +295,21 @@ bool layer_tail_ok(const Work& w, const Stack& s, int B, int nvis, int ndec) {
     return fuse_row_ln(s, B * (nvis + ndec)) && gemm_row_ln_ok(B * ndec, s.D, s.D);
 }
 
+// First mode (stack.h LayerFirst): bvc_set_option("dec_first", 1 / 0 / -1) = on whenever the shapes allow / off / the measured gate.  A
+// stack of one layer keeps it off (that layer may be the tail layer), and so do padded heads (the padded qkv copies are not wired
+// through the by-position products) and a gate on the branches.
+// Same-process A/B of the base step, forward + backward (profiles/dec_first_bench_parent_ab.txt): 256 clips -0.88 / -0.98 ms of 76.9, 64 clips
+// -0.17 / -0.18 of 22.3, 16 clips +0.03 / +0.04 of 7.7 - the by-position launches cost more than they save there.  Between 16 and 64: not measured.
+constexpr int kFirstAutoClips = 64;
+bool layer_first_ok(const Work& w, const Stack& s, int B, int nvis, int ndec) {
+    const int mode = options().dec_first;
+    if (mode == 0 || s.nlayers < 2 || nvis < 1 || ndec < 1 || B < 1) return false;
+    if (w.drop != nullptr && w.drop->active) return false;
+    if (s.hdp != s.hd || s.D % 8 != 0) return false;
+    if (mode > 0) return true;
+    return B >= kFirstAutoClips;
+}
+
 int alloc_drop(Arena& a, DropState& d, int nlayers, int max_samples) {
     d.nlayers = nlayers;
     d.max_samples = max_samples;
@@ -299,7 +347,7 @@ int take_drop(DropState& d, int samples, int rows, const char* who) {
 }
 
 int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_in, float* x_out, int B, int N, hipStream_t st,
-                  const LayerOff* next, const LayerTail* tail) {
+                  const LayerOff* next, const LayerTail* tail, const LayerFirst* first) {
     LayerAct& a = s.act[li];
     const int D = s.D, I = s.I, M = B * N;
     // tail mode: everything behind the qkv product runs on the Mq = B * ndec decoded rows, stored compact (ctx, lse, h, ln2o, mean2, rstd2,
@@ -314,8 +362,15 @@ int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_i
     const int gl = w.drop_layer >= 0 ? w.drop_layer : li;
     const bool fuse = !gated && fuse_row_ln(s, M);
     if (li == 0) s.ln1_ready = false;
+    if (first) BVC_REQUIRE(li == 0 && !tail && x_in == a.x_in && first->nvis + first->ndec == N && layer_first_ok(w, s, B, first->nvis, first->ndec),
+                           "layer_forward: first mode is not available for this layer");
     // (the previous layer's fc2 epilogue may have left this layer's first LayerNorm behind)
-    if (!(fuse && s.ln1_ready)) TRY(launch_ln_fwd(x_in, identity_rows(), P + o.ln1w, P + o.ln1b, a.ln1o, a.mean1, a.rstd1, M, D, eps, st));
+    if (first) {
+        // LayerNorm 1 of the table rows (twice: stack.h) and of the visible rows, one qkv product over [visible | T1] -> [qkv | T2]
+        const int Mv = B * first->nvis;
+        TRY(launch_ln_fwd(first->t0, identity_rows(), P + o.ln1w, P + o.ln1b, first->ln1c + (size_t)Mv * D, first->tmean, first->trstd, 2 * first->L, D, eps, st));
+        TRY(launch_ln_fwd(x_in, RowMap{first->nvis, N, 0}, P + o.ln1w, P + o.ln1b, first->ln1c, a.mean1, a.rstd1, Mv, D, eps, st));
+    } else if (!(fuse && s.ln1_ready)) TRY(launch_ln_fwd(x_in, identity_rows(), P + o.ln1w, P + o.ln1b, a.ln1o, a.mean1, a.rstd1, M, D, eps, st));
     s.ln1_ready = false;
     const int Da = s.Da;
     const bool pad = s.hdp != s.hd;
@@ -326,7 +381,14 @@ int layer_forward(Work& w, Stack& s, int li, const LayerOff& o, const float* x_i
         TRY(launch_pad_heads(W + o.wqkv, P + o.bqkv, W + o.wo, s.wqkv_pad, s.bqkv_pad, s.wo_pad, D, s.H, s.hd, s.hdp, st));
         Wqkv = s.wqkv_pad; Wo = s.wo_pad; bqkv = s.bqkv_pad;
     }
-    {
+    if (first) {
+        const int Mf = B * first->nvis + first->L;
+        GemmProblem p = gemm(first->ln1c, (size_t)Mf * D, D, Wqkv, (size_t)3 * Da * D, D, Mf, 3 * Da, D, EPI_BF16, first->qc, 3 * Da);
+        p.bias = bqkv;
+        TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
+        TRY(launch_first_assemble(first->qc, first->qc + (size_t)B * first->nvis * 3 * Da, first->t0, first->dec_idx, a.qkv, a.x_in, B, first->nvis,
+                                  first->ndec, 3 * Da, D, st));
+    } else {
         GemmProblem p = gemm(a.ln1o, (size_t)M * D, D, Wqkv, (size_t)3 * Da * D, D, M, 3 * Da, D, EPI_BF16, a.qkv, 3 * Da);
         p.bias = bqkv;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
@@ -378,7 +440,7 @@ int join_side(Work& c_, int parity, hipStream_t st, bvc_bucket_fn on_bucket, voi
 // layout - the dX fc1 epilogue adds into its decoded rows through the segment map, the visible rows (zero on entry: the head sends them no
 // gradient) reach the dX qkv product untouched.
 int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x_in, float* dres, float* G, int B, int N,
-                   hipStream_t st, bvc_bucket_fn on_bucket, void* user, const LayerTail* tail) {
+                   hipStream_t st, bvc_bucket_fn on_bucket, void* user, const LayerTail* tail, const LayerFirst* first) {
     LayerAct& a = s.act[li];
     const int D = s.D, I = s.I, M = B * N;
     const int Mq = tail ? B * tail->ndec : M;
@@ -431,7 +493,25 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
     }
     if (tail) TRY(launch_attn_bwd_win(a.qkv, a.ctx, c_.dctx, a.lse, c_.delta, dqkv, B, N, s.H, s.hdp, tail->nvis, tail->ndec, st, sm_scale));
     else TRY(launch_attn_bwd(a.qkv, a.ctx, c_.dctx, a.lse, c_.delta, dqkv, B, N, s.H, s.hdp, st, sm_scale));
-    if (fuse) {      // dX of qkv with the first LayerNorm's backward in its epilogue: dres becomes d/d(layer input), dyb_next its bf16 copy
+    const int Mv = first ? B * first->nvis : 0, Lp = first ? first->L : 0;
+    if (first) {
+        // first mode: S hi / lo behind the compact visible dqkv rows (one K range for the weight gradient below); dX qkv of the visible rows
+        // as bf16 for the separate LayerNorm backward, of the S rows as f32, then as a pair.  The next bf16 copy is not produced: what
+        // follows the first layer of such a stack reads the f32 rows.
+        BVC_REQUIRE(li == 0 && !tail && !pad && !gated && first->nvis + first->ndec == N && first->dtoken, "layer_backward: first mode is not available for this layer");
+        const int W3 = 3 * Da;
+        bf16_t* shi = first->qc + (size_t)Mv * W3;
+        TRY(launch_first_reduce(dqkv, first->dec_slot, B, Lp, N, first->nvis, W3, nullptr, shi, shi + (size_t)Lp * W3, st));
+        TRY(launch_gather_rows_copy_bf16(dqkv, RowMap{first->nvis, N, 0}, first->qc, Mv, W3, st));
+        // (the visible rows: bf16 as the separate LayerNorm passes take it, or - where the off path's epilogue would have seen the f32 product -
+        //  f32 and then a pair, so that the two paths differ by no rounding of their own)
+        GemmProblem p = gemm(first->qc, (size_t)Mv * W3, W3, Wqkv, (size_t)W3 * D, D, Mv, D, W3, fuse ? EPI_F32 : EPI_BF16, fuse ? (void*)first->xv : (void*)c_.dln, D);
+        TRY(launch_gemm(&p, 1, GEMM_NN, -1, st));
+        if (fuse) TRY(launch_pair_split(first->xv, nullptr, first->dyv, first->dyv + (size_t)Mv * D, (size_t)Mv * D, st));
+        GemmProblem t = gemm(shi, (size_t)2 * Lp * W3, W3, Wqkv, (size_t)W3 * D, D, 2 * Lp, D, W3, EPI_F32, first->xt, D);
+        TRY(launch_gemm(&t, 1, GEMM_NN, -1, st));
+        TRY(launch_pair_split(first->xt, first->xt + (size_t)Lp * D, first->dyt, first->dyt + (size_t)Lp * D, (size_t)Lp * D, st));
+    } else if (fuse) {      // dX of qkv with the first LayerNorm's backward in its epilogue: dres becomes d/d(layer input), dyb_next its bf16 copy
         GemmProblem p = gemm(dqkv, (size_t)M * 3 * Da, 3 * Da, Wqkv, (size_t)3 * Da * D, D, M, D, 3 * Da, EPI_DLN, dres, D);
         p.C2 = dyb_next; p.ln_x = x_in; p.ln_mean = a.mean1; p.ln_rstd = a.rstd1; p.ln_gamma = P + o.ln1w;
         p.ln_part = c_.ln_part; p.ln_dgamma = G + o.ln1w; p.ln_dbeta = G + o.ln1b;
@@ -454,6 +534,10 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
         g[1] = gemm(dh, (size_t)Mq * I, I, a.ln2o, (size_t)Mq * D, D, I, D, Mq, EPI_F32, G + o.w1, D);
         g[2] = gemm(dhb, (size_t)Mq * D, D, a.ctx, (size_t)Mq * Da, Da, D, Da, Mq, EPI_F32, pad ? s.gwo_pad : G + o.wo, Da);
         g[3] = gemm(dqkv, (size_t)M * 3 * Da, 3 * Da, a.ln1o, (size_t)M * D, D, 3 * Da, D, M, EPI_F32, pad ? s.gwqkv_pad : G + o.wqkv, D);
+        if (first) {     // [visible dqkv | S hi | S lo]^T [LN1 visible | T1 | T1]: the mask rows' share rides in the same contraction
+            const int Kf = Mv + 2 * Lp;
+            g[3] = gemm(first->qc, (size_t)Kf * 3 * Da, 3 * Da, first->ln1c, (size_t)Kf * D, D, 3 * Da, D, Kf, EPI_F32, G + o.wqkv, D);
+        }
         g[0].rowsum = G + o.b2;     // bias gradients ride along as one extra MFMA column each
         g[1].rowsum = G + o.b1;
         g[2].rowsum = G + o.bo;
@@ -468,7 +552,14 @@ int layer_backward(Work& c_, Stack& s, int li, const LayerOff& o, const float* x
         if (pad)
             TRY(launch_unpad_head_grads(s.gwqkv_pad, s.gbqkv_pad, s.gwo_pad, G + o.wqkv, G + o.bqkv, G + o.wo, D, s.H, s.hd, s.hdp, ws));
     }
-    if (!fuse) TRY(launch_ln_bwd(c_.dln, x_in, identity_rows(), a.mean1, a.rstd1, P + o.ln1w, dres, 1, dyb_next, G + o.ln1w, G + o.ln1b, c_.ln_part, M, D, st,
+    if (first) {
+        const RowMap vis{first->nvis, N, 0};
+        TRY(launch_ln_bwd(fuse ? first->dyv : c_.dln, x_in, vis, a.mean1, a.rstd1, P + o.ln1w, dres, 1, nullptr, G + o.ln1w, G + o.ln1b, c_.ln_part, Mv, D, st));
+        if (fuse) TRY(launch_ln_bwd(first->dyv + (size_t)Mv * D, x_in, vis, a.mean1, a.rstd1, P + o.ln1w, dres, 1, nullptr, G + o.ln1w, G + o.ln1b, c_.ln_part, Mv, D, st));
+        TRY(launch_ln_bwd(first->dyt, first->t0, identity_rows(), first->tmean, first->trstd, P + o.ln1w, first->dt, 0, nullptr, G + o.ln1w, G + o.ln1b,
+                          first->part, 2 * Lp, D, st));
+        TRY(launch_colsum_f32(first->dt, identity_rows(), 2 * Lp, D, first->dtoken, st));
+    } else if (!fuse) TRY(launch_ln_bwd(c_.dln, x_in, identity_rows(), a.mean1, a.rstd1, P + o.ln1w, dres, 1, dyb_next, G + o.ln1w, G + o.ln1b, c_.ln_part, M, D, st,
                                  gated && li > 0 ? &g_below : nullptr));
     if (c_.overlap) {
         BVC_CHECK_HIP(hipEventRecord(c_.ev_join[par], c_.side));

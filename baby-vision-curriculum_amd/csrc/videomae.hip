@@ -107,6 +107,11 @@ struct bvc_ctx {
     // the last forward ran the last decoder layer in tail mode (stack.h LayerTail): dec.x_out and that layer's activations behind qkv
     // hold the B * ndec decoded rows, compact; its backward and the "dec<last>" tap follow suit
     bool tail_on = false;
+    // first mode of the first decoder layer (stack.h LayerFirst): the per-position tables and compact operands, allocated when the decoder
+    // has the shapes for it; first_on = the last forward ran that way (its backward follows suit)
+    int *dec_slot = nullptr, *pos_iota = nullptr;      // [B][L]; [2 L] = p mod L
+    LayerFirst first{};
+    bool first_on = false;
 };
 
 namespace {
@@ -211,6 +216,28 @@ int bvc_videomae_create_dual(const bvc_videomae_config* cfg, int max_batch, int 
                    std::max(ln_bwd_workspace_floats_upto((int)Mv, D), ln_bwd_workspace_floats_upto((int)Md, Dd))));
     TRY(upload_sinusoid(c->pos_enc, L, D));
     TRY(upload_sinusoid(c->pos_dec, L, Dd));
+    if (c->dec.nlayers >= 2 && c->dec.hdp == c->dec.hd) {
+        LayerFirst& f = c->first;
+        const size_t T = 2 * (size_t)L, Mf = Mv + T;
+        float* t0 = nullptr;
+        f.nvis = nvis; f.ndec = num_decoded; f.L = L;
+        TRY(c->arena.alloc(&c->dec_slot, B * L));
+        TRY(c->arena.alloc(&c->pos_iota, T));
+        TRY(c->arena.alloc(&t0, T * Dd));
+        TRY(c->arena.alloc(&f.tmean, T));
+        TRY(c->arena.alloc(&f.trstd, T));
+        TRY(c->arena.alloc(&f.ln1c, Mf * Dd));
+        TRY(c->arena.alloc(&f.qc, Mf * 3 * c->dec.Da));
+        TRY(c->arena.alloc(&f.xt, T * Dd));
+        TRY(c->arena.alloc(&f.dt, T * Dd));
+        TRY(c->arena.alloc(&f.dyt, T * Dd));
+        TRY(c->arena.alloc(&f.part, ln_bwd_workspace_floats_upto((int)T, Dd)));
+        TRY(c->arena.alloc(&f.xv, Mv * Dd));
+        TRY(c->arena.alloc(&f.dyv, 2 * Mv * Dd));
+        f.t0 = t0; f.dec_idx = c->dec_idx; f.dec_slot = c->dec_slot;
+        TRY(launch_iota_mod(c->pos_iota, (int)T, L, nullptr));
+        BVC_CHECK_HIP(hipStreamSynchronize(nullptr));
+    }
     guard.done = true;
     *out = c;
     return BVC_OK;
@@ -260,11 +287,19 @@ int bvc_videomae_forward_dual(bvc_ctx* c, const void* pixels_any, const bvc_pixe
         p.rowtok = c->vis_idx; p.pos = c->pos_dec; p.rin = nvis; p.rout = Ld;
         TRY(launch_gemm(&p, 1, GEMM_NT, -1, st));
     }
-    TRY(launch_fill_masked(c->dec.act[0].x_in, params + L.mask_token, c->pos_dec, c->dec_idx, B, Ld, nvis, ndec, Dd, st));
+    // the decoded rows enter as mask_token + pos[p]: in first mode the first layer works on the L-row table of them (twice over: stack.h) and
+    // writes the rows themselves when it assembles its qkv
+    c->first_on = c->dec_slot != nullptr && layer_first_ok(c->w, c->dec, B, nvis, ndec);
+    if (c->first_on) {
+        TRY(launch_dec_slot(c->dec_idx, c->dec_slot, B, Lq, ndec, st));
+        TRY(launch_fill_masked(const_cast<float*>(c->first.t0), params + L.mask_token, c->pos_dec, c->pos_iota, 1, 2 * Lq, 0, 2 * Lq, Dd, st));
+    } else {
+        TRY(launch_fill_masked(c->dec.act[0].x_in, params + L.mask_token, c->pos_dec, c->dec_idx, B, Ld, nvis, ndec, Dd, st));
+    }
     // the head reads the decoded rows only: the last layer computes nothing else behind its qkv product when the shapes allow (tail mode)
     const LayerTail lt{nvis, ndec};
     c->tail_on = layer_tail_ok(c->w, c->dec, B, nvis, ndec);
-    TRY(stack_forward(c->w, c->dec, L.dec, B, Ld, st, true, c->tail_on ? &lt : nullptr));
+    TRY(stack_forward(c->w, c->dec, L.dec, B, Ld, st, true, c->tail_on ? &lt : nullptr, c->first_on ? &c->first : nullptr));
     // last ndec tokens -> LayerNorm -> head, fused with the pixel-target MSE (HF:497-501,588-664); in tail mode x_out holds just those rows
     const RowMap tail = c->tail_on ? identity_rows() : RowMap{ndec, Ld, nvis};
     TRY(launch_ln_fwd(c->dec.x_out, tail, params + L.norm_w, params + L.norm_b, c->lnf, c->meanf, c->rstdf, Mm, Dd, cf.decoder_norm_eps, st));
@@ -325,7 +360,8 @@ int bvc_videomae_backward(bvc_ctx* c, const float* grad_loss, float* G, bvc_buck
                           G + L.norm_w, G + L.norm_b, c->w.ln_part, Mm, Dd, st));
     }
     if (on_bucket) on_bucket(L.norm_w, L.total - L.norm_w, user);
-    TRY(stack_backward(c->w, c->dec, L.dec, c->dres_dec, G, B, Ld, st, on_bucket, user, c->tail_on ? &lt : nullptr));
+    c->first.dtoken = G + L.mask_token;
+    TRY(stack_backward(c->w, c->dec, L.dec, c->dres_dec, G, B, Ld, st, on_bucket, user, c->tail_on ? &lt : nullptr, c->first_on ? &c->first : nullptr));
     // decoder input: mask token, encoder_to_decoder
     TRY(launch_colsum_f32(c->dres_dec, tail, Mm, Dd, G + L.mask_token, st));
     const RowMap headrows{nvis, Ld, 0};

@@ -102,32 +102,42 @@ def _gemm_rows(dev, B, add):
         us = _time(lambda: _ops.gemm(d, _ops.TN, tile))
         add(name, label, count, us, 2.0 * Mo * No * K, 2.0 * K * (Mo + No) + 4.0 * Mo * No)
 
-    def dw_group(label, M, Dm, Im, count):
-        dy, act, dh, ln2, dqkv = _rb(dev, M, Dm), _rb(dev, M, Im), _rb(dev, M, Im), _rb(dev, M, Dm), _rb(dev, M, 3 * Dm)
+    def dw_group(label, M, Dm, Im, count, Kq=None):
+        # Kq: the rows the qkv member contracts over when they are not the layer's M (first mode: visible rows + the position sums as a pair)
+        Kq = M if Kq is None else Kq
+        dy, act, dh, ln2, dqkv = _rb(dev, M, Dm), _rb(dev, M, Im), _rb(dev, M, Im), _rb(dev, M, Dm), _rb(dev, Kq, 3 * Dm)
+        lnq = ln2 if Kq == M else _rb(dev, Kq, Dm)
         shapes = [(Dm, Im), (Im, Dm), (Dm, Dm), (3 * Dm, Dm)]
         outs = [torch.zeros(s, device=dev) for s in shapes]
         bs = [torch.zeros(s[0], device=dev) for s in shapes]
         ds = [_ops.gemm_desc(dy, act, Dm, Im, M, E["F32"], outs[0], rowsum=bs[0]),
               _ops.gemm_desc(dh, ln2, Im, Dm, M, E["F32"], outs[1], rowsum=bs[1]),
               _ops.gemm_desc(dy, ln2, Dm, Dm, M, E["F32"], outs[2], rowsum=bs[2]),
-              _ops.gemm_desc(dqkv, ln2, 3 * Dm, Dm, M, E["F32"], outs[3], rowsum=bs[3])]
+              _ops.gemm_desc(dqkv, lnq, 3 * Dm, Dm, Kq, E["F32"], outs[3], rowsum=bs[3])]
         tile, split = _ops.plan_dw(ds)
         name = _ops.gemm_kernel_name(ds, _ops.TN, tile)
         us = _time(lambda: _ops.gemm(ds, _ops.TN, tile), iters=3)
-        fl = 2.0 * M * (2 * Dm * Im + 4 * Dm * Dm)
-        nb = 2.0 * M * (2 * Dm + 2 * Im + 2 * Dm + Dm + 3 * Dm) + 4.0 * (2 * Dm * Im + 4 * Dm * Dm)    # eight operand slices, four outputs
-        add(name, f"{label} (tile {tile}, split {split})", count, us, fl, nb)
+        fl = 2.0 * M * (2 * Dm * Im + Dm * Dm) + 2.0 * Kq * 3 * Dm * Dm
+        nb = 2.0 * M * (2 * Dm + 2 * Im + 2 * Dm) + 2.0 * Kq * (Dm + 3 * Dm) + 4.0 * (2 * Dm * Im + 4 * Dm * Dm)    # eight operand slices, four outputs
+        splits = split if Kq == M else "/".join(str(d.split_k) for d in ds)
+        add(name, f"{label} (tile {tile}, split {splits})", count, us, fl, nb)
 
     NT, NN = _ops.NT, _ops.NN
     # the decoder's LayerNorms inside the neighbouring products' epilogues (csrc/stack.hip: fuse_row_ln) at this batch?
     fused = bool(_lib.lib().bvc_op_row_ln_selected(Md, Dd, Id, 6))
+    # the first decoder layer by position (csrc/stack.h LayerFirst) at this batch?  Then layer 0 has products of its own ("dec0 ...") and
+    # the per-row qkv rows below count the layers 1 - 3
+    first = bool(_lib.lib().bvc_op_dec_first_selected(B, 4))
+    nq, Lp = (3, 1568) if first else (4, 0)
     one("patch embed", NT, Mv, D, 1536, "POS", 1)
     one("enc qkv", NT, Mv, 3 * D, D, "BF16", 12)
     one("enc proj", NT, Mv, D, D, "RESID", 12)
     one("enc fc1+GELU", NT, Mv, I, D, "GELU", 12)
     one("enc fc2", NT, Mv, D, I, "RESID", 12)
     one("enc->dec", NT, Mv, Dd, D, "E2D", 1)
-    one("dec qkv", NT, Md, 3 * Dd, Dd, "BF16", 4)
+    one("dec qkv", NT, Md, 3 * Dd, Dd, "BF16", nq)
+    if first:
+        one("dec0 qkv (visible rows, position table)", NT, Mv + Lp, 3 * Dd, Dd, "BF16", 1)
     if fused:
         one("dec proj + LayerNorm", NT, Md, Dd, Dd, "RESID_LN", 4)
     else:
@@ -143,7 +153,10 @@ def _gemm_rows(dev, B, add):
     one("dec dX fc2", NN, Md, Id, Dd, "DGELU", 4)
     one("dec dX fc1 + LayerNorm bwd" if fused else "dec dX fc1", NN, Md, Dd, Id, "DLN" if fused else "BF16", 4)
     one("dec dX proj", NN, Md, Dd, Dd, "BF16", 4)
-    one("dec dX qkv + LayerNorm bwd" if fused else "dec dX qkv", NN, Md, Dd, 3 * Dd, "DLN" if fused else "BF16", 4)
+    one("dec dX qkv + LayerNorm bwd" if fused else "dec dX qkv", NN, Md, Dd, 3 * Dd, "DLN" if fused else "BF16", nq)
+    if first:
+        one("dec0 dX qkv (visible rows)", NN, Mv, Dd, 3 * Dd, "F32" if fused else "BF16", 1)
+        one("dec0 dX qkv (position sums, bf16 pair)", NN, 2 * Lp, Dd, 3 * Dd, "F32", 1)
     one("enc->dec dX", NN, Mv, D, Dd, "F32_BF16", 1)
     one("enc dX fc2", NN, Mv, I, D, "DGELU", 12)
     one("enc dX fc1", NN, Mv, D, I, "BF16", 12)
@@ -152,7 +165,9 @@ def _gemm_rows(dev, B, add):
     dw_single("head dW", P, Dd, Mm, 1)
     dw_single("enc->dec dW", Dd, D, Mv, 1)
     dw_single("patch dW", D, 1536, Mv, 1)
-    dw_group("dec layer dW group", Md, Dd, Id, 4)
+    dw_group("dec layer dW group", Md, Dd, Id, nq)
+    if first:
+        dw_group("dec0 layer dW, qkv member by position", Md, Dd, Id, 1, Kq=Mv + 2 * Lp)
     dw_group("enc layer dW group", Mv, D, I, 12)
 
 

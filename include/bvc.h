@@ -67,6 +67,13 @@ const char* bvc_version(void);
  *                 epilogues ("row_ln"), the heads are 64 wide, a clip has more than 160 rows (below, the whole-head attention backward
  *                 serves) and no gate is set; otherwise, and with 0, the layer runs on all rows with the launches and the results of
  *                 earlier builds.  Read by every forward (its backward follows the forward).
+ *   "dec_first"   -1 (default) / 0 / 1: first mode of the VideoMAE pre-training step.  The decoded rows enter the FIRST decoder layer as
+ *                 mask_token + the sinusoid of their position, so that layer's LayerNorm 1 and qkv row of such a row depend on the position
+ *                 alone: they are computed once per position and copied into the qkv the attention kernels read, and in the backward
+ *                 the rows' share of the qkv weight and bias gradients, of LayerNorm 1's and of the mask token's gradient follows from
+ *                 the per-position sums of d qkv (f32, clips in ascending order: the same bits on every run).  The visible rows take the
+ *                 per-row path.  1 = whenever the decoder has more than one layer, unpadded heads and no gate; -1 = that, from the
+ *                 batch at which it was measured to pay; 0 = never (the launches and results of earlier builds).  Read by every forward.
  * bvc_get_option returns the value, or BVC_ERR_INVALID for an unknown name; bvc_set_option rejects values outside the list. */
 int bvc_set_option(const char* name, int value);
 int bvc_get_option(const char* name);
@@ -736,6 +743,16 @@ int bvc_op_mask_index(const uint8_t* mask, int B, int L, int nvis, int nmask, in
  * visible count is not nvis, its decoded count is not ndec, or a decoded token is not masked (vis_idx [B][nvis], dec_idx [B][ndec]) */
 int bvc_op_dual_mask_index(const uint8_t* mask, const uint8_t* decode_mask, int B, int L, int nvis, int ndec, int* vis_idx, int* dec_idx,
                            int* status, void* stream);
+/* 1 when a VideoMAE pre-training forward of `clips` clips runs its first decoder layer by position under the options in force ("dec_first";
+ * unpadded heads and no gate assumed), 0 otherwise */
+int bvc_op_dec_first_selected(int clips, int decoder_layers);
+/* dec_slot [B][L]: the slot j of position p among clip b's decoded tokens (dec_idx[b][j] == p), -1 where clip b does not decode p */
+int bvc_op_dec_slot(const int* dec_idx, int* dec_slot, int B, int L, int ndec, void* stream);
+/* S[p][c] = sum over clips b = 0 .. B-1, in that order, of dqkv[b][nvis + dec_slot[b][p]][c] (bf16 [B][Ld][W] in, f32 sums; a slot of -1
+ * adds nothing; W a multiple of 8).  S (f32 [L][W]) and / or the bf16 pair hi = bf16(S), lo = bf16(S - hi) ([L][W] each; both or
+ * neither).  No atomics: two runs give the same bits. */
+int bvc_op_first_reduce(const void* dqkv_bf16, const int* dec_slot, int B, int L, int Ld, int nvis, int W, float* S, void* hi_bf16,
+                        void* lo_bf16, void* stream);
 /* tube patches of the visible tokens in Conv3d weight order (HF:157-177) */
 int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A_bf16, int B, int nvis, int T, int C, int H, int W,
                           int ts, int ps, void* stream);

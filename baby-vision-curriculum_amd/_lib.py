@@ -222,6 +222,10 @@ SYMBOLS = {
     "bvc_op_attention_bwd_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                             ctypes.c_float, c_void_p]),
     "bvc_op_attention_probs": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p]),
+    "bvc_op_topk_workspace": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "bvc_op_topk_splits": (c_int, [c_int, c_int, c_int, c_int]),
+    "bvc_op_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int, c_int, c_float, c_void_p]),
     "bvc_op_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -567,6 +567,30 @@ int bvc_op_attention_bwd_scaled(const void* qkv, const void* ctx_in, const void*
  * the same bits on every run. */
 int bvc_op_attention_probs(const void* qkv, const float* lse, float* probs, int B, int N, int H, int head_dim, float softmax_scale,
                            void* stream);
+/* Embedding retrieval (csrc/retrieval.hip; the reference's notebooks/EvaluateEmbeddings.ipynb get_nn_score / topk_retrieval): for
+ * each of the Q f32 query rows (row stride ldq elements) the k <= 64 best of the N f32 key rows (row stride ldk elements) of D
+ * columns, as out_idx int32 [Q][k] and out_val f32 [Q][k].  metric 0 = cosine: score = q.key / (|q| |key|) with inverse norm 0
+ * for a zero row, out_val = the cosine distance 1 - score (sklearn cosine_distances); metric 1 = Euclidean: d2 = max(|q|^2 +
+ * |key|^2 - 2 q.key, 0), out_val = sqrt(d2) (sklearn euclidean_distances).  All arithmetic is f32: q.key is one fused
+ * multiply-add chain over d = 0 .. D-1 whatever tile, key split or chunk the pair falls into.  Each row of the outputs is ordered
+ * best first: out_val ascending (a non-increasing function of the score) and, among bit-equal out_val, out_idx ascending; with
+ * fewer than k keys the remaining slots hold index -1 and distance +inf.  The reported index is key_base + the key's row.
+ *   key_splits    0 = chosen by the library (bvc_op_topk_splits), else that many ranges of key tiles run as workgroups of their own
+ *                 (capped at the number of 128-key tiles); the result does not depend on it, bit for bit.
+ *   accumulate    1 = out_idx / out_val hold the result of earlier calls (same queries, metric and k, other keys): this call
+ *                 merges its keys into them, and a loop of calls over the chunks of a gallery gives the bits of one call over the
+ *                 whole gallery.  0 = they are overwritten.
+ *   workspace     bvc_op_topk_workspace(Q, N, D, k, key_splits) bytes (8-byte aligned; -1 for invalid sizes): row statistics and the
+ *                 per-split lists.  No [Q][N] array exists anywhere.
+ * Read: the D columns of the Q and N rows (never the ldq - D / ldk - D padding), and out_idx / out_val when accumulate.  Written:
+ * the Q * k indices, the Q * k values, the workspace; nothing else.  No atomics on floats (integer LDS counters only, and the order
+ * above makes the result independent of arrival order): the same bits on every run.  BVC_ERR_INVALID (bvc_last_error) and nothing
+ * launched for k outside 1 .. 64, a non-positive size, a null pointer, a stride below D or key_base + N beyond int. */
+int64_t bvc_op_topk_workspace(int Q, int N, int D, int k, int key_splits);
+/* what key_splits = 0 resolves to for this shape (-1 for invalid sizes) */
+int bvc_op_topk_splits(int Q, int N, int D, int k);
+int bvc_op_topk(const float* queries, int64_t ldq, const float* keys, int64_t ldk, int Q, int N, int D, int k, int metric,
+                int key_splits, int key_base, int accumulate, int* out_idx, float* out_val, void* workspace, void* stream);
 /* nn.LayerNorm forward/backward (HF:336-337,484); rows may be strided by (rin, rout, roff), rin<=0 = dense */
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y_bf16,
                          float* mean, float* rstd, int M, int D, float eps, void* stream);

@@ -226,6 +226,12 @@ SYMBOLS = {
     "bvc_op_topk_splits": (c_int, [c_int, c_int, c_int, c_int]),
     "bvc_op_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_colstats": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_linear_pass_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
+    "bvc_op_linear_pass_splits": (c_int, [c_int, c_int, c_int]),
+    "bvc_op_linear_pass_tile_rows": (c_int, [c_int]),
+    "bvc_op_linear_pass": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int, c_int, c_float, c_void_p]),
     "bvc_op_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

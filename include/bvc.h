@@ -591,6 +591,36 @@ int64_t bvc_op_topk_workspace(int Q, int N, int D, int k, int key_splits);
 int bvc_op_topk_splits(int Q, int N, int D, int k);
 int bvc_op_topk(const float* queries, int64_t ldq, const float* keys, int64_t ldk, int Q, int N, int D, int k, int metric,
                 int key_splits, int key_base, int accumulate, int* out_idx, float* out_val, void* workspace, void* stream);
+/* Linear separability (csrc/separability.hip; the reference's notebooks/EvaluateEmbeddings.ipynb get_separability_score with
+ * method='svm': StandardScaler + LinearSVC).  bvc_op_colstats: StandardScaler's statistics of the n f32 rows (row stride ldx
+ * elements) of D columns: mean f32 [D] and inv_std f32 [D] = 1 / sqrt(population variance), exactly 1 where the variance is exactly 0;
+ * sums in float64 in a fixed order, one rounding to f32 each.  Read: the D columns of the n rows (never the ldx - D padding);
+ * written: mean and inv_std.
+ * bvc_op_linear_pass: one evaluation for K one-vs-rest squared-hinge problems at once.  Row i is used as xs_i = [(x_i - mean) *
+ * inv_std (two f32 roundings), 1]: D + 1 columns, the last one carrying the (regularised) intercept; the standardised matrix is
+ * never stored.  W and V are f32 [K][D + 1]; column j of the outputs belongs to label class0 + j: y_ij = +1 where labels[i]
+ * (int32, on the device) == class0 + j, else -1 (a two-class problem is one column, class0 = 1).  z_ij = w_j . xs_i is one f32
+ * fused-multiply-add chain over d = 0 .. D starting at 0.
+ *   mode 0 GRAD      out_loss[j] = sum_i max(0, 1 - y z)^2,  out_G[j][d] = sum_i a_ij xs_id with a = -2 C y max(0, 1 - y z):
+ *                    C * out_loss + |w_j|^2 / 2 is the objective and out_G + W its gradient.
+ *   mode 1 HESSVEC   out_G[j][d] = sum_i a_ij xs_id with a = 2 C [1 - y z(W) > 0] (xs_i . v_j): out_G + V is the generalised
+ *                    Hessian at W times V.  out_loss is not used.
+ *   mode 2 DECISION  out_pred int32 [n] = the column of the largest z of the row (the smaller column among equal ones, as
+ *                    numpy.argmax), for K = 1 z > 0; out_dec f32 [n][K], when not null, receives z.  labels, V, C, out_G are not used.
+ * Sums over rows are f32 chains in ascending row order inside each of bvc_op_linear_pass_splits(n, D, K) contiguous row ranges
+ * (whole tiles of bvc_op_linear_pass_tile_rows(D) rows), and the ranges are added in ascending order: no atomics on floats, the
+ * same bits on every run.  Read: the D columns of the n rows - once per chunk of 32 columns of W, so once for K <= 32 and ceil(K / 32)
+ * times otherwise -, labels, mean, inv_std, W (V).  Written: the named outputs and the
+ * workspace (bvc_op_linear_pass_workspace(n, D, K, mode) bytes, -1 for invalid sizes; no [n][D] array exists in it).
+ * BVC_ERR_INVALID and nothing launched for a non-positive size, D above 1343, K above 1024 (more classes: a host loop over class
+ * chunks), an unknown mode, a null pointer among those the mode uses, a pointer that is not 4-byte aligned, or a stride below D. */
+int bvc_op_colstats(const float* x, int64_t ldx, int n, int D, float* mean, float* inv_std, void* stream);
+int64_t bvc_op_linear_pass_workspace(int n, int D, int K, int mode);
+int bvc_op_linear_pass_splits(int n, int D, int K);
+int bvc_op_linear_pass_tile_rows(int D);
+int bvc_op_linear_pass(const float* x, int64_t ldx, const int* labels, const float* mean, const float* inv_std, const float* W,
+                       const float* V, int n, int D, int K, int class0, int mode, float C, float* out_G, float* out_loss, int* out_pred,
+                       float* out_dec, void* workspace, void* stream);
 /* nn.LayerNorm forward/backward (HF:336-337,484); rows may be strided by (rin, rout, roff), rin<=0 = dense */
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y_bf16,
                          float* mean, float* rstd, int M, int D, float eps, void* stream);

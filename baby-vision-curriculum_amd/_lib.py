@@ -208,6 +208,10 @@ SYMBOLS = {
     "bvc_op_clip_post_workspace": (c_int64, [c_int, c_int, c_int]),
     "bvc_op_clip_post": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "bvc_clip_post_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "bvc_frame_randaug_bytes": (c_int, []),
+    "bvc_op_clip_randaug_workspace": (c_int64, [c_int, c_int, c_int]),
+    "bvc_op_clip_randaug": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bvc_clip_randaug_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "bvc_videomae_cls_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_encoder_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_cls_set_mix": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

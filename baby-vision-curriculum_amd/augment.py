@@ -23,6 +23,15 @@ whole letter set, ``c j b g o n``: it runs the stage above and then the post sta
 with one ``bvc_frame_post`` per output frame: ``'b'`` is PIL's ``ImageFilter.GaussianBlur`` (three box passes per direction, each
 rounded to uint8, in 8.24 fixed point), ``'o'`` RandomHorizontalFlip + PIL's ``Image.rotate(angle, NEAREST)`` (an inverse affine map in
 16.16 fixed point).  Both are integer arithmetic restated from Pillow: ``clip_post``, ``clip_post_host`` and PIL give the same bytes.
+
+RandAugment (the ``rand-m7-n4-mstd0.5-inc1`` family of the fine-tuning recipes) is a third stage (include/bvc.h, bvc_frame_randaug):
+
+    ra = bvc.RandAugment("rand-m7-n4-mstd0.5-inc1", generator=np.random.default_rng(seed))
+    clips = ra(clips)                              # [B, T, 3, H, W] uint8 on the device -> the same shape
+    aug = bvc.ClipAugment(224, augs="c", randaug="rand-m7-n4-mstd0.5-inc1", generator=...)      # or as ClipAugment's last stage
+
+Per clip it draws up to ``num_ops`` of the fifteen PIL operations ``RANDAUG_OPS`` with their parameters (``sample_randaug_params``);
+``rand_augment`` applies them, ``rand_augment_host`` is the host twin, and both give the bytes of the PIL calls.
 """
 import math
 
@@ -42,6 +51,13 @@ MAX_SCALE = 16      # BVC_AUG_MAX_SCALE
 FRAME_POST = np.dtype([("blur_r", "<i4"), ("blur_ww", "<u4"), ("blur_fw", "<u4"), ("gray", "<i4"), ("rotate", "<i4"), ("rot", "<i4", (6,))])
 assert FRAME_POST.itemsize == 44
 MAX_BLUR_RADIUS = 4.0      # BVC_AUG_MAX_BLUR_RADIUS
+# bvc_randaug_stage, 36 bytes, and bvc_frame_randaug, 296 bytes
+RANDAUG_MAX_OPS = 8        # BVC_RANDAUG_MAX_OPS
+RANDAUG_STAGE = np.dtype([("op", "<i4"), ("ival", "<i4"), ("fval", "<f4"), ("aff", "<i4", (6,))])
+FRAME_RANDAUG = np.dtype([("nops", "<i4"), ("fill", "u1", (4,)), ("stage", RANDAUG_STAGE, (RANDAUG_MAX_OPS,))])
+assert RANDAUG_STAGE.itemsize == 36 and FRAME_RANDAUG.itemsize == 296
+RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness",
+               "Sharpness", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
 
 
 def pack_order(ops):
@@ -295,6 +311,15 @@ def rotation_coeffs(angle, size):
     cx, cy = W / 2.0, H / 2.0
     m[2] = m[0] * -cx + m[1] * -cy + m[2] + cx
     m[5] = m[3] * -cx + m[4] * -cy + m[5] + cy
+    return affine_coeffs(m)
+
+
+def affine_coeffs(matrix):
+    """The six 16.16 coefficients of PIL's ``Image.transform(size, AFFINE, matrix, NEAREST)``: ``matrix`` = (a, b, c, d, e, f) maps output
+    (x, y) to source (a x + b y + c, d x + e y + f); fixed as ``rotation_coeffs`` fixes its matrix."""
+    m = [float(v) for v in matrix]
+    if len(m) != 6 or not all(math.isfinite(v) for v in m):
+        raise ValueError("affine_coeffs: six finite values")
 
     def fix(v):
         return int(math.floor(v * 65536.0 + 0.5))
@@ -403,11 +428,15 @@ class ClipAugment:
     ``flip`` defaults to 0.5 with 'o', RandomRotation's companion flip, and to 0 otherwise), then the post table with
     ``sample_post_params``; it runs ``clip_transform`` and, only if some entry blurs, turns gray or rotates, ``clip_post``.  With
     letters from ``c j g n`` alone and the same seed it returns exactly what ``ClipTransform`` returns.  ``last_table`` and
-    ``last_post_table`` keep the tables of the last call."""
+    ``last_post_table`` keep the tables of the last call.
+
+    ``randaug``: ``None`` (the default) draws nothing more and launches nothing more.  A ``RandAugment``, or a config string such as
+    ``"rand-m7-n4-mstd0.5-inc1"``, runs as the last stage on the ``[views * B, T, 3, size, size]`` clips: its table is drawn from this
+    object's generator after the two others (``sample`` then returns three tables, ``last_randaug_table`` keeps the third)."""
 
     def __init__(self, size, augs="cjo", crop_scale=(0.08, 1.0), jitter_strength=0.5, flip=None, consistent=True, generator=None,
                  views=1, crop_ratio=(3.0 / 4.0, 4.0 / 3.0), jitter_p=0.8, gray_p=0.2, extra_gray_p=0.5, blur_p=0.5,
-                 blur_radius=(0.1, 2.0), degrees=(-90.0, 90.0)):
+                 blur_radius=(0.1, 2.0), degrees=(-90.0, 90.0), randaug=None):
         if int(views) < 1:
             raise ValueError("views must be >= 1")
         for ch in augs:
@@ -425,22 +454,286 @@ class ClipAugment:
         self.generator = generator if generator is not None else np.random.default_rng()
         sample_params(1, 1, self.size, self.size, generator=np.random.default_rng(0), **self.kw)      # argument errors surface here
         sample_post_params(1, 1, self.size, generator=np.random.default_rng(0), **self.post_kw)
-        self.last_table = self.last_post_table = None
+        if randaug is not None and not isinstance(randaug, RandAugment):
+            randaug = RandAugment(randaug, consistent=consistent)
+        self.randaug = randaug
+        self.last_table = self.last_post_table = self.last_randaug_table = None
 
     def sample(self, batch, frames, src_size):
-        """(stage-one table, post table) for one batch, drawn in that order from the generator"""
+        """(stage-one table, post table) for one batch, drawn in that order from the generator; with ``randaug`` a third table after them"""
         table = sample_params(batch, frames, src_size, self.size, views=self.views, generator=self.generator, **self.kw)
         post = sample_post_params(batch, frames, self.size, views=self.views, generator=self.generator, **self.post_kw)
-        return table, post
+        if self.randaug is None:
+            return table, post
+        return table, post, self.randaug.sample(batch, frames, self.size, views=self.views, generator=self.generator)
 
     def __call__(self, clips, tables=None):
         _check_clips(clips)
         B, T, C, Hs, Ws = (int(v) for v in clips.shape)
         if C != 3:
             raise ValueError(f"clips have {C} channels; the transforms are defined for 3")
-        table, post = self.sample(B, T, (Hs, Ws)) if tables is None else tables
+        tables = self.sample(B, T, (Hs, Ws)) if tables is None else tuple(tables)
+        if len(tables) != (2 if self.randaug is None else 3):
+            raise ValueError("tables: (stage-one table, post table), and the RandAugment table when randaug is set")
+        table, post = tables[:2]
         self.last_table, self.last_post_table = table, post
         out = clip_transform(clips, table, self.size)
         if post_needed(post):
             out = clip_post(out, post)
+        if self.randaug is not None:
+            self.last_randaug_table = tables[2]
+            out = rand_augment(out, tables[2])
         return out.view(-1, T, 3, *self.size)
+
+
+# ---------------------------------------------------------------- RandAugment (bvc_frame_randaug)
+_RA_ID = {name: i for i, name in enumerate(RANDAUG_OPS)}
+_RA_SIGNED = frozenset(("Color", "Contrast", "Brightness", "Sharpness", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate"))
+_RA_ENHANCE = ("Color", "Contrast", "Brightness", "Sharpness")
+_RA_INT_RANGE = {"Posterize": 8, "Solarize": 256, "SolarizeAdd": 110}
+
+
+def _ra_name(op):
+    if isinstance(op, str):
+        if op not in _RA_ID:
+            raise ValueError(f"RandAugment op {op!r} unknown ({', '.join(RANDAUG_OPS)})")
+        return op
+    if not 0 <= int(op) < len(RANDAUG_OPS):
+        raise ValueError(f"RandAugment op id {op} unknown (0 .. {len(RANDAUG_OPS) - 1})")
+    return RANDAUG_OPS[int(op)]
+
+
+def empty_randaug_table(n):
+    """n identity entries: no stages, fill 0."""
+    return np.zeros(int(n), dtype=FRAME_RANDAUG)
+
+
+def randaug_stage(op, param, size):
+    """One RANDAUG_STAGE record for ``op`` (a name of RANDAUG_OPS or its id) on frames of ``size`` = (H, W).  ``param`` is PIL's own
+    argument: bits (Posterize), threshold (Solarize), the added value (SolarizeAdd), the enhancement factor (Color, Contrast,
+    Brightness, Sharpness), the shear factor (ShearX, ShearY: the matrix entry), pixels (TranslateX, TranslateY: the matrix entry),
+    degrees (Rotate); ignored by AutoContrast, Equalize and Invert."""
+    name = _ra_name(op)
+    H, W = _size2(size)
+    st = np.zeros((), dtype=RANDAUG_STAGE)
+    st["op"] = _RA_ID[name]
+    if name in _RA_INT_RANGE:
+        if int(param) != param or not 0 <= int(param) <= _RA_INT_RANGE[name]:
+            raise ValueError(f"{name}: ival {param!r} outside 0 .. {_RA_INT_RANGE[name]}")
+        st["ival"] = int(param)
+    elif name in _RA_ENHANCE:
+        if not (math.isfinite(param) and param >= 0):
+            raise ValueError(f"{name}: fval {param!r} must be finite and >= 0")
+        st["fval"] = param
+    elif name == "Rotate":
+        st["aff"] = rotation_coeffs(param, (H, W))
+    elif name in _RA_SIGNED:
+        p = float(param)
+        st["aff"] = affine_coeffs({"ShearX": (1.0, p, 0.0, 0.0, 1.0, 0.0), "ShearY": (1.0, 0.0, 0.0, p, 1.0, 0.0),
+                                   "TranslateX": (1.0, 0.0, p, 0.0, 1.0, 0.0), "TranslateY": (1.0, 0.0, 0.0, 0.0, 1.0, p)}[name])
+    return st
+
+
+def randaug_entry(stages, size, fill=(124, 116, 104)):
+    """One FRAME_RANDAUG record from a list of ``(op, param)`` (see ``randaug_stage``), applied in that order."""
+    stages = list(stages)
+    if len(stages) > RANDAUG_MAX_OPS:
+        raise ValueError(f"an entry holds at most {RANDAUG_MAX_OPS} stages, got {len(stages)}")
+    e = np.zeros((), dtype=FRAME_RANDAUG)
+    e["nops"] = len(stages)
+    e["fill"][:3] = [int(v) for v in fill]
+    for i, (op, param) in enumerate(stages):
+        e["stage"][i] = randaug_stage(op, param, size)
+    return e
+
+
+def _ra_param(name, level, sign, H, W):
+    """the "increasing" magnitude maps: level in [0, 1] -> the op's parameter"""
+    if name == "Rotate":
+        return sign * 30.0 * level
+    if name in ("ShearX", "ShearY"):
+        return sign * 0.3 * level
+    if name == "TranslateX":
+        return sign * 0.45 * level * W
+    if name == "TranslateY":
+        return sign * 0.45 * level * H
+    if name in _RA_ENHANCE:
+        return max(0.1, 1.0 + sign * 0.9 * level)
+    if name == "Posterize":
+        return 4 - int(4 * level)
+    if name == "Solarize":
+        return 256 - int(256 * level)
+    if name == "SolarizeAdd":
+        return int(110 * level)
+    return None
+
+
+def sample_randaug_params(batch, frames, size, num_ops=4, magnitude=7.0, magnitude_std=0.5, prob=0.5, ops=None, fill=(124, 116, 104),
+                          consistent=True, views=1, generator=None):
+    """Draw the RandAugment table for ``views`` x ``batch`` clips of ``frames`` frames of ``size``, entries in ``sample_params``' order.
+    Per clip (per frame with ``consistent=False``), ``num_ops`` times in turn:
+      * an op, uniform with replacement from ``ops`` (names or ids; default all of RANDAUG_OPS);
+      * a uniform draw; only below ``prob`` does the op apply - otherwise it adds no stage and nothing more is drawn for it;
+      * ``level = clip(normal(magnitude, magnitude_std), 0, 10) / 10``;
+      * for the signed ops (the geometric ones and the four enhancers) a sign, negative with probability 1/2.
+    Level to parameter, the "increasing" set: Rotate +-30 level degrees; ShearX / ShearY +-0.3 level; TranslateX / TranslateY
+    +-0.45 level x W / H pixels (floats); Color, Contrast, Brightness, Sharpness f = max(0.1, 1 +- 0.9 level); Posterize
+    bits = 4 - int(4 level); Solarize thresh = 256 - int(256 level); SolarizeAdd add = int(110 level); AutoContrast, Equalize and Invert
+    take none.  Pixels that a geometric op leaves uncovered take ``fill`` (r, g, b).
+
+    The draws come from a ``numpy.random.Generator``: the same seed gives the same table, but the stream is this project's own - it is
+    not the stream of timm, torchvision or any other library."""
+    B, T, V, K = int(batch), int(frames), int(views), int(num_ops)
+    if not 0 <= K <= RANDAUG_MAX_OPS:
+        raise ValueError(f"num_ops must lie in 0 .. {RANDAUG_MAX_OPS}")
+    if not (0.0 <= prob <= 1.0):
+        raise ValueError("prob must lie in [0, 1]")
+    if not (0.0 <= magnitude <= 10.0 and magnitude_std >= 0.0 and math.isfinite(magnitude_std)):
+        raise ValueError("magnitude must lie in [0, 10] and magnitude_std be finite and >= 0")
+    names = [_ra_name(op) for op in (RANDAUG_OPS if ops is None else ops)]
+    if not names:
+        raise ValueError("ops must name at least one op")
+    if len(fill) != 3 or not all(0 <= int(v) <= 255 for v in fill):
+        raise ValueError("fill must be three values in 0 .. 255")
+    g = generator if generator is not None else np.random.default_rng()
+    H, W = _size2(size)
+    table = empty_randaug_table(V * B * T)
+    for first in range(0, V * B * T, T):
+        for t in range(T):
+            if consistent and t > 0:
+                table[first + t] = table[first]
+                continue
+            stages = []
+            for _ in range(K):
+                name = names[int(g.integers(0, len(names)))]
+                if not g.random() < prob:
+                    continue
+                level = min(max(float(g.normal(magnitude, magnitude_std)), 0.0), 10.0) / 10.0
+                sign = (-1.0 if g.random() < 0.5 else 1.0) if name in _RA_SIGNED else 1.0
+                stages.append((name, _ra_param(name, level, sign, H, W)))
+            table[first + t] = randaug_entry(stages, (H, W), fill=fill)
+    return table
+
+
+_RA_FIELDS = {"m": "magnitude", "n": "num_ops", "mstd": "magnitude_std", "p": "prob"}
+
+
+def parse_randaug(config):
+    """``"rand-m7-n4-mstd0.5-inc1"`` -> the keyword dict for ``sample_randaug_params`` / ``RandAugment``.  Fields: ``m`` magnitude,
+    ``n`` num_ops, ``mstd`` magnitude_std, ``p`` prob, and ``inc1`` (the increasing magnitude maps: the only set there is, so it adds
+    nothing).  Any other field - ``inc0`` among them - is refused by name."""
+    parts = str(config).split("-")
+    if parts[0] != "rand":
+        raise ValueError(f"parse_randaug: {config!r} does not start with 'rand'")
+    kw = {}
+    for part in parts[1:]:
+        if part == "inc1":
+            continue
+        for key in ("mstd", "m", "n", "p"):
+            if part.startswith(key) and len(part) > len(key) and (part[len(key)].isdigit() or part[len(key)] == "."):
+                try:
+                    value = float(part[len(key):])
+                except ValueError:
+                    raise ValueError(f"parse_randaug: field {part!r} has no number") from None
+                kw[_RA_FIELDS[key]] = int(value) if key == "n" and value == int(value) else value
+                break
+        else:
+            raise ValueError(f"parse_randaug: field {part!r} is not supported (m, n, mstd, p, inc1)")
+    return kw
+
+
+def format_randaug(num_ops=4, magnitude=7.0, magnitude_std=0.5, prob=0.5):
+    """the config string that ``parse_randaug`` turns back into these keywords"""
+    return f"rand-m{magnitude:g}-n{int(num_ops)}-mstd{magnitude_std:g}-p{prob:g}-inc1"
+
+
+_ra_size_checked = False
+
+
+def _check_randaug(frames, table):
+    global _ra_size_checked
+    if not _ra_size_checked:
+        n = int(_lib.lib().bvc_frame_randaug_bytes())
+        if n != FRAME_RANDAUG.itemsize:
+            raise _lib.BvcError(f"bvc_frame_randaug is {n} bytes in the library, FRAME_RANDAUG {FRAME_RANDAUG.itemsize}")
+        _ra_size_checked = True
+    if frames.dtype != torch.uint8 or frames.dim() < 3 or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous uint8 tensor [..., 3, H, W]")
+    C, H, W = (int(v) for v in frames.shape[-3:])
+    if C != 3:
+        raise ValueError(f"frames have {C} channels; RandAugment is defined for 3")
+    t = np.ascontiguousarray(table)
+    F = frames.numel() // max(1, 3 * H * W)
+    if t.dtype != FRAME_RANDAUG or t.ndim != 1 or t.shape[0] != F or F < 1:
+        raise ValueError(f"table must be a 1-d array of augment.FRAME_RANDAUG entries, one per frame ({F})")
+    return t, F, H, W
+
+
+def rand_augment_host(frames, table):
+    """bvc_clip_randaug_host: uint8 host frames ``[..., 3, H, W]`` and one FRAME_RANDAUG entry per frame -> a new tensor of the same
+    shape, every frame through its stages in order.  No GPU needed."""
+    if frames.device.type != "cpu":
+        raise ValueError("frames must be a host tensor")
+    t, F, H, W = _check_randaug(frames, table)
+    out = torch.empty_like(frames)
+    _lib.check(_lib.lib().bvc_clip_randaug_host(frames.data_ptr(), t.ctypes.data, F, H, W, out.data_ptr()), "bvc_clip_randaug_host")
+    return out
+
+
+def rand_augment(frames, table, out=None, workspace=None):
+    """bvc_op_clip_randaug on the current stream: uint8 device frames ``[..., 3, H, W]`` and a host table with one FRAME_RANDAUG entry
+    per frame -> uint8 frames of the same shape (``out``: a contiguous uint8 device tensor of as many bytes that shares no memory with
+    ``frames``; it is returned as it is.  ``workspace``: a uint8 device tensor of at least ``bvc_op_clip_randaug_workspace`` bytes to
+    use instead of a fresh one).  The table travels through pinned memory in one asynchronous copy; nothing synchronises."""
+    t, F, H, W = _check_randaug(frames, table)
+    L = _lib.lib()
+    if frames.device.type != "cuda":
+        raise _lib.BvcError("rand_augment runs on the GPU (rand_augment_host is the host twin); there is no CPU fallback")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != frames.numel() or out.device != frames.device:
+        raise ValueError("out must be a contiguous uint8 tensor of as many elements as frames, on their device")
+    need = int(L.bvc_op_clip_randaug_workspace(F, H, W)) if bool((t["nops"] != 0).any()) else 4
+    if workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need or
+                                  workspace.device != frames.device):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} elements on the frames' device")
+    with torch.cuda.device(frames.device):
+        staging = torch.empty(t.nbytes, dtype=torch.uint8, pin_memory=True)
+        staging.numpy()[:] = t.view(np.uint8).reshape(-1)
+        table_dev = staging.to(frames.device, non_blocking=True)
+        work = torch.empty(need, dtype=torch.uint8, device=frames.device) if workspace is None else workspace
+        _lib.check(L.bvc_op_clip_randaug(frames.data_ptr(), t.ctypes.data, table_dev.data_ptr(), F, H, W, out.data_ptr(), work.data_ptr(),
+                                         _lib.current_stream_ptr()), "bvc_op_clip_randaug")
+        # the stream still reads these after the call returns: keep the caching allocator from handing them out on another stream
+        table_dev.record_stream(torch.cuda.current_stream())
+        work.record_stream(torch.cuda.current_stream())
+    return out
+
+
+class RandAugment:
+    """RandAugment as one GPU stage: ``RandAugment("rand-m7-n4-mstd0.5-inc1")(clips)`` with uint8 device clips ``[B, T, 3, H, W]``
+    returns uint8 clips of the same shape.  ``config`` (see ``parse_randaug``) sets ``num_ops``, ``magnitude``, ``magnitude_std`` and
+    ``prob`` over the keyword arguments; the others are ``sample_randaug_params``'.  ``last_table`` keeps the table of the last call."""
+
+    def __init__(self, config=None, num_ops=4, magnitude=7.0, magnitude_std=0.5, prob=0.5, ops=None, fill=(124, 116, 104),
+                 consistent=True, generator=None):
+        self.kw = dict(num_ops=num_ops, magnitude=magnitude, magnitude_std=magnitude_std, prob=prob, ops=ops, fill=tuple(fill),
+                       consistent=consistent)
+        if config is not None:
+            self.kw.update(parse_randaug(config))
+        self.generator = generator if generator is not None else np.random.default_rng()
+        sample_randaug_params(1, 1, 8, generator=np.random.default_rng(0), **self.kw)      # argument errors surface here
+        self.last_table = None
+
+    def sample(self, batch, frames, size, views=1, generator=None):
+        return sample_randaug_params(batch, frames, size, views=views, generator=self.generator if generator is None else generator,
+                                     **self.kw)
+
+    def __call__(self, clips, table=None):
+        _check_clips(clips)
+        B, T, C, H, W = (int(v) for v in clips.shape)
+        if C != 3:
+            raise ValueError(f"clips have {C} channels; RandAugment is defined for 3")
+        table = self.sample(B, T, (H, W)) if table is None else table
+        self.last_table = table
+        return rand_augment(clips, table)

@@ -395,6 +395,47 @@ int64_t bvc_op_clip_post_workspace(int F, int H, int W);
 int bvc_op_clip_post(const uint8_t* in_dev, const bvc_frame_post* table_host, const bvc_frame_post* table_dev, int F, int H, int W,
                      uint8_t* out_dev, void* workspace_dev, void* stream);
 int bvc_clip_post_host(const uint8_t* in, const bvc_frame_post* table, int F, int H, int W, uint8_t* out);
+/* RandAugment (the timm "rand-m7-n4-mstd0.5-inc1" family of the VideoMAE fine-tuning recipes): a third stage on uint8 frames
+ * [F][3][H][W].  One bvc_frame_randaug per frame: up to BVC_RANDAUG_MAX_OPS stages, applied in order, each on the frame as the stage
+ * before left it; an op may repeat.  Statistics (histograms, the mean) are of that one frame as it stands.  Each op gives the bytes of
+ * the named PIL call on an RGB frame (arithmetic in csrc/randaug.h); the device, the host twin and PIL agree bit for bit.
+ *   op  0 AutoContrast  ImageOps.autocontrast         1 Equalize     ImageOps.equalize           2 Invert      ImageOps.invert
+ *       3 Posterize     ival = bits, 0 .. 8           4 Solarize     ival = threshold, 0 .. 256  5 SolarizeAdd ival = add, 0 .. 110
+ *       6 Color  7 Contrast  8 Brightness  9 Sharpness  ImageEnhance.*(im).enhance(fval), fval finite and >= 0
+ *       10 ShearX  11 ShearY  12 TranslateX  13 TranslateY  14 Rotate  Image.transform(AFFINE, NEAREST) / Image.rotate(NEAREST):
+ *       aff[6] is the inverse map in 16.16 fixed point as in bvc_frame_post.rot (bvc.augment.affine_coeffs, rotation_coeffs), with the
+ *       same bounds; pixels whose source lies outside the frame take fill[0 .. 2]
+ *   ival, fval and aff are read only by the ops named with them.
+ * bvc_op_clip_randaug: in_dev / table_dev / out_dev / workspace_dev are device memory, table_host is the same table in host memory,
+ * read during the call only: validated there, without a device sync, and it tells the call what to launch.  The host walks the stage
+ * index; per stage one read-write pass over the frames that have such a stage, and, when some frame's stage is AutoContrast, Equalize
+ * or Contrast, before it one read of those frames into integer histograms (integer LDS and global atomics: order-independent, so
+ * nothing for the deterministic mode to switch) and a small kernel that turns them into byte tables.  Frames alternate between out_dev
+ * and workspace_dev (bvc_op_clip_randaug_workspace bytes, 4-byte aligned, overlapping neither in nor out) so that each frame's last
+ * stage lands in out_dev.  A table with nops == 0 everywhere is one device-to-device copy.  BVC_ERR_INVALID with a message that names the
+ * field for nops outside 0 .. 8, an unknown op, a non-finite or negative fval, an ival outside its op's range, an affine op on a frame
+ * with an edge above 4096 or with |aff[0, 1, 3, 4]| > 65537 or |aff[2, 5]| > 2^30, and in / out that overlap - before anything is
+ * launched.  The kernels do not trust the device copy of the table: they clamp nops and ival, copy through an unknown op and test every
+ * gather's source index.
+ * bvc_clip_randaug_host: the same arithmetic compiled for the host, on host memory; needs no GPU.
+ * bvc_frame_randaug_bytes: sizeof the entry, for bindings that restate its layout. */
+#define BVC_RANDAUG_MAX_OPS 8
+typedef struct bvc_randaug_stage {
+    int32_t op;
+    int32_t ival;
+    float fval;
+    int32_t aff[6];
+} bvc_randaug_stage; /* 36 bytes */
+typedef struct bvc_frame_randaug {
+    int32_t nops;
+    uint8_t fill[4]; /* r, g, b, unused */
+    bvc_randaug_stage stage[BVC_RANDAUG_MAX_OPS];
+} bvc_frame_randaug; /* 296 bytes */
+int bvc_frame_randaug_bytes(void);
+int64_t bvc_op_clip_randaug_workspace(int F, int H, int W);
+int bvc_op_clip_randaug(const uint8_t* in_dev, const bvc_frame_randaug* table_host, const bvc_frame_randaug* table_dev, int F, int H, int W,
+                        uint8_t* out_dev, void* workspace_dev, void* stream);
+int bvc_clip_randaug_host(const uint8_t* in, const bvc_frame_randaug* table, int F, int H, int W, uint8_t* out);
 
 /* ------------------------------------------------------------------------------------------------
  * JEPA encoder and predictor (pretraining/predictive/vision_transformer.py).  Same conventions as above: flat f32

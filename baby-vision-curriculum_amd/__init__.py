@@ -28,3 +28,5 @@ from .augment import (FRAME_RANDAUG, RANDAUG_OPS, RandAugment, empty_randaug_tab
 from . import simclr, distributed, jepa, jepa_mask, checkpoint, launch, comm, probe, retrieval, separability  # noqa: F401
 from . import input as input_pipeline  # noqa: F401
 from .input import ClipUploadRing  # noqa: F401
+from . import jpeg  # noqa: F401
+from .jpeg import JpegClipRing, JpegUnsupported  # noqa: F401

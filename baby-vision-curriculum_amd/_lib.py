@@ -212,6 +212,13 @@ SYMBOLS = {
     "bvc_op_clip_randaug_workspace": (c_int64, [c_int, c_int, c_int]),
     "bvc_op_clip_randaug": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "bvc_clip_randaug_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "bvc_jpeg_info_bytes": (c_int, []),
+    "bvc_jpeg_parse": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int]),
+    "bvc_jpeg_decode_host": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_jpeg_decode_workspace": (c_int64, [c_void_p, c_int]),
+    # (blob, blob_bytes, infos host / dev, n, segs host / dev, nseg, out_offsets host / dev, out, out_bytes, status, workspace, workspace_bytes, lanes, stages, stream)
+    "bvc_op_jpeg_decode": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "bvc_videomae_cls_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_encoder_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_cls_set_mix": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

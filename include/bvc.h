@@ -436,6 +436,74 @@ int64_t bvc_op_clip_randaug_workspace(int F, int H, int W);
 int bvc_op_clip_randaug(const uint8_t* in_dev, const bvc_frame_randaug* table_host, const bvc_frame_randaug* table_dev, int F, int H, int W,
                         uint8_t* out_dev, void* workspace_dev, void* stream);
 int bvc_clip_randaug_host(const uint8_t* in, const bvc_frame_randaug* table, int F, int H, int W, uint8_t* out);
+/* JPEG decode (baseline Huffman) to planar RGB uint8 [3][H][W], the bytes libjpeg-turbo gives at its defaults (ISLOW IDCT, fancy
+ * upsampling, the 16-bit YCbCr tables; arithmetic in csrc/jpeg.h, shared by the kernels and the host twin).
+ * Decoded: 8-bit SOF0 / SOF1, one component (three equal channels) or three YCbCr components with luma 1x1, 2x1 or 2x2 and chroma
+ * 1x1, JFIF colour or Adobe transform 1, up to four DQT tables (8- or 16-bit), Huffman tables 0 and 1 of each class, DRI / RSTn, one
+ * scan, 1 .. BVC_JPEG_MAX_DIM pixels a side.  Everything else is refused at parse with a BVC_JPEG_REFUSE_* reason.
+ * bvc_jpeg_parse: plain C++, NO HIP call on its path - it may run in loader workers that never open the device.  Walks the markers
+ * (every length checked against n), fills *info (tables in decode form, rebuilt from the DHT counts; over-subscribed, over-long or
+ * out-of-range tables are refused, so the device never sees a table it could walk off), and scans the entropy-coded bytes once for
+ * 0xFF to list the independent segments: seg[4 * i + 0 .. 3] = first byte, end byte (offsets into data), first MCU, MCU count.  A
+ * file without DRI is one segment; RSTn numbering is checked; the last segment takes every MCU that is left.  At most max_seg records
+ * are written, info->nseg is the full count (seg may be NULL with max_seg 0).  Returns BVC_OK, a positive BVC_JPEG_REFUSE_* (also in
+ * info->reason), or BVC_ERR_INVALID for a null argument.  A scan that runs to the end of the data without EOI is not refused: the
+ * file decodes as far as it goes and BVC_JPEG_ST_NO_EOI is pre-set in info->flags and raised in the image's status.
+ * Status bits of a decoded image (0 = every segment decoded cleanly): a reader that needs bits past the end of its segment
+ * (TRUNCATED), a code that matches nothing (BAD_CODE) and a run past coefficient 63 (BAD_RUN) end the segment; its remaining blocks
+ * are DC-only at the component's last DC prediction.  The reader never forms an address outside [begin, end) of its segment.
+ * The caller fills blob_offset (where the file's bytes begin in the blob) and seg_first (index of the image's first record in the
+ * concatenated segment table); bvc_op_jpeg_decode_workspace fills plane_offset of n infos and returns the workspace bytes (the
+ * components' uint8 planes padded to whole MCUs, 1.5 bytes per padded pixel at 4:2:0).  Infos with reason != 0 take no part.
+ * bvc_op_jpeg_decode: blob_dev / infos_dev / segs_dev / out_offsets_dev / status_dev / workspace_dev are device memory; infos_host,
+ * segs_host and out_offsets_host are the same tables in host memory, read during the call only: validated there (every range against
+ * blob_bytes, out_bytes and the workspace) and they set the launch geometry.  Two kernels, no synchronisation, no atomics: (1) one
+ * lane per segment - entropy decode, dequantise, IDCT with the block in LDS, 8-byte rows into the planes; (2) upsample, colour-convert
+ * and crop into out_dev + out_offsets[i].  status_dev[i] is written for every image (0 for refused ones, whose output is not
+ * touched).  lanes = segments per wave, 1 .. 64, or 0 to let the call choose by the number of segments.  stages = 3; 1 or 2 launch one
+ * of the two kernels alone, for measurements (2 reads the planes an earlier call left in the workspace).
+ * bvc_jpeg_decode_host: parse's info and segments -> RGB, the same arithmetic compiled for the host; returns the status bits (>= 0).
+ * bvc_jpeg_info_bytes: sizeof the descriptor, for bindings that restate its layout. */
+#define BVC_JPEG_MAX_DIM 4096
+enum {
+    BVC_JPEG_REFUSE_NOT_JPEG = 1, BVC_JPEG_REFUSE_BAD_LENGTH = 2, BVC_JPEG_REFUSE_PROGRESSIVE = 3, BVC_JPEG_REFUSE_ARITHMETIC = 4,
+    BVC_JPEG_REFUSE_LOSSLESS = 5, BVC_JPEG_REFUSE_PRECISION = 6, BVC_JPEG_REFUSE_COMPONENTS = 7, BVC_JPEG_REFUSE_RGB = 8,
+    BVC_JPEG_REFUSE_SAMPLING = 9, BVC_JPEG_REFUSE_MULTI_SCAN = 10, BVC_JPEG_REFUSE_HUFFMAN = 11, BVC_JPEG_REFUSE_QUANT = 12,
+    BVC_JPEG_REFUSE_SIZE = 13, BVC_JPEG_REFUSE_SCAN_HEADER = 14, BVC_JPEG_REFUSE_RESTART = 15, BVC_JPEG_REFUSE_HEADER = 16
+};
+enum { BVC_JPEG_ST_TRUNCATED = 1, BVC_JPEG_ST_BAD_CODE = 2, BVC_JPEG_ST_BAD_RUN = 4, BVC_JPEG_ST_NO_EOI = 8 };
+typedef struct bvc_jpeg_huff {
+    uint16_t look[256];  /* by the next 8 bits: (code length << 8) | symbol, 0 = the code is longer than 8 bits */
+    int32_t maxcode[18]; /* [l], l = 1 .. 16: largest code of length l, -1 = none; [17] ends every search */
+    int32_t valoff[18];  /* [l]: huffval index of a code of length l = code + valoff[l] (valptr - mincode) */
+    uint8_t huffval[256];
+} bvc_jpeg_huff; /* 912 bytes */
+typedef struct bvc_jpeg_info {
+    int32_t width, height;
+    int32_t ncomp;            /* 1 or 3 */
+    int32_t hs, vs;           /* luma sampling: 1x1, 2x1 or 2x2 (1x1 for one component) */
+    int32_t mcus_x, mcus_y;
+    int32_t restart_interval; /* MCUs, 0 = none */
+    int32_t scan_begin, scan_end; /* the entropy-coded bytes, offsets into the file */
+    int32_t nseg;
+    int32_t reason;           /* 0, or the BVC_JPEG_REFUSE_* parse returned */
+    int32_t flags;            /* status bits known at parse (BVC_JPEG_ST_NO_EOI) */
+    int32_t seg_first;        /* caller: index of the first segment record */
+    int64_t blob_offset;      /* caller: where the file begins in the blob */
+    int64_t plane_offset;     /* bvc_op_jpeg_decode_workspace: where the planes begin in the workspace, a multiple of 16 */
+    uint8_t tq[4], td[4], ta[4]; /* per component: quantisation table, DC table, AC table (huff[td], huff[2 + ta]) */
+    uint32_t pad_;
+    uint16_t qt[4][64];       /* natural (row-major) order */
+    bvc_jpeg_huff huff[4];    /* DC 0, DC 1, AC 0, AC 1 */
+} bvc_jpeg_info; /* 4248 bytes */
+int bvc_jpeg_info_bytes(void);
+int bvc_jpeg_parse(const uint8_t* data, int64_t n, bvc_jpeg_info* info, int32_t* seg, int max_seg);
+int bvc_jpeg_decode_host(const uint8_t* data, int64_t n, const bvc_jpeg_info* info, const int32_t* seg, uint8_t* out_rgb);
+int64_t bvc_op_jpeg_decode_workspace(bvc_jpeg_info* infos_host, int n);
+int bvc_op_jpeg_decode(const uint8_t* blob_dev, int64_t blob_bytes, const bvc_jpeg_info* infos_host, const bvc_jpeg_info* infos_dev, int n,
+                       const int32_t* segs_host, const int32_t* segs_dev, int64_t nseg, const int64_t* out_offsets_host,
+                       const int64_t* out_offsets_dev, uint8_t* out_dev, int64_t out_bytes, int32_t* status_dev, void* workspace_dev,
+                       int64_t workspace_bytes, int lanes, int stages, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * JEPA encoder and predictor (pretraining/predictive/vision_transformer.py).  Same conventions as above: flat f32

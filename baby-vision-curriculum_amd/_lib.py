@@ -219,6 +219,13 @@ SYMBOLS = {
     # (blob, blob_bytes, infos host / dev, n, segs host / dev, nseg, out_offsets host / dev, out, out_bytes, status, workspace, workspace_bytes, lanes, stages, stream)
     "bvc_op_jpeg_decode": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "bvc_jpeg_split_chunk": (c_int, [c_int, c_int]),
+    # (data, n, info, seg, split, chunk, out_rgb, info_out)
+    "bvc_jpeg_decode_host_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "bvc_op_jpeg_decode_split_workspace": (c_int64, [c_void_p, c_int]),
+    # bvc_op_jpeg_decode's arguments up to stages, then (split, chunk, info_out, stream)
+    "bvc_op_jpeg_decode_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bvc_videomae_cls_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_encoder_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_cls_set_mix": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

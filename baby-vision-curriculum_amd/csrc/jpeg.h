@@ -311,6 +311,202 @@ JPG_HD int decode_segment(const Info* I, const uint8_t* file, int begin, int end
     return st;
 }
 
+// ---------------------------------------------------------------- stage 1, split: one segment on the lanes of a workgroup
+// include/bvc.h, bvc_op_jpeg_decode_split.  The segment's bytes are cut into chunks, one lane per chunk; a lane decodes the symbols
+// that START inside its chunk.  States that lanes hand to each other live in ONE coordinate system: bit positions in the raw file,
+// relative to the segment's first byte, where a stuffed 00 belongs to its FF - a position is never inside a stuffed byte, and the
+// position after the last bit of an FF is the first bit after its 00.
+constexpr int kSplitThreads = BVC_JPEG_SPLIT_THREADS;      // lanes of a workgroup = the most chunks a segment is cut into
+constexpr int kSplitMinChunk = BVC_JPEG_SPLIT_MIN_CHUNK;   // a symbol is at most 31 bits: an entry point lies inside its own chunk
+constexpr int kSplitDefaultChunk = BVC_JPEG_SPLIT_DEFAULT_CHUNK;
+constexpr int kSplitMaxBytes = 1 << 28;                    // bit positions are 32-bit
+
+struct SplitState {
+    uint32_t pos;       // the next symbol's first bit
+    uint32_t meta;      // block within the MCU | zig-zag index k << 3 | kSplitDead
+};
+constexpr uint32_t kSplitDead = 1u << 9;      // an error, or the end of the data inside a symbol, lies before this point
+
+JPG_HD bool split_same(SplitState a, SplitState b) { return a.pos == b.pos && a.meta == b.meta; }
+JPG_HD SplitState split_dead() { return SplitState{0u, kSplitDead}; }
+
+JPG_HD bool seg_is_split(int bytes, int split) { return split > 0 && bytes >= split && bytes >= 2 * kSplitMinChunk && bytes < kSplitMaxBytes; }
+// bytes per lane: max(chunk, bytes / kSplitThreads rounded up to a multiple of 4)
+JPG_HD int split_chunk_bytes(int bytes, int chunk) {
+    const int c = chunk > 0 ? chunk : kSplitDefaultChunk, per = ((bytes + kSplitThreads - 1) / kSplitThreads + 3) & ~3;
+    return c > per ? c : per;
+}
+
+// the reader of the split path: Bits, and where it is in the raw file
+struct SBits {
+    Bits b;
+    uint64_t ff;      // aligned with b.buf: the last bit of every buffered FF whose stuffed 00 follows it in the file
+    bool hard;        // the data ended at a marker or a lone FF: b.pos says nothing any more
+};
+
+JPG_HD void refill(SBits& s) {
+    Bits& b = s.b;
+    while (b.cnt <= 56 && b.pos < b.end) {
+        if (b.cnt <= 32 && b.pos + 4 <= b.end) {
+            const uint32_t b0 = b.p[b.pos], b1 = b.p[b.pos + 1], b2 = b.p[b.pos + 2], b3 = b.p[b.pos + 3];
+            if (b0 != 255u && b1 != 255u && b2 != 255u && b3 != 255u) {
+                b.buf |= (uint64_t)((b0 << 24) | (b1 << 16) | (b2 << 8) | b3) << (32 - b.cnt);
+                b.cnt += 32;
+                b.pos += 4;
+                continue;
+            }
+        }
+        const uint32_t c = b.p[b.pos];
+        if (c == 255u) {
+            if (b.pos + 1 < b.end && b.p[b.pos + 1] == 0) {
+                b.pos += 2;
+                s.ff |= 1ull << (56 - b.cnt);
+            } else {
+                b.pos = b.end;
+                s.hard = true;
+                break;
+            }
+        } else {
+            b.pos += 1;
+        }
+        b.buf |= (uint64_t)c << (56 - b.cnt);
+        b.cnt += 8;
+    }
+}
+
+JPG_HD bool consume(SBits& s, int n) {
+    s.ff <<= n;
+    return consume(s.b, n);
+}
+
+JPG_HD int popcount64(uint64_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __popcll(v);
+#else
+    return __builtin_popcountll(v);
+#endif
+}
+
+// the next bit's position; an FF that is not consumed whole still has its 00 ahead
+JPG_HD uint32_t position(const SBits& s, int begin) { return (uint32_t)(8 * (s.b.pos - begin) - s.b.cnt - 8 * popcount64(s.ff)); }
+
+// where a lane that knows nothing enters chunk bytes [at, ...) of the segment: at the chunk's first byte that is not a stuffed 00,
+// at the start of an MCU
+JPG_HD SplitState split_guess(const uint8_t* file, int begin, int end, int at) {
+    const int p = begin + at;
+    const bool stuffed = at > 0 && p < end && file[p] == 0 && file[p - 1] == 255u;
+    return SplitState{(uint32_t)(8 * (at + (stuffed ? 1 : 0))), 0u};
+}
+
+// what a lane enters its chunk with: the state its predecessor handed over, or its own guess when that is dead - a dead hand-over
+// must not undo a lane that found the true chain by itself; placement ends the true chain at the first dead exit
+JPG_HD SplitState split_entry(SplitState handed, SplitState guess) { return (handed.meta & kSplitDead) ? guess : handed; }
+
+// One chunk: from state `in`, every symbol that starts before bit `stop`.  Returns the state at the first symbol at or after `stop`,
+// or split_dead() when a bad code, a bad run or the end of the data came first (no status is raised here: the caller decides what a
+// dead chain means), and in *blocks the blocks that were completed.  After the data's end at a marker positions mean nothing, so the
+// lane goes on to the last buffered bit and leaves dead.  kWrite: block first_block + i of the segment, if it is below `need`, gets
+// its AC coefficients dequantised into coef (64 int16 in natural order per block) and its DC DIFFERENCE into dc.
+// nblk, hv: blocks per MCU, luma blocks per MCU.  No byte outside [begin, end) is read and every table index is masked.
+template <bool kWrite>
+JPG_HD SplitState decode_chunk(const Info* I, const uint8_t* file, int begin, int end, uint32_t stop, SplitState in, int nblk, int hv,
+                               int first_block, int need, int16_t* coef, int32_t* dc, int* blocks) {
+    *blocks = 0;
+    if (in.meta & kSplitDead) return split_dead();
+    if (in.pos >= stop) return in;
+    int bi = (int)(in.meta & 7u), k = (int)((in.meta >> 3) & 63u), nb = 0;
+    if (bi >= nblk) return split_dead();
+    int at = begin + (int)(in.pos >> 3);
+    if (at > end) at = end;
+    SBits s = {{file, at, end, 0ull, 0}, 0ull, false};
+    refill(s);
+    consume(s, (int)(in.pos & 7u));
+    int comp = bi < hv ? 0 : bi - hv + 1;
+    const Huff* hdc = &I->huff[I->td[comp] & 1];
+    const Huff* hac = &I->huff[2 + (I->ta[comp] & 1)];
+    const uint16_t* q = I->qt[I->tq[comp] & 3];
+    for (;;) {
+        const uint32_t pos = position(s, begin);
+        if (!s.hard && pos >= stop) {
+            *blocks = nb;
+            return SplitState{pos, (uint32_t)bi | ((uint32_t)k << 3)};
+        }
+        if (s.b.cnt < 32) refill(s);
+        int len;
+        const int sym = huff_symbol(k == 0 ? hdc : hac, (uint32_t)(s.b.buf >> 48), &len);
+        bool err = sym < 0 || len < 1;      // a table of the caller's with a code of no bits: every pass of this loop takes at least one
+        bool over = consume(s, len);
+        const int sz = sym & 15, r = (sym >> 4) & 15;
+        uint32_t bits = 0u;
+        if (!err && sz) {
+            bits = (uint32_t)(s.b.buf >> (64 - sz));
+            over = consume(s, sz) || over;
+        }
+        err = err || over;
+        const int blk = first_block + nb;
+        if (!err) {
+            if (k == 0) {
+                if (kWrite && blk < need) dc[blk] = sz ? extend(bits, sz) : 0;
+                k = 1;
+            } else if (sz) {
+                k += r;
+                if (k > 63) {
+                    err = true;
+                } else {
+                    const int nat = natural_of(k);
+                    if (kWrite && blk < need) coef[(size_t)blk * 64 + nat] = (int16_t)dequant(extend(bits, sz), q[nat]);
+                    k += 1;
+                }
+            } else if (r == 15) {
+                k += 16;
+                err = k > 63;
+            } else {
+                k = 64;      // end of block
+            }
+        }
+        if (err) {
+            *blocks = nb;
+            return split_dead();
+        }
+        if (k > 63) {
+            k = 0;
+            nb += 1;
+            bi = bi + 1 == nblk ? 0 : bi + 1;
+            const int c = bi < hv ? 0 : bi - hv + 1;
+            if (c != comp) {
+                comp = c;
+                hdc = &I->huff[I->td[c] & 1];
+                hac = &I->huff[2 + (I->ta[c] & 1)];
+                q = I->qt[I->tq[c] & 3];
+            }
+        }
+    }
+}
+
+// where block bi of MCU mcu goes in the planes (decode_segment's layout)
+JPG_HD uint8_t* block_dst(const Info* I, uint8_t* planes, int mcu, int bi, int* stride) {
+    const int hs = I->hs, hv = I->hs * I->vs, mcus_x = I->mcus_x;
+    const int mx = mcu % mcus_x, my = mcu / mcus_x;
+    if (I->ncomp == 1) {
+        *stride = mcus_x * 8;
+        return planes + ((size_t)my * 8) * *stride + (size_t)mx * 8;
+    }
+    if (bi < hv) {
+        *stride = luma_stride(I);
+        return planes + ((size_t)(my * I->vs + bi / hs) * 8) * *stride + (size_t)(mx * hs + bi % hs) * 8;
+    }
+    *stride = chroma_stride(I);
+    return planes + luma_bytes(I) + (bi - hv == 1 ? chroma_bytes(I) : 0) + ((size_t)my * 8) * *stride + (size_t)mx * 8;
+}
+
+// block b of the image (MCU-major, as the scan has them): blk, its 64 dequantised coefficients in natural order (in place) -> samples
+JPG_HD void idct_block(const Info* I, int b, int32_t* blk, uint8_t* planes) {
+    const int nblk = I->ncomp == 1 ? 1 : I->hs * I->vs + 2;
+    int stride;
+    uint8_t* dst = block_dst(I, planes, b / nblk, b % nblk, &stride);
+    idct_store(blk, dst, stride);
+}
+
 // ---------------------------------------------------------------- stage 2: one pixel
 JPG_HD int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
@@ -557,6 +753,111 @@ inline int decode_host(const uint8_t* data, const Info* I, const int32_t* seg, u
     int st = I->flags;
     for (int s = 0; s < I->nseg; ++s)
         st |= decode_segment(I, data, seg[kSegInts * s], seg[kSegInts * s + 1], seg[kSegInts * s + 2], seg[kSegInts * s + 3], blk, planes.data());
+    const size_t plane = (size_t)I->height * I->width;
+    for (int y = 0; y < I->height; ++y)
+        for (int x = 0; x < I->width; ++x) {
+            int r, g, b;
+            pixel_rgb(I, planes.data(), x, y, &r, &g, &b);
+            out[(size_t)y * I->width + x] = (uint8_t)r;
+            out[plane + (size_t)y * I->width + x] = (uint8_t)g;
+            out[2 * plane + (size_t)y * I->width + x] = (uint8_t)b;
+        }
+    return st;
+}
+
+// ---------------------------------------------------------------- host twin of the split path
+// jpeg_split_kernel in plain C++, its lanes run one after another: the same chunks, the same rounds, the same placement.  coef / dc:
+// the IMAGE's coefficient blocks and DC values (mcus_x * mcus_y * blocks per MCU of them).  Returns true when the true chain ended
+// before the segment's last block: the caller decodes the segment again with decode_segment.  *rounds: hand-over rounds taken.
+inline bool decode_segment_split(const Info* I, const uint8_t* file, int begin, int end, int first_mcu, int mcu_count, int chunk,
+                                 int16_t* coef, int32_t* dc, int* rounds) {
+    const int hv = I->hs * I->vs, nblk = I->ncomp == 1 ? 1 : hv + 2;
+    const int bytes = end - begin, c = split_chunk_bytes(bytes, chunk), nch = (bytes + c - 1) / c, need = mcu_count * nblk;
+    coef += (size_t)first_mcu * nblk * 64;
+    dc += (size_t)first_mcu * nblk;
+    std::vector<SplitState> guess(nch), entry(nch), exit_(nch), hand[2];
+    std::vector<int> count(nch);
+    hand[0].resize(nch);
+    hand[1].resize(nch);
+    auto stop = [&](int j) { return (uint32_t)(8 * ((int64_t)(j + 1) * c < bytes ? (j + 1) * c : bytes)); };
+    for (int j = 0; j < nch; ++j) {
+        entry[j] = guess[j] = j == 0 ? SplitState{0u, 0u} : split_guess(file, begin, end, j * c);
+        exit_[j] = decode_chunk<false>(I, file, begin, end, stop(j), entry[j], nblk, hv, 0, 0, nullptr, nullptr, &count[j]);
+        hand[0][j] = exit_[j];
+    }
+    int cur = 0, r = 0;
+    for (int round = 1; round < nch; ++round) {
+        bool any = false;
+        for (int j = 0; j < nch; ++j) {
+            const SplitState e = j > 0 ? split_entry(hand[cur][j - 1], guess[j]) : entry[j];
+            if (!split_same(e, entry[j])) {
+                entry[j] = e;
+                const SplitState x = decode_chunk<false>(I, file, begin, end, stop(j), entry[j], nblk, hv, 0, 0, nullptr, nullptr, &count[j]);
+                any = any || !split_same(x, exit_[j]);
+                exit_[j] = x;
+            }
+            hand[cur ^ 1][j] = exit_[j];
+        }
+        cur ^= 1;
+        ++r;
+        if (!any) break;
+    }
+    *rounds = r;
+    std::vector<int> first(nch);
+    int total = 0;
+    bool chain = true;      // the true chain: up to the first dead exit
+    for (int j = 0; j < nch; ++j) {
+        first[j] = total;
+        if (!chain) count[j] = -1;
+        total += chain ? count[j] : 0;
+        chain = chain && !(exit_[j].meta & kSplitDead);
+    }
+    if (total < need) return true;
+    for (size_t i = 0; i < (size_t)need * 64; ++i) coef[i] = 0;
+    for (int j = 0; j < nch; ++j) {
+        int n;
+        if (count[j] >= 0) decode_chunk<true>(I, file, begin, end, stop(j), entry[j], nblk, hv, first[j], need, coef, dc, &n);
+    }
+    int32_t pred[3] = {0, 0, 0};
+    for (int b = 0; b < need; ++b) {
+        const int bi = b % nblk, comp = bi < hv ? 0 : bi - hv + 1;
+        pred[comp] = add(pred[comp], dc[b]);
+        dc[b] = dequant(pred[comp], I->qt[I->tq[comp] & 3][0]);
+    }
+    return false;
+}
+
+// include/bvc.h, bvc_jpeg_decode_host_split.  info_out[0]: segments that fell back; info_out[1]: the most rounds a segment took.
+inline int decode_host_split(const uint8_t* data, const Info* I, const int32_t* seg, int split, int chunk, uint8_t* out, int32_t* info_out) {
+    std::vector<uint8_t> planes((size_t)plane_bytes(I));
+    const int nblk = I->ncomp == 1 ? 1 : I->hs * I->vs + 2;
+    const size_t blocks = (size_t)I->mcus_x * I->mcus_y * nblk;
+    std::vector<int16_t> coef;
+    std::vector<int32_t> dc;
+    int32_t blk[64];
+    int st = I->flags;
+    info_out[0] = info_out[1] = 0;
+    for (int s = 0; s < I->nseg; ++s) {
+        const int32_t* g = seg + kSegInts * s;
+        bool whole = !seg_is_split(g[1] - g[0], split);
+        if (!whole) {
+            if (coef.empty()) {
+                coef.resize(blocks * 64);
+                dc.resize(blocks);
+            }
+            int rounds = 0;
+            whole = decode_segment_split(I, data, g[0], g[1], g[2], g[3], chunk, coef.data(), dc.data(), &rounds);
+            info_out[0] += whole;
+            info_out[1] = rounds > info_out[1] ? rounds : info_out[1];
+            if (!whole)
+                for (int b = g[2] * nblk; b < (g[2] + g[3]) * nblk; ++b) {
+                    for (int i = 1; i < 64; ++i) blk[i] = coef[(size_t)b * 64 + i];
+                    blk[0] = dc[b];
+                    idct_block(I, b, blk, planes.data());
+                }
+        }
+        if (whole) st |= decode_segment(I, data, g[0], g[1], g[2], g[3], blk, planes.data());
+    }
     const size_t plane = (size_t)I->height * I->width;
     for (int y = 0; y < I->height; ++y)
         for (int x = 0; x < I->width; ++x) {

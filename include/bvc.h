@@ -463,8 +463,35 @@ int bvc_clip_randaug_host(const uint8_t* in, const bvc_frame_randaug* table, int
  * touched).  lanes = segments per wave, 1 .. 64, or 0 to let the call choose by the number of segments.  stages = 3; 1 or 2 launch one
  * of the two kernels alone, for measurements (2 reads the planes an earlier call left in the workspace).
  * bvc_jpeg_decode_host: parse's info and segments -> RGB, the same arithmetic compiled for the host; returns the status bits (>= 0).
- * bvc_jpeg_info_bytes: sizeof the descriptor, for bindings that restate its layout. */
+ * bvc_jpeg_info_bytes: sizeof the descriptor, for bindings that restate its layout.
+ *
+ * bvc_op_jpeg_decode_split / _workspace: the same call with a second path for long segments - a file without DRI is ONE segment and
+ * would sit on one lane.  split: segments of at least this many bytes (and of at least 2 * BVC_JPEG_SPLIT_MIN_CHUNK and fewer than
+ * 2^28 bytes) take the split path, 0 = none; every other segment goes through the one-lane kernel unchanged, in the same call.
+ * chunk: bytes per lane, 0 (BVC_JPEG_SPLIT_DEFAULT_CHUNK) or >= BVC_JPEG_SPLIT_MIN_CHUNK.  Chunk layout, deterministic:
+ *   one workgroup of T = BVC_JPEG_SPLIT_THREADS lanes per split segment [begin, end);
+ *   c = max(chunk, ceil((end - begin) / T) rounded up to a multiple of 4)      (bvc_jpeg_split_chunk)
+ *   chunk j = bytes [begin + j c, min(begin + (j + 1) c, end)), j < ceil((end - begin) / c) <= T, on lane j.
+ * A lane decodes the symbols that start in its chunk.  Lane 0 enters at the true state, every other lane at a guess; in rounds, lane
+ * j takes over the exit state lane j - 1 recorded (bit position, block within the MCU, zig-zag index, dead) and decodes again until
+ * a workgroup-wide reduction says that no exit changed - at most chunks - 1 rounds, after which the chain is right by induction
+ * from chunk 0.  Bit positions are those of the RAW file, a stuffed 00 belonging to its FF.  All waiting is the barrier of one
+ * workgroup: no workgroup waits for another, no atomics.  A speculative lane that meets a bad code, a bad run or the data's end
+ * records "dead" and raises nothing.  An exclusive scan of the blocks completed per chunk places every chunk; blocks beyond the
+ * segment's last (the padding bits decode as garbage) are dropped; a last pass writes AC coefficients dequantised (64 int16 per
+ * block, natural order) and DC differences into the workspace; a wrapping 32-bit scan per component turns the differences into DC
+ * values; jpeg_idct_kernel (one lane per block) writes the planes, and the colour kernel runs as before.  When the true chain ends
+ * before the segment's last block (what the one-lane decoder reports as TRUNCATED, BAD_CODE or BAD_RUN) the segment is flagged on
+ * the device and decoded again, whole, by the one-lane decoder in a launch that skips every other segment: bytes and status of a
+ * damaged file are the one-lane path's by construction.  info_out_dev: int32 [n][2], per image the segments that fell back and the
+ * most hand-over rounds one of its segments took (0, 0 without split segments).  The workspace holds, after that of
+ * bvc_op_jpeg_decode, per segment a flag, a round count and a routed segment record, and per 8 x 8 block 4 + 128 bytes.
+ * bvc_jpeg_decode_host_split: the split path in plain C++, its lanes run one after another (csrc/jpeg.h, decode_segment_split);
+ * info_out: int32 [2] as above.  bvc_jpeg_split_chunk: c of the rule above for a segment of `bytes` bytes. */
 #define BVC_JPEG_MAX_DIM 4096
+#define BVC_JPEG_SPLIT_THREADS 512
+#define BVC_JPEG_SPLIT_MIN_CHUNK 16
+#define BVC_JPEG_SPLIT_DEFAULT_CHUNK 64
 enum {
     BVC_JPEG_REFUSE_NOT_JPEG = 1, BVC_JPEG_REFUSE_BAD_LENGTH = 2, BVC_JPEG_REFUSE_PROGRESSIVE = 3, BVC_JPEG_REFUSE_ARITHMETIC = 4,
     BVC_JPEG_REFUSE_LOSSLESS = 5, BVC_JPEG_REFUSE_PRECISION = 6, BVC_JPEG_REFUSE_COMPONENTS = 7, BVC_JPEG_REFUSE_RGB = 8,
@@ -504,6 +531,14 @@ int bvc_op_jpeg_decode(const uint8_t* blob_dev, int64_t blob_bytes, const bvc_jp
                        const int32_t* segs_host, const int32_t* segs_dev, int64_t nseg, const int64_t* out_offsets_host,
                        const int64_t* out_offsets_dev, uint8_t* out_dev, int64_t out_bytes, int32_t* status_dev, void* workspace_dev,
                        int64_t workspace_bytes, int lanes, int stages, void* stream);
+int bvc_jpeg_split_chunk(int bytes, int chunk);
+int bvc_jpeg_decode_host_split(const uint8_t* data, int64_t n, const bvc_jpeg_info* info, const int32_t* seg, int split, int chunk,
+                               uint8_t* out_rgb, int32_t* info_out);
+int64_t bvc_op_jpeg_decode_split_workspace(bvc_jpeg_info* infos_host, int n);
+int bvc_op_jpeg_decode_split(const uint8_t* blob_dev, int64_t blob_bytes, const bvc_jpeg_info* infos_host, const bvc_jpeg_info* infos_dev,
+                             int n, const int32_t* segs_host, const int32_t* segs_dev, int64_t nseg, const int64_t* out_offsets_host,
+                             const int64_t* out_offsets_dev, uint8_t* out_dev, int64_t out_bytes, int32_t* status_dev, void* workspace_dev,
+                             int64_t workspace_bytes, int lanes, int stages, int split, int chunk, int32_t* info_out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * JEPA encoder and predictor (pretraining/predictive/vision_transformer.py).  Same conventions as above: flat f32

@@ -41,6 +41,11 @@ class Policy:
     grads: bool = True
     gelu_grad: bool = True
     autocast_outputs: bool = False      # + linear outputs and weight gradients rounded (CUDA / CPU autocast proper)
+    # the attention forward as the build's kernel forms it (attention.hip, fwd_subtile): the probability operand of P V is the
+    # UNNORMALISED exp(s - rowmax) rounded to bf16, the f32 accumulator is divided by the f32 row sum of the unrounded values.  Off
+    # (today's behaviour of every caller but tests/jepa_rows_ref.py): the normalised p is rounded.  The two differ where many keys
+    # share one probability: 9 keys at p = 1/9 all round by +0.2 %, so r(p) V is 0.2 % over in every row, exp(s - max) ~ 1 is not.
+    p_unnormalised: bool = False
 
     def label(self):
         on = [k for k in ("weights", "acts", "grads", "gelu_grad", "autocast_outputs") if getattr(self, k)]
@@ -111,7 +116,11 @@ class _Attention(torch.autograd.Function):
         d = q.shape[-1]
         s = torch.matmul(q, k.transpose(-1, -2)) * (d ** -0.5)
         p = torch.softmax(s, dim=-1)
-        o = _r(torch.matmul(_r(p, pol.acts), v), pol.acts)
+        if pol.acts and pol.p_unnormalised:
+            e = torch.exp(s - s.amax(dim=-1, keepdim=True))
+            o = _r(torch.matmul(_r(e), v) / e.sum(dim=-1, keepdim=True))
+        else:
+            o = _r(torch.matmul(_r(p, pol.acts), v), pol.acts)
         ctx.save_for_backward(q, k, v, p, o)
         ctx.pol = pol
         return o

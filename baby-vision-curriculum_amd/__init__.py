@@ -15,6 +15,7 @@ from ._lib import use_deterministic_algorithms, are_deterministic_algorithms_ena
 from .videomae import (VideoMAEConfig, VideoMAEForPreTraining, VideoMAEForPreTrainingOutput, VideoMAEForVideoClassification,  # noqa: F401
                        get_config, get_model, VIDEOMAE_ARCHS, videomae_config, soft_target_cross_entropy)
 from .mixup import Mixup, ClipMix  # noqa: F401
+from .erase import RandomErasing, ClipErase, erase_noise  # noqa: F401
 from .mask import TubeMaskingGenerator, RandomMaskingGenerator, DecoderSubsetGenerator  # noqa: F401
 from .ddp import DistributedDataParallel  # noqa: F401
 from .ddputils import AllReduce  # noqa: F401

@@ -230,6 +230,9 @@ SYMBOLS = {
     "bvc_videomae_encoder_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_videomae_cls_set_mix": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "bvc_videomae_encoder_set_mix": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "bvc_videomae_cls_set_erase": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
+    "bvc_videomae_encoder_set_erase": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
+    "bvc_op_erase_noise": (c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bvc_vit_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_predictor_set_drop": (c_int, [c_void_p, ctypes.POINTER(BranchDropC), c_int, c_void_p]),
     "bvc_op_attention_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -300,6 +303,8 @@ SYMBOLS = {
     "bvc_op_gather_patches": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_op_gather_patches_mix": (c_int, [c_void_p, ctypes.POINTER(PixelFormatC), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                           c_int, c_int, c_int, c_int, c_void_p]),
+    "bvc_op_gather_patches_aug": (c_int, [c_void_p, ctypes.POINTER(PixelFormatC), c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint64,
+                                          ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_op_pixel_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bvc_comm_unique_id": (c_int, [c_void_p]),
     "bvc_comm_init": (c_int, [c_int, c_int, c_void_p, ctypes.POINTER(c_void_p)]),

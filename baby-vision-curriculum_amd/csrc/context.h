@@ -28,6 +28,16 @@ struct MixState {
 int alloc_mix(Arena& a, MixState& m, int max_batch);
 int set_mix(MixState& m, const bvc_clip_mix* mix, int samples, int max_batch, const char* who);
 
+// Random erasing of a classification context (bvc_*_set_erase); its forward reports through the MixState's status word
+struct EraseState {
+    EraseBox* table = nullptr;         // the context's copy, max_batch * BVC_ERASE_MAX_BOXES entries
+    const bvc_erase_box* armed = nullptr;
+    int samples = 0, boxes = 0;
+    uint64_t seed = 0, offset = 0;
+};
+int alloc_erase(Arena& a, EraseState& e, int max_batch);
+int set_erase(EraseState& e, const bvc_erase_box* tab, int samples, int boxes, uint64_t seed, uint64_t offset, int max_batch, const char* who);
+
 template <typename Config>   // bvc_videomae_config and bvc_vit_config name these fields alike
 PatchGeom patch_geom(const Config& c) { return PatchGeom{c.num_frames, c.num_channels, c.image_size, c.image_size, c.tubelet_size, c.patch_size}; }
 inline int seq_len(PatchGeom g) { return (g.T / g.ts) * (g.H / g.ps) * (g.W / g.ps); }
@@ -42,9 +52,10 @@ struct PatchFront {
     bf16_t* Ape = nullptr;     // bf16 [max_tokens][Kp] gathered tubes
     // with identity_list, idx_all is filled on the null stream and that stream synchronised: a first forward on any stream may read it
     int alloc(Arena& a, PatchGeom geom, size_t max_tokens, bool identity_list);
-    // gather (consuming an armed mix, when the context has one) + projection + bias + pos[idx] -> out f32 [B*N][D]
+    // gather (consuming an armed mix and an armed erase, when the context has them) + projection + bias + pos[idx] -> out f32 [B*N][D];
+    // *mixed: either was armed, so mix->status is to be checked
     int embed(PixelSrc px, const int* idx, int B, int N, const bf16_t* w, const float* bias, const float* pos, float* out, int D,
-              hipStream_t st, const char* who, MixState* mix = nullptr, bool* mixed = nullptr);
+              hipStream_t st, const char* who, MixState* mix = nullptr, bool* mixed = nullptr, EraseState* erase = nullptr);
     // weight and bias gradients from the stack's last bf16 copy (pixels need no gradient)
     int embed_backward(Work& w, int M, int D, float* gw, float* gb, hipStream_t st);
 };

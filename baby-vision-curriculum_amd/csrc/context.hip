@@ -32,17 +32,39 @@ int set_mix(MixState& m, const bvc_clip_mix* mix, int samples, int max_batch, co
     return BVC_OK;
 }
 
-// the gather of a forward: the plain kernel, or - consuming an armed table - the mix kernel on the context's copy of it
-static int gather_for_forward(MixState& m, bool* mixed, PixelSrc pixels, const int* idx, bf16_t* A, int B, int N, PatchGeom pg, const char* who,
-                              hipStream_t st) {
+int alloc_erase(Arena& a, EraseState& e, int max_batch) { return a.alloc(&e.table, (size_t)max_batch * BVC_ERASE_MAX_BOXES); }
+
+int set_erase(EraseState& e, const bvc_erase_box* tab, int samples, int boxes, uint64_t seed, uint64_t offset, int max_batch, const char* who) {
+    e.armed = nullptr;
+    if (!tab) return BVC_OK;
+    BVC_REQUIRE(samples >= 1 && samples <= max_batch, "%s: %d samples outside [1, %d]", who, samples, max_batch);
+    BVC_REQUIRE(boxes >= 1 && boxes <= BVC_ERASE_MAX_BOXES, "%s: %d boxes per clip outside [1, %d]", who, boxes, BVC_ERASE_MAX_BOXES);
+    e.armed = tab;
+    e.samples = samples;
+    e.boxes = boxes;
+    e.seed = seed;
+    e.offset = offset;
+    return BVC_OK;
+}
+
+// the gather of a forward: the plain kernel, or - consuming an armed table - the mix kernel on the context's copy of it, or - consuming
+// an armed erase table, with or without a mix - the erase-then-mix kernel on the context's copies of both
+static int gather_for_forward(MixState& m, EraseState* er, bool* mixed, PixelSrc pixels, const int* idx, bf16_t* A, int B, int N, PatchGeom pg,
+                              const char* who, hipStream_t st) {
     const bvc_clip_mix* src = m.armed;
+    const bvc_erase_box* esrc = er ? er->armed : nullptr;
     m.armed = nullptr;
-    *mixed = src != nullptr;
-    if (!src) return launch_gather_patches(pixels, idx, A, B, N, pg, st);
-    BVC_REQUIRE(m.samples == B, "%s: the mix was set for %d samples, the call has %d", who, m.samples, B);
-    BVC_CHECK_HIP(hipMemcpyAsync(m.table, src, (size_t)B * sizeof(ClipMix), hipMemcpyDeviceToDevice, st));
+    if (er) er->armed = nullptr;
+    *mixed = src != nullptr || esrc != nullptr;
+    if (!src && !esrc) return launch_gather_patches(pixels, idx, A, B, N, pg, st);
+    if (src) BVC_REQUIRE(m.samples == B, "%s: the mix was set for %d samples, the call has %d", who, m.samples, B);
+    if (esrc) BVC_REQUIRE(er->samples == B, "%s: the erase was set for %d samples, the call has %d", who, er->samples, B);
+    if (src) BVC_CHECK_HIP(hipMemcpyAsync(m.table, src, (size_t)B * sizeof(ClipMix), hipMemcpyDeviceToDevice, st));
     BVC_CHECK_HIP(hipMemsetAsync(m.status, 0, 4, st));
-    return launch_gather_patches_mix(pixels, idx, A, B, N, pg, m.table, st, m.status);
+    if (!esrc) return launch_gather_patches_mix(pixels, idx, A, B, N, pg, m.table, st, m.status);
+    BVC_CHECK_HIP(hipMemcpyAsync(er->table, esrc, (size_t)B * er->boxes * sizeof(EraseBox), hipMemcpyDeviceToDevice, st));
+    return launch_gather_patches_aug(pixels, idx, A, B, N, pg, src ? m.table : nullptr, erase_tab(er->table, er->boxes, er->seed, er->offset), st,
+                                     m.status);
 }
 
 int pixel_src(const char* who, const void* pixels, const bvc_pixel_format* fmt, int channels, PixelSrc* out) {
@@ -74,8 +96,8 @@ int PatchFront::alloc(Arena& a, PatchGeom geom, size_t max_tokens, bool identity
 }
 
 int PatchFront::embed(PixelSrc px, const int* idx, int B, int N, const bf16_t* w, const float* bias, const float* pos, float* out, int D,
-                      hipStream_t st, const char* who, MixState* mix, bool* mixed) {
-    if (mix) TRY(gather_for_forward(*mix, mixed, px, idx, Ape, B, N, pg, who, st));
+                      hipStream_t st, const char* who, MixState* mix, bool* mixed, EraseState* erase) {
+    if (mix) TRY(gather_for_forward(*mix, erase, mixed, px, idx, Ape, B, N, pg, who, st));
     else TRY(launch_gather_patches(px, idx, Ape, B, N, pg, st));
     const int M = B * N;
     GemmProblem p = gemm(Ape, (size_t)M * Kp, Kp, w, (size_t)D * Kp, Kp, M, D, Kp, EPI_POS, out, D);

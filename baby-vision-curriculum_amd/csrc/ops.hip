@@ -344,6 +344,22 @@ int bvc_op_gather_patches_mix(const void* clip, const bvc_pixel_format* fmt, con
     TRY(pixel_src("op_gather_patches_mix", clip, fmt, C, &px));
     return launch_gather_patches_mix(px, idx, (bf16_t*)A, B, n, PatchGeom{T, C, H, W, ts, ps}, mix, (hipStream_t)stream);
 }
+int bvc_op_gather_patches_aug(const void* clip, const bvc_pixel_format* fmt, const int* idx, void* A, const bvc_clip_mix* mix,
+                              const bvc_erase_box* erase, int boxes, uint64_t seed, uint64_t offset, int B, int n, int T, int C, int H, int W,
+                              int ts, int ps, void* stream) {
+    BVC_REQUIRE(clip && idx && A && erase, "op_gather_patches_aug: null argument");
+    BVC_REQUIRE(boxes >= 1 && boxes <= BVC_ERASE_MAX_BOXES, "op_gather_patches_aug: %d boxes per clip outside [1, %d]", boxes, BVC_ERASE_MAX_BOXES);
+    BVC_REQUIRE(T >= 1 && C >= 1 && H >= 1 && W >= 1 && ts >= 1 && ps >= 1 && T % ts == 0 && H % ps == 0 && W % ps == 0,
+                "op_gather_patches_aug: bad geometry");
+    PixelSrc px;
+    TRY(pixel_src("op_gather_patches_aug", clip, fmt, C, &px));
+    return launch_gather_patches_aug(px, idx, (bf16_t*)A, B, n, PatchGeom{T, C, H, W, ts, ps}, mix, erase_tab(erase, boxes, seed, offset),
+                                     (hipStream_t)stream);
+}
+int bvc_op_erase_noise(uint64_t seed, uint64_t offset, int kind, int B, int T, int C, int H, int W, float* out_dev, void* stream) {
+    BVC_REQUIRE(out_dev, "op_erase_noise: null argument");
+    return launch_erase_noise(erase_tab(nullptr, 0, seed, offset), kind, B, T, C, H, W, out_dev, (hipStream_t)stream);
+}
 int bvc_op_pixel_labels(const float* clip, const int* msk_idx, float* labels, int B, int nmask, int T, int C, int H, int W, int ts,
                         int ps, int norm_pix, void* stream) {
     BVC_REQUIRE(clip && msk_idx && labels, "op_pixel_labels: null argument");

@@ -61,6 +61,21 @@ int launch_gather_patches(PixelSrc clip, const int* vis_idx, bf16_t* A, int B, i
 typedef bvc_clip_mix ClipMix;
 int launch_gather_patches_mix(PixelSrc clip, const int* idx, bf16_t* A, int B, int n, PatchGeom pg, const ClipMix* mix, hipStream_t s,
                               int* status = nullptr);
+// the same with every clip erased first (random erasing, bvc_erase_box in include/bvc.h): a device table of [B][boxes] entries and
+// the generator's key and call offset; mix may be null (no mix).  Entries out of range are clamped and raise bit 0 of *status
+typedef bvc_erase_box EraseBox;
+struct EraseTab {
+    const EraseBox* tab;
+    int boxes;
+    uint32_t key0, key1, off0, off1;
+};
+inline EraseTab erase_tab(const EraseBox* tab, int boxes, uint64_t seed, uint64_t offset) {
+    return EraseTab{tab, boxes, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
+}
+int launch_gather_patches_aug(PixelSrc clip, const int* idx, bf16_t* A, int B, int n, PatchGeom pg, const ClipMix* mix, EraseTab er,
+                              hipStream_t s, int* status = nullptr);
+// the values that kernel writes: kind 0 the pixel noise of a batch [B][T][C][H][W], kind 1 the colours [B][T][4][4] (er.tab unused)
+int launch_erase_noise(EraseTab er, int kind, int B, int T, int C, int H, int W, float* out, hipStream_t s);
 // x[0 .. count) = NaN when bit 0 of *status is set (the device-side report of a failed input check; no host sync)
 int launch_poison_on_status(float* x, size_t count, const int* status, hipStream_t s);
 // dec_idx [B][ndec]: the tokens the decoder reconstructs (every masked token, or the decoded subset), ascending per clip;

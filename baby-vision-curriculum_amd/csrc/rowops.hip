@@ -663,6 +663,150 @@ __global__ void gather_patches_mix_kernel(const PixelSrc clip, const int* __rest
         uint4{pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(d[0], d[1]), pack2bf(d[2], d[3])};
 }
 
+// ============================================================================ tube-patch gather with random erasing, then Mixup / CutMix
+// Four N(0, 1) values from one Philox call (include/bvc.h, bvc_erase_box): counter {low q, high q | tag << 16, offset}, key = seed;
+// lanes 0 / 1 the cos / sin branch of Box-Muller on (r0, r1), lanes 2 / 3 on (r2, r3).  Both uniforms are exact in f32 and u1 > 0.
+__device__ __forceinline__ f32x4 erase_normals4(const EraseTab& er, uint64_t q, uint32_t tag) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)q, (uint32_t)(q >> 32) | (tag << 16), er.off0, er.off1, er.key0, er.key1, r);
+    f32x4 z;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = (float)((r[2 * h] >> 8) + 1u) * 0x1p-24f, u2 = (float)(r[2 * h + 1] >> 8) * 0x1p-24f;
+        const float rad = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        z[2 * h] = rad * cs;
+        z[2 * h + 1] = rad * sn;
+    }
+    return z;
+}
+
+// out: kind 0 the pixel noise of elements 4 i .. 4 i + 3 of a batch, kind 1 the four channels' colours of (clip, frame, box) i
+__global__ void erase_noise_kernel(EraseTab er, int kind, size_t quads, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < quads) reinterpret_cast<f32x4*>(out)[i] = erase_normals4(er, i, kind == 0 ? 0xE0u : 0xE1u);
+}
+
+// What the boxes of clip s (row = its `boxes` table entries) put on the 8-pixel run of frame t, channel c, image row y that starts at
+// column x, whose first element is e0 (a multiple of 4): v[p] for every covered pixel p, the later box over the earlier.  Returns
+// the bit mask of covered pixels; *bad is set when an entry had to be clamped.  The entries and c are wave-uniform in the
+// WAVE_ROW instantiation (scalar loads, clamps in SGPRs); t, y and x are per lane.  Colours cost one Philox call per rand box that
+// touches the run, pixel noise one per covered half of the run, after the last box is known.
+__device__ __forceinline__ int erase_run(const EraseTab& er, const EraseBox* __restrict__ row, const PatchGeom& pg, int s, int t, int c,
+                                         int y, int x, uint64_t e0, float (&v)[8], bool* bad) {
+    int cov = 0, pix = 0;
+#pragma unroll
+    for (int j = 0; j < BVC_ERASE_MAX_BOXES; ++j) {
+        if (j >= er.boxes) break;
+        const EraseBox e = row[j];
+        const int y0 = min(max(e.y0, 0), pg.H), y1 = min(max(e.y1, 0), pg.H), x0 = min(max(e.x0, 0), pg.W), x1 = min(max(e.x1, 0), pg.W);
+        const int mode = min(max(e.mode, 0), 2);
+        if (y0 != e.y0 || y1 != e.y1 || x0 != e.x0 || x1 != e.x1 || mode != e.mode) *bad = true;
+        const int lo = max(x0 - x, 0), hi = min(x1 - x, 8);
+        if (y < y0 || y >= y1 || lo >= hi) continue;
+        const int m = ((1 << hi) - 1) & ~((1 << lo) - 1);
+        cov |= m;
+        if (mode == 2) { pix |= m; continue; }
+        pix &= ~m;
+        float val = 0.f;
+        if (mode == 1) val = erase_normals4(er, ((uint64_t)s * pg.T + t) * 4 + j, 0xE1u)[c & 3];
+#pragma unroll
+        for (int p = 0; p < 8; ++p) v[p] = (m >> p) & 1 ? val : v[p];
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (!((pix >> (4 * h)) & 15)) continue;
+        const f32x4 z = erase_normals4(er, (e0 >> 2) + h, 0xE0u);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) v[4 * h + p] = (pix >> (4 * h + p)) & 1 ? z[p] : v[4 * h + p];
+    }
+    return cov;
+}
+
+// the run of clip s after erasing: the erased values where a box covers it, the source elsewhere - not loaded when all is covered
+__device__ __forceinline__ void erased_pixels8(const PixelSrc& clip, const EraseTab& er, const PatchGeom& pg, int s, int t, int c, int y,
+                                               int x, size_t src, f32x4& a, f32x4& d, bool* bad) {
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int cov = erase_run(er, er.tab + (size_t)s * er.boxes, pg, s, t, c, y, x, (uint64_t)src, v, bad);
+    if (cov != 0xff) {
+        a = load_pixels4(clip, src, c);
+        d = load_pixels4(clip, src + 4, c);
+    }
+    if (cov) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            a[p] = (cov >> p) & 1 ? v[p] : a[p];
+            d[p] = (cov >> (p + 4)) & 1 ? v[p + 4] : d[p];
+        }
+    }
+}
+
+// gather_patches_mix_kernel with every clip erased before it is mixed: out = mix entry of clip b applied to erased(b) and
+// erased(partner), where erased(s) is clip s with its boxes' content in place of the source (bvc_erase_box).  A clip's erased content
+// is a function of (seed, offset, clip, position) only, so it is the same read as `own` and as a `partner`.  As in the mix kernel a
+// source is read only where its value is used; of that, a run a box covers whole issues no load and a run no box touches costs the
+// box compares alone.  mix == nullptr: no mix (partner b, lam 1, empty box).  Neither table is trusted: boxes are clamped to the
+// image and modes to 0 .. 2 before any address or counter is formed, and the first thread of clip b raises bit 0 of *status for
+// clip b's entries.
+template <bool WAVE_ROW>
+__global__ void gather_patches_aug_kernel(const PixelSrc clip, const int* __restrict__ idx, bf16_t* __restrict__ A, int B, int n,
+                                          PatchGeom pg, const ClipMix* __restrict__ mix, const EraseTab er, int* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int K = pg.C * pg.ts * pg.ps * pg.ps;
+    const int k8 = K >> 3;
+    if (i >= (size_t)B * n * k8) return;
+    const int mv = (int)(i / k8);
+    const int m = WAVE_ROW ? __builtin_amdgcn_readfirstlane(mv) : mv;
+    const int k = (int)(i - (size_t)m * k8) * 8;
+    const int dx = k % pg.ps, dy = (k / pg.ps) % pg.ps, dt = (k / (pg.ps * pg.ps)) % pg.ts, c = k / (pg.ps * pg.ps * pg.ts);
+    const int b = m / n, tok = idx[m];
+    const int wp = pg.W / pg.ps, hp = pg.H / pg.ps;
+    const int tp = tok / (hp * wp), yp = (tok / wp) % hp, xp = tok % wp;
+    const int t = tp * pg.ts + dt, y = yp * pg.ps + dy, x = xp * pg.ps + dx;
+    ClipMix e = ClipMix{b, 1.0f, 0, 0, 0, 0};
+    if (mix) e = mix[b];
+    const int partner = min(max(e.partner, 0), B - 1);
+    const int y0 = min(max(e.y0, 0), pg.H), y1 = min(max(e.y1, 0), pg.H), x0 = min(max(e.x0, 0), pg.W), x1 = min(max(e.x1, 0), pg.W);
+    const float lam = e.lam;
+    bool bad = partner != e.partner || y0 != e.y0 || y1 != e.y1 || x0 != e.x0 || x1 != e.x1 || !(lam >= 0.f && lam <= 1.f);
+    const size_t in_clip = ((((size_t)t) * pg.C + c) * pg.H + y) * pg.W + x;
+    const size_t per_clip = (size_t)pg.T * pg.C * pg.H * pg.W;
+    const size_t own = (size_t)b * per_clip + in_clip, oth = (size_t)partner * per_clip + in_clip;
+    // pixels of the run inside the mix box: [lo, hi) in run coordinates
+    const bool row_in = y >= y0 && y < y1;
+    const int lo = row_in ? max(x0 - x, 0) : 8, hi = row_in ? min(x1 - x, 8) : 0;
+    const bool all_in = lo == 0 && hi == 8, none_in = lo >= hi;
+    f32x4 a = {0.f, 0.f, 0.f, 0.f}, d = a, a1 = a, d1 = a;
+    bool bad_oth = false;      // the partner's entries are reported by the partner's own first thread
+    if (!all_in) erased_pixels8(clip, er, pg, b, t, c, y, x, own, a, d, &bad);
+    if (!(none_in && lam == 1.0f)) erased_pixels8(clip, er, pg, partner, t, c, y, x, oth, a1, d1, &bad_oth);
+    if (all_in) { a = a1; d = d1; }
+    else if (!(none_in && lam == 1.0f)) {
+        const float rem = 1.0f - lam;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ma = lam == 1.0f ? a[j] : lam * a[j] + rem * a1[j];
+            const float md = lam == 1.0f ? d[j] : lam * d[j] + rem * d1[j];
+            a[j] = (j >= lo && j < hi) ? a1[j] : ma;
+            d[j] = (j + 4 >= lo && j + 4 < hi) ? d1[j] : md;
+        }
+    }
+    if (status && k == 0 && m % n == 0) {
+        // a run the mix box covers whole did not look at clip b's own entries: check them here
+        if (all_in) {
+            for (int j = 0; j < er.boxes && j < BVC_ERASE_MAX_BOXES; ++j) {
+                const EraseBox q = er.tab[(size_t)b * er.boxes + j];
+                bad |= q.y0 < 0 || q.y0 > pg.H || q.y1 < 0 || q.y1 > pg.H || q.x0 < 0 || q.x0 > pg.W || q.x1 < 0 || q.x1 > pg.W ||
+                       q.mode < 0 || q.mode > 2;
+            }
+        }
+        if (bad) atomicOr(status, 1);
+    }
+    *reinterpret_cast<uint4*>(A + (size_t)m * K + k) =
+        uint4{pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(d[0], d[1]), pack2bf(d[2], d[3])};
+}
+
 // x[i] = NaN for every i when bit 0 of *status is set: how a call whose device-side input check failed reports it without a host sync
 __global__ void poison_on_status_kernel(float* __restrict__ x, size_t count, const int* __restrict__ status) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2063,6 +2207,31 @@ int launch_gather_patches_mix(PixelSrc clip, const int* idx, bf16_t* A, int B, i
         hipLaunchKernelGGL(gather_patches_mix_kernel<true>, dim3(blocks_for(items)), dim3(256), 0, s, clip, idx, A, B, n, pg, mix, status);
     else
         hipLaunchKernelGGL(gather_patches_mix_kernel<false>, dim3(blocks_for(items)), dim3(256), 0, s, clip, idx, A, B, n, pg, mix, status);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_gather_patches_aug(PixelSrc clip, const int* idx, bf16_t* A, int B, int n, PatchGeom pg, const ClipMix* mix, EraseTab er,
+                              hipStream_t s, int* status) {
+    BVC_REQUIRE(clip.ptr && idx && A && er.tab, "gather_patches_aug: null argument");
+    BVC_REQUIRE(B >= 1 && n >= 1, "gather_patches_aug: B=%d clips of n=%d tokens", B, n);
+    BVC_REQUIRE(er.boxes >= 1 && er.boxes <= BVC_ERASE_MAX_BOXES, "gather_patches_aug: %d boxes per clip outside [1, %d]", er.boxes, BVC_ERASE_MAX_BOXES);
+    BVC_REQUIRE(pg.ps % 8 == 0 && pg.W % 4 == 0, "gather_patches_aug: patch size must be a multiple of 8");
+    BVC_REQUIRE(pg.C <= 4, "gather_patches_aug: %d channels (the colour counter holds at most 4)", pg.C);
+    const size_t items = (size_t)B * n * (pg.C * pg.ts * pg.ps * pg.ps / 8);
+    if ((pg.C * pg.ts * pg.ps * pg.ps / 8) % 64 == 0)
+        hipLaunchKernelGGL(gather_patches_aug_kernel<true>, dim3(blocks_for(items)), dim3(256), 0, s, clip, idx, A, B, n, pg, mix, er, status);
+    else
+        hipLaunchKernelGGL(gather_patches_aug_kernel<false>, dim3(blocks_for(items)), dim3(256), 0, s, clip, idx, A, B, n, pg, mix, er, status);
+    BVC_CHECK_HIP(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_erase_noise(EraseTab er, int kind, int B, int T, int C, int H, int W, float* out, hipStream_t s) {
+    BVC_REQUIRE(out && (kind == 0 || kind == 1), "erase_noise: kind %d unknown", kind);
+    BVC_REQUIRE(B >= 1 && T >= 1 && C >= 1 && H >= 1 && W >= 1 && W % 4 == 0, "erase_noise: bad geometry (W must be a multiple of 4)");
+    const size_t quads = kind == 0 ? (size_t)B * T * C * H * (W / 4) : (size_t)B * T * 4;
+    hipLaunchKernelGGL(erase_noise_kernel, dim3(blocks_for(quads)), dim3(256), 0, s, er, kind, quads, out);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
 }

@@ -468,6 +468,7 @@ struct bvc_encoder_ctx {
     int pooled_batch = 0;    // clips whose pre-norm pooled rows and fc_norm statistics the last encode left (0: none)
     DropState drop;          // bvc_videomae_encoder_set_drop: the forward gate of a train-mode module on the forward-only path
     MixState mix;            // bvc_videomae_encoder_set_mix
+    EraseState erase;        // bvc_videomae_encoder_set_erase
 };
 
 void bvc_videomae_encoder_destroy(bvc_encoder_ctx* c) {
@@ -500,6 +501,7 @@ int bvc_videomae_encoder_create(const bvc_videomae_config* cfg, int max_batch, b
     TRY(alloc_stack(c->arena, c->st, D, I, H, 1, cfg->layer_norm_eps, M, (size_t)max_batch * H * c->L));
     TRY(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
     TRY(alloc_mix(c->arena, c->mix, max_batch));
+    TRY(alloc_erase(c->arena, c->erase, max_batch));
     TRY(c->arena.alloc(&c->xa, M * D));
     TRY(c->arena.alloc(&c->xb, M * D));
     TRY(c->arena.alloc(&c->pooled, (size_t)max_batch * D));
@@ -545,7 +547,8 @@ int bvc_videomae_encode_ex(bvc_encoder_ctx* c, const void* pixels_any, const bvc
     float* x = hs ? hs : c->xa;                                // given hidden_states, slot 0 is the embedding output
     float* y = c->xb;
     bool mixed = false;
-    TRY(c->front.embed(pixels, c->front.idx_all, B, N, c->shadow.wbf + L.pe_w, params + L.pe_b, c->pos_enc, x, D, st, "encode", &c->mix, &mixed));
+    TRY(c->front.embed(pixels, c->front.idx_all, B, N, c->shadow.wbf + L.pe_w, params + L.pe_b, c->pos_enc, x, D, st, "encode", &c->mix, &mixed,
+                       &c->erase));
     const int nl = (int)L.enc.size();
     for (int i = 0; i < nl; ++i) {
         // the last layer writes straight into the caller's buffer; with hidden_states, layer i reads slot i and writes slot i + 1
@@ -583,6 +586,13 @@ int bvc_videomae_encoder_set_mix(bvc_encoder_ctx* c, const bvc_clip_mix* mix_dev
     return set_mix(c->mix, mix_dev, samples, c->max_batch, "encoder_set_mix");
 }
 
+int bvc_videomae_encoder_set_erase(bvc_encoder_ctx* c, const bvc_erase_box* tab_dev, int samples, int boxes, uint64_t seed, uint64_t offset,
+                                   void* stream) {
+    (void)stream;      // as for the mix: copied by the forward that consumes it
+    BVC_REQUIRE(c, "encoder_set_erase: null context");
+    return set_erase(c->erase, tab_dev, samples, boxes, seed, offset, c->max_batch, "encoder_set_erase");
+}
+
 int bvc_videomae_encoder_fc_norm_backward(bvc_encoder_ctx* c, const float* dpooled, const float* fc_norm_w, float* dfc_norm_w,
                                           float* dfc_norm_b, void* stream) {
     BVC_REQUIRE(c && dpooled && fc_norm_w && dfc_norm_w && dfc_norm_b, "encoder_fc_norm_backward: null argument");
@@ -613,6 +623,7 @@ struct bvc_cls_ctx {
     bool have_forward = false;
     DropState drop;              // bvc_videomae_cls_set_drop
     MixState mix;                // bvc_videomae_cls_set_mix
+    EraseState erase;            // bvc_videomae_cls_set_erase
 };
 
 void bvc_videomae_cls_destroy(bvc_cls_ctx* c) {
@@ -646,6 +657,7 @@ int bvc_videomae_cls_create(const bvc_videomae_config* cfg, int max_batch, bvc_c
     TRY(alloc_stack(c->arena, c->enc, D, I, H, cfg->num_hidden_layers, cfg->layer_norm_eps, M, (size_t)max_batch * H * L));
     TRY(alloc_drop(c->arena, c->drop, cfg->num_hidden_layers, max_batch));
     TRY(alloc_mix(c->arena, c->mix, max_batch));
+    TRY(alloc_erase(c->arena, c->erase, max_batch));
     TRY(c->arena.alloc(&c->pooled_pre, (size_t)max_batch * D));
     TRY(c->arena.alloc(&c->mean, (size_t)max_batch));
     TRY(c->arena.alloc(&c->rstd, (size_t)max_batch));
@@ -678,7 +690,7 @@ int bvc_videomae_cls_forward_px(bvc_cls_ctx* c, const void* pixels_any, const bv
     TRY(c->shadow.refresh(params, st));
     bool mixed = false;
     TRY(c->front.embed(pixels, c->front.idx_all, B, N, c->shadow.wbf + L.pe_w, params + L.pe_b, c->pos_enc, c->enc.act[0].x_in, D, st,
-                       "cls_forward", &c->mix, &mixed));
+                       "cls_forward", &c->mix, &mixed, &c->erase));
     TRY(stack_forward(c->w, c->enc, L.enc, B, N, st, false));     // unchained, as the inference context runs its layers
     TRY(launch_token_mean(c->enc.x_out, B, N, D, c->pooled_pre, st));
     TRY(launch_ln_fwd(c->pooled_pre, identity_rows(), fc_norm_w, fc_norm_b, nullptr, c->mean, c->rstd, B, D, fc_norm_eps, st, pooled));
@@ -739,6 +751,13 @@ int bvc_videomae_cls_set_mix(bvc_cls_ctx* c, const bvc_clip_mix* mix_dev, int sa
     (void)stream;      // the table is copied by the forward that consumes it, on that forward's stream
     BVC_REQUIRE(c, "cls_set_mix: null context");
     return set_mix(c->mix, mix_dev, samples, c->max_batch, "cls_set_mix");
+}
+
+int bvc_videomae_cls_set_erase(bvc_cls_ctx* c, const bvc_erase_box* tab_dev, int samples, int boxes, uint64_t seed, uint64_t offset,
+                               void* stream) {
+    (void)stream;      // as for the mix: copied by the forward that consumes it
+    BVC_REQUIRE(c, "cls_set_erase: null context");
+    return set_erase(c->erase, tab_dev, samples, boxes, seed, offset, c->max_batch, "cls_set_erase");
 }
 
 int bvc_videomae_cls_shadow(bvc_cls_ctx* c, int valid, void** shadow_bf16, int64_t* numel) {

@@ -448,9 +448,9 @@ class _ClsTrain(torch.autograd.Function):
     buffer (views as .grad) and returns fc_norm's gradients to autograd."""
 
     @staticmethod
-    def forward(ctx, anchor, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False, mix=None):
+    def forward(ctx, anchor, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False, mix=None, erase=None):
         ctx.model = model
-        pooled, tokens, hs, att = model._run_train_forward(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions, mix)
+        pooled, tokens, hs, att = model._run_train_forward(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions, mix, erase)
         ctx.stamp = model._stamp_forward()
         _mark_detached(ctx, tokens, hs, att)
         return pooled, tokens, hs, att
@@ -459,16 +459,16 @@ class _ClsTrain(torch.autograd.Function):
     def backward(ctx, dpooled, _dtokens, _dhs, _datt):
         ctx.model._check_generation(ctx.stamp)
         dw, db = ctx.model._run_train_backward(dpooled)
-        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None, None
+        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None, None, None
 
 
 class _FcNormProbe(torch.autograd.Function):
     """The inference context's encode (today's call, the same bits) with fc_norm under autograd: the linear-probe case."""
 
     @staticmethod
-    def forward(ctx, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False, mix=None):
+    def forward(ctx, fc_w, fc_b, model, pixels, want_tokens, want_hidden=False, want_attentions=False, mix=None, erase=None):
         ctx.model = model
-        pooled, tokens, hs, att = model._run_encode(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions, mix)
+        pooled, tokens, hs, att = model._run_encode(pixels, fc_w, fc_b, want_tokens, want_hidden, want_attentions, mix, erase)
         ctx.stamp = model._stamp_forward()
         ctx.save_for_backward(fc_w)
         _mark_detached(ctx, tokens, hs, att)
@@ -484,7 +484,7 @@ class _FcNormProbe(torch.autograd.Function):
         dw, db = torch.empty_like(w), torch.empty_like(w)
         _lib.check(_lib.lib().bvc_videomae_encoder_fc_norm_backward(m._ctx, g.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                                                     _lib.current_stream_ptr()), "bvc_videomae_encoder_fc_norm_backward")
-        return dw if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None, None, None, None
+        return dw if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None, None, None, None, None
 
 
 class VideoMAEForVideoClassification(FlatParamModule):
@@ -616,6 +616,12 @@ class VideoMAEForVideoClassification(FlatParamModule):
         if mix is not None:
             _lib.check(set_mix(h, mix.table.data_ptr(), int(B), _lib.current_stream_ptr()), "set_mix")
 
+    def _arm_erase(self, set_erase, h, erase, B):
+        """Hand a ClipErase to the context that runs next (``set_erase`` = its bvc_*_set_erase), as ``_arm_mix`` does with a ClipMix."""
+        if erase is not None:
+            _lib.check(set_erase(h, erase.table.data_ptr(), int(B), erase.num_boxes, erase.seed, erase.offset, _lib.current_stream_ptr()),
+                       "set_erase")
+
     def _encoder_trainable(self):
         return any(self._param(n).requires_grad for n in self._names)
 
@@ -623,7 +629,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
     def _fc_norm_args(self, fc_w, fc_b, dev):
         return fc_w.detach().to(device=dev, dtype=torch.float32).contiguous(), fc_b.detach().to(device=dev, dtype=torch.float32).contiguous()
 
-    def _run_encode(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False, mix=None):
+    def _run_encode(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False, mix=None, erase=None):
         cfg = self.config
         B, dev = pixels.shape[0], pixels.device
         fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
@@ -636,6 +642,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
             tokens = hs[-1] if hs is not None else torch.empty((B, cfg.seq_length, cfg.hidden_size), dtype=torch.float32, device=dev)
         self._arm_gate(_lib.lib().bvc_videomae_encoder_set_drop, h, B, dev)     # train mode on the forward-only path: the same gate
         self._arm_mix(_lib.lib().bvc_videomae_encoder_set_mix, h, mix, B)
+        self._arm_erase(_lib.lib().bvc_videomae_encoder_set_erase, h, erase, B)
         args = (h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
                 float(self.fc_norm.eps), tokens.data_ptr() if tokens is not None and hs is None else None, pooled.data_ptr())
         out = _lib.introspect(hs, att)
@@ -645,7 +652,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
             _lib.check(_lib.lib().bvc_videomae_encode_ex(*args, ctypes.byref(out), _lib.current_stream_ptr()), "bvc_videomae_encode_ex")
         return pooled, tokens, hs, att
 
-    def _run_train_forward(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False, mix=None):
+    def _run_train_forward(self, pixels, fc_w, fc_b, want_tokens, want_hidden=False, want_attentions=False, mix=None, erase=None):
         cfg = self.config
         B, dev = pixels.shape[0], pixels.device
         fmt = _lib.pixel_format(pixels, self.pixel_mean, self.pixel_std, cfg.num_channels)
@@ -657,6 +664,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
         self._shadow_vouch(h)
         self._arm_gate(_lib.lib().bvc_videomae_cls_set_drop, h, B, dev)
         self._arm_mix(_lib.lib().bvc_videomae_cls_set_mix, h, mix, B)
+        self._arm_erase(_lib.lib().bvc_videomae_cls_set_erase, h, erase, B)
         _lib.check(_lib.lib().bvc_videomae_cls_forward_px(
             h, pixels.data_ptr(), ctypes.byref(fmt) if fmt is not None else None, B, self._flat.data_ptr(), w.data_ptr(), b.data_ptr(),
             float(self.fc_norm.eps), pooled.data_ptr(), tokens.data_ptr() if tokens is not None else None, _lib.current_stream_ptr()),
@@ -681,7 +689,7 @@ class VideoMAEForVideoClassification(FlatParamModule):
         return dw.to(self.fc_norm.weight.dtype), db.to(self.fc_norm.bias.dtype)
 
     def forward(self, pixel_values=None, labels=None, output_last_hidden_state=False, output_hidden_states=None, output_attentions=None,
-                mix=None, **kwargs):
+                mix=None, erase=None, **kwargs):
         """``output_hidden_states`` / ``output_attentions`` (None = ``config.output_hidden_states`` / ``config.output_attentions``, as in
         transformers): ``hidden_states`` is a tuple of L + 1 tensors (B, N, D) - the embedding output, then every layer's output -
         and ``attentions`` a tuple of L tensors (B, H, N, N) of softmax probabilities (row = query).  Each tuple is f32 views of one
@@ -693,9 +701,17 @@ class VideoMAEForVideoClassification(FlatParamModule):
         ``mix`` (a ``ClipMix`` from ``bvc.Mixup``, train mode only): the clips enter the patch embedding mixed with their partners
         (Mixup / CutMix inside the patch gather, uint8 or f32 input; nothing is written back and ``pixel_values`` is untouched).
         It serves this forward alone.  Pass the soft targets that came with it as ``labels`` under
-        ``config.problem_type = "soft_label_classification"``.  A table entry out of range makes the logits NaN."""
+        ``config.problem_type = "soft_label_classification"``.  A table entry out of range makes the logits NaN.
+
+        ``erase`` (a ``ClipErase`` from ``bvc.RandomErasing``, train mode only): the clips enter the patch embedding with their boxes
+        erased (random erasing inside the patch gather, uint8 or f32 input; nothing is written back).  With ``mix`` as well each clip
+        is erased first and the batch is mixed then.  It serves this forward alone, and a bad table entry makes the logits NaN."""
         if mix is not None and not self.training:
             raise ValueError("mix= in eval mode: evaluating on mixed clips is a mistake (call .train(), or pass mix=None)")
+        if erase is not None and not self.training:
+            raise ValueError("erase= in eval mode: evaluating on erased clips is a mistake (call .train(), or pass erase=None)")
+        if erase is not None and pixel_values is not None and erase.batch_size != pixel_values.shape[0]:
+            raise ValueError(f"erase was built for a batch of {erase.batch_size} clips, pixel_values holds {pixel_values.shape[0]}")
         if pixel_values is None or not pixel_values.is_cuda:
             raise _lib.BvcError("VideoMAEForVideoClassification runs on a GPU only (libbvc_hip.so has no CPU path)")
         cfg = self.config
@@ -710,6 +726,8 @@ class VideoMAEForVideoClassification(FlatParamModule):
                 raise ValueError(f"mix was built for a batch of {mix.batch_size} clips, pixel_values holds {B}")
             if mix.table is None or mix.table.device != dev:
                 raise ValueError(f"mix has no device table on {dev}: build it with device=pixel_values.device")
+        if erase is not None and (erase.table is None or erase.table.device != dev):
+            raise ValueError(f"erase has no device table on {dev}: build it with device=pixel_values.device")
         self._ensure_flat(dev)
         pixels = pixel_values.detach()
         pixels = (pixels if pixels.dtype == torch.uint8 else pixels.to(dtype=torch.float32)).contiguous()
@@ -718,17 +736,17 @@ class VideoMAEForVideoClassification(FlatParamModule):
         fc_w, fc_b = self.fc_norm.weight, self.fc_norm.bias
         if classification_path(self.training, grad, trainable) == "train":
             anchor = next(self._param(n) for n in self._names if self._param(n).requires_grad)
-            pooled, tokens, hs, att = _ClsTrain.apply(anchor, fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att, mix)
+            pooled, tokens, hs, att = _ClsTrain.apply(anchor, fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att, mix, erase)
         else:
             if grad and trainable and not self._warned_eval_grad:
                 self._warned_eval_grad = True
                 warnings.warn("VideoMAEForVideoClassification in eval mode: the encoder receives no gradient (call .train() to "
                               "fine-tune it); fc_norm and the classifier still do", stacklevel=2)
             if grad and (fc_w.requires_grad or fc_b.requires_grad):
-                pooled, tokens, hs, att = _FcNormProbe.apply(fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att, mix)
+                pooled, tokens, hs, att = _FcNormProbe.apply(fc_w, fc_b, self, pixels, output_last_hidden_state, want_hs, want_att, mix, erase)
             else:
                 with torch.no_grad():
-                    pooled, tokens, hs, att = self._run_encode(pixels, fc_w, fc_b, output_last_hidden_state, want_hs, want_att, mix)
+                    pooled, tokens, hs, att = self._run_encode(pixels, fc_w, fc_b, output_last_hidden_state, want_hs, want_att, mix, erase)
                 self._stamp_forward()     # a pending backward of an earlier forward must not run on overwritten state
         logits = self.classifier(pooled)
         loss = classification_loss(cfg, logits, labels) if labels is not None else None

@@ -301,6 +301,39 @@ typedef struct bvc_clip_mix {
 int bvc_videomae_cls_set_mix(bvc_cls_ctx* ctx, const bvc_clip_mix* mix_dev, int samples, void* stream);
 /* forward only (a train-mode linear probe, a train-mode module under torch.no_grad()) */
 int bvc_videomae_encoder_set_mix(bvc_encoder_ctx* ctx, const bvc_clip_mix* mix_dev, int samples, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Random erasing inside the patch gather, before the mix.  Each clip has `boxes` (<= BVC_ERASE_MAX_BOXES) table entries; at pixel
+ * (t, c, y, x) of clip s the LAST entry j with y0 <= y < y1 and x0 <= x < x1 replaces the source pixel (a normalised value) by
+ *     mode 0 (const): 0
+ *     mode 1 (rand):  one N(0, 1) value per clip, frame, box and channel
+ *     mode 2 (pixel): one N(0, 1) value per element
+ * The boxes are the same in every frame, the noise is fresh per frame; an empty box (y0 >= y1 or x0 >= x1) erases nothing.  Then
+ * the clip's bvc_clip_mix entry (when a mix is armed as well) composes the ERASED clip with its ERASED partner: a clip's erased
+ * content depends on (seed, offset, clip, position) only, the same as `own` and as somebody's `partner`.  The erased clip is never
+ * written and a run of pixels a box covers is not loaded.
+ * The values are Box-Muller normals of Philox4x32-10 draws: key = the halves of `seed`, counter words 2 and 3 = the halves of
+ * `offset`.  Pixel noise: element e = (((s T + t) C + c) H + y) W + x, q = e >> 2, lane = e & 3, counter words 0 and 1 =
+ * low 32 bits of q and (q >> 32) | 0xE0 << 16.  Colours: e = ((s T + t) 4 + j) 4 + c (C <= 4), the same split, tag 0xE1 << 16.
+ * From one call's outputs r0 .. r3, lanes 0 / 1 are the cos / sin branch on (r0, r1) and lanes 2 / 3 on (r2, r3):
+ * u1 = ((ra >> 8) + 1) 2^-24, u2 = (rb >> 8) 2^-24, z = sqrt(-2 ln u1) {cos, sin}(2 pi u2) in f32, so |z| <= 5.77.
+ * The *_set_erase calls follow *_set_mix: they arm the NEXT forward of the context, which copies the table ([samples][boxes] entries
+ * of device memory, alive until that forward has been enqueued), gathers through it and disarms; `samples` must equal its batch
+ * (BVC_ERR_INVALID otherwise), boxes must lie in [1, BVC_ERASE_MAX_BOXES], tab_dev == NULL disarms.  Mix and erase are independent:
+ * either, both or neither may be armed.  An entry with a box outside the image or a mode outside 0 .. 2 is clamped before any
+ * address or counter is formed and makes that forward's pooled rows (and tokens) NaN, as a bad mix entry does. */
+#define BVC_ERASE_MAX_BOXES 4
+typedef struct bvc_erase_box {
+    int y0, y1, x0, x1;
+    int mode;
+} bvc_erase_box; /* 20 bytes; mode 0 const, 1 rand, 2 pixel */
+int bvc_videomae_cls_set_erase(bvc_cls_ctx* ctx, const bvc_erase_box* tab_dev, int samples, int boxes, uint64_t seed, uint64_t offset,
+                               void* stream);
+/* forward only */
+int bvc_videomae_encoder_set_erase(bvc_encoder_ctx* ctx, const bvc_erase_box* tab_dev, int samples, int boxes, uint64_t seed,
+                                   uint64_t offset, void* stream);
+/* the f32 values the gather writes for erased elements: kind 0 the pixel noise of a whole batch [B][T][C][H][W] (W % 4 == 0), kind 1
+ * the colours [B][T][4][4] (box, channel) */
+int bvc_op_erase_noise(uint64_t seed, uint64_t offset, int kind, int B, int T, int C, int H, int W, float* out_dev, void* stream);
 /* keep bytes (1 = kept, 0 = dropped) of the M x N element mask of one branch, row-major, on the device and on the host */
 int bvc_op_dropout_mask(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_dev, void* stream);
 int bvc_dropout_mask_host(uint64_t seed, uint64_t offset, int layer, int branch, int M, int N, float p, uint8_t* out_host);
@@ -958,6 +991,11 @@ int bvc_op_gather_patches(const float* clip, const int* vis_idx, void* A_bf16, i
  * Out-of-range entries are clamped (no status word at this level). */
 int bvc_op_gather_patches_mix(const void* clip, const bvc_pixel_format* fmt, const int* idx, void* A_bf16, const bvc_clip_mix* mix,
                               int B, int n, int T, int C, int H, int W, int ts, int ps, void* stream);
+/* the same through a bvc_erase_box table of [B][boxes] entries as well (erase each clip, then mix the batch); mix NULL = no mix, boxes
+ * in [1, BVC_ERASE_MAX_BOXES], C <= 4.  Out-of-range entries are clamped (no status word at this level). */
+int bvc_op_gather_patches_aug(const void* clip, const bvc_pixel_format* fmt, const int* idx, void* A_bf16, const bvc_clip_mix* mix,
+                              const bvc_erase_box* erase, int boxes, uint64_t seed, uint64_t offset, int B, int n, int T, int C, int H,
+                              int W, int ts, int ps, void* stream);
 /* per-patch-normalised pixel targets of the masked tokens (HF:588-661) */
 int bvc_op_pixel_labels(const float* clip, const int* msk_idx, float* labels, int B, int nmask, int T, int C, int H, int W,
                         int ts, int ps, int norm_pix, void* stream);

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "attnpool.h"
 #include "context.h"
 #include "optim_layerwise.h"
 
@@ -392,6 +393,18 @@ int bvc_op_token_mean(const float* x, int batch, int ntok, int dim, float* out, 
 int bvc_op_token_mean_bwd(const float* dmean, int batch, int ntok, int dim, float* dx, void* stream) {
     BVC_REQUIRE(dmean && dx && batch > 0 && ntok > 0 && dim > 0, "op_token_mean_bwd: bad argument");
     return launch_token_mean_bwd(dmean, batch, ntok, dim, dx, (hipStream_t)stream);
+}
+
+// ============================================================================ attentive pooling (attnpool.hip)
+int bvc_op_attn_pool_splits(int B, int N, int D, int R) { return attn_pool_splits(B, N, D, R); }
+int64_t bvc_op_attn_pool_workspace(int B, int N, int D, int R, int splits) { return attn_pool_workspace(B, N, D, R, splits); }
+int bvc_op_attn_pool_fwd(const float* x, int64_t ldx, const float* u, int B, int N, int D, int R, float eps, int splits, float* pooled,
+                         float* lse, void* workspace, void* stream) {
+    return launch_attn_pool_fwd(x, ldx, u, B, N, D, R, eps, splits, pooled, lse, workspace, (hipStream_t)stream);
+}
+int bvc_op_attn_pool_bwd(const float* x, int64_t ldx, const float* u, const float* pooled, const float* lse, const float* dpooled, int B,
+                         int N, int D, int R, float eps, int splits, float* du, float* dx, int64_t lddx, void* workspace, void* stream) {
+    return launch_attn_pool_bwd(x, ldx, u, pooled, lse, dpooled, B, N, D, R, eps, splits, du, dx, lddx, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -798,6 +798,31 @@ int bvc_op_linear_pass_tile_rows(int D);
 int bvc_op_linear_pass(const float* x, int64_t ldx, const int* labels, const float* mean, const float* inv_std, const float* W,
                        const float* V, int n, int D, int K, int class0, int mode, float C, float* out_G, float* out_loss, int* out_pred,
                        float* out_dec, void* workspace, void* stream);
+/* Attentive pooling (csrc/attnpool.hip): the part of an attentive probe's cross-attention block that touches the tokens.  For each
+ * of the B clips, R <= 16 query rows u f32 [R][D] softmax-pool the STANDARDISED token rows of x f32 [B][N] rows of D columns (row
+ * stride ldx elements):  xh_j = (x_j - mean_j) / sqrt(var_j + eps) (biased variance, as nn.LayerNorm without its affine),
+ * s_jr = xh_j . u_r,  p_jr = softmax over the N tokens,  pooled f32 [B][R][D] = sum_j p_jr xh_j,  lse f32 [B][R] = log sum_j
+ * exp(s_jr) (natural log).  LayerNorm's weight and bias, the K / V projections and the query fold into u and into [B][D] algebra
+ * (bvc/attentive.py); no K or V array exists.  All arithmetic is f32 (v_mfma_f32_16x16x4_f32 products).
+ *   splits      0 = chosen by the library from the shape (bvc_op_attn_pool_splits), else the tokens of every clip are cut into that
+ *               many contiguous ranges [s N / splits, (s + 1) N / splits) (up to 256; empty ranges are legal) run by workgroups of
+ *               their own and merged in ascending order.  Different split counts agree to rounding, not bit for bit.
+ *   workspace   bvc_op_attn_pool_workspace(B, N, D, R, splits) bytes, 16-byte aligned (-1 for a refused shape); serves the forward
+ *               and the backward of that shape; its contents on entry do not matter.
+ * Backward, for dpooled f32 [B][R][D] (pooled and lse as the forward wrote them): du f32 [R][D] = the gradient of u summed over
+ * the clips (written, not accumulated), and, unless dx is NULL, dx f32 [B][N] rows of D columns (row stride lddx) = the gradient
+ * of x through the scores, the pooled rows and the standardisation.  With dx NULL nothing of it is computed or stored.
+ * Read: the D columns of the rows (never the ldx - D padding).  Written: the named outputs and the workspace, nothing else.  No
+ * atomics and no host synchronisation or allocation: the same bits on every run, a clip's pooled / lse / dx do not depend on the
+ * other clips, and the calls may be captured in a graph.  BVC_ERR_INVALID (bvc_last_error) and nothing launched unless
+ * B, N >= 1, D % 64 == 0 with 64 <= D <= 2048, 1 <= R <= 16, 0 <= splits <= 256, ldx (lddx) >= D and a multiple of 4, and
+ * x, u, dpooled, dx and the workspace 16-byte aligned. */
+int bvc_op_attn_pool_splits(int B, int N, int D, int R);
+int64_t bvc_op_attn_pool_workspace(int B, int N, int D, int R, int splits);
+int bvc_op_attn_pool_fwd(const float* x, int64_t ldx, const float* u, int B, int N, int D, int R, float eps, int splits, float* pooled,
+                         float* lse, void* workspace, void* stream);
+int bvc_op_attn_pool_bwd(const float* x, int64_t ldx, const float* u, const float* pooled, const float* lse, const float* dpooled, int B,
+                         int N, int D, int R, float eps, int splits, float* du, float* dx, int64_t lddx, void* workspace, void* stream);
 /* nn.LayerNorm forward/backward (HF:336-337,484); rows may be strided by (rin, rout, roff), rin<=0 = dense */
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y_bf16,
                          float* mean, float* rstd, int M, int D, float eps, void* stream);

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "attnpool.h"
+#include "ntxent.h"
 #include "context.h"
 #include "optim_layerwise.h"
 
@@ -405,6 +406,22 @@ int bvc_op_attn_pool_fwd(const float* x, int64_t ldx, const float* u, int B, int
 int bvc_op_attn_pool_bwd(const float* x, int64_t ldx, const float* u, const float* pooled, const float* lse, const float* dpooled, int B,
                          int N, int D, int R, float eps, int splits, float* du, float* dx, int64_t lddx, void* workspace, void* stream) {
     return launch_attn_pool_bwd(x, ldx, u, pooled, lse, dpooled, B, N, D, R, eps, splits, du, dx, lddx, workspace, (hipStream_t)stream);
+}
+
+// ============================================================================ NT-Xent / SupCon loss (ntxent.hip)
+int bvc_op_ntxent_splits(int n, int p) { return ntxent_splits(n, p); }
+int bvc_op_ntxent_block_rows(int n, int p) { return ntxent_block_rows(n, p); }
+int64_t bvc_op_ntxent_workspace(int n, int p, int key_splits, int block_rows) { return ntxent_workspace(n, p, key_splits, block_rows); }
+int bvc_op_ntxent_fwd(const float* f, int64_t ldf, const int32_t* groups, int views, int n, int p, float temperature, float eps,
+                      int key_splits, float* row_loss, float* lse, int32_t* npos, float* stats2, void* workspace, void* stream) {
+    return launch_ntxent_fwd(f, ldf, groups, views, n, p, temperature, eps, key_splits, row_loss, lse, npos, stats2, workspace,
+                             (hipStream_t)stream);
+}
+int bvc_op_ntxent_bwd(const float* f, int64_t ldf, const int32_t* groups, int views, int n, int p, float temperature, float eps,
+                      const float* lse, const int32_t* npos, const float* row_weight, int key_splits, int block_rows, float* df,
+                      int64_t lddf, void* workspace, void* stream) {
+    return launch_ntxent_bwd(f, ldf, groups, views, n, p, temperature, eps, lse, npos, row_weight, key_splits, block_rows, df, lddf,
+                             workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

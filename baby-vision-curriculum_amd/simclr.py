@@ -191,6 +191,132 @@ class SimCLRViT(nn.Module):
         return self.fc(jepa.token_mean(tokens))
 
 
+# ---------------------------------------------------------------------------------------------- NT-Xent / SupCon (csrc/ntxent.hip)
+NT_XENT_EPS = 1e-8
+
+
+def view_groups(n, views, order="view", device=None):
+    """int32 group ids [n] of `views` views per sample: order "view" = i mod (n / views), the view-major rows ClipAugment(views=...)
+    returns (all first views, then all second views, ..); "sample" = i // views, the reference loader's (B, T, ...) -> (B T, ...)."""
+    n, views = int(n), int(views)
+    if views < 1 or n < 0 or n % views:
+        raise ValueError(f"view_groups: views {views} does not divide n {n}")
+    if order not in ("view", "sample"):
+        raise ValueError(f"view_groups: order {order!r} is neither 'view' nor 'sample'")
+    i = torch.arange(n, dtype=torch.int32, device=device)
+    return i % (n // views) if order == "view" else torch.div(i, views, rounding_mode="floor")
+
+
+def global_groups(rank, world, n_local, views, order="view", device=None):
+    """The ids a rank's n_local rows carry in the batch gathered from `world` ranks: rank * (n_local / views) + the local id."""
+    rank, world = int(rank), int(world)
+    if not 0 <= rank < world:
+        raise ValueError(f"global_groups: rank {rank} outside 0 .. {world - 1}")
+    return view_groups(n_local, views, order, device) + rank * (int(n_local) // int(views))
+
+
+def _ntxent_workspace(n, p, device):
+    L = _lib.lib()
+    nbytes = L.bvc_op_ntxent_workspace(n, p, 0, 0)
+    if nbytes < 0:
+        raise _lib.BvcError(f"bvc_op_ntxent_workspace: {L.bvc_last_error().decode()}")
+    return torch.empty((nbytes + 15) // 16 * 4, dtype=torch.float32, device=device)
+
+
+class _NTXent(torch.autograd.Function):
+    """(row_loss [n], stats {loss, m}) of bvc_op_ntxent_fwd; the backward takes the upstream gradient of either as row weights."""
+
+    @staticmethod
+    def forward(ctx, feats, groups, views, temperature):
+        f = feats.detach().float()
+        if f.stride(1) != 1 or f.stride(0) < f.shape[1]:
+            f = f.contiguous()
+        n, p = f.shape
+        ws = _ntxent_workspace(n, p, f.device)
+        row_loss = torch.empty(n, dtype=torch.float32, device=f.device)
+        lse = torch.empty(n, dtype=torch.float32, device=f.device)
+        npos = torch.empty(n, dtype=torch.int32, device=f.device)
+        stats = torch.empty(2, dtype=torch.float32, device=f.device)
+        with torch.cuda.device(f.device):
+            _lib.check(_lib.lib().bvc_op_ntxent_fwd(f.data_ptr(), f.stride(0), None if groups is None else groups.data_ptr(), views, n, p,
+                                                    temperature, NT_XENT_EPS, 0, row_loss.data_ptr(), lse.data_ptr(), npos.data_ptr(),
+                                                    stats.data_ptr(), ws.data_ptr(), _lib.current_stream_ptr()), "bvc_op_ntxent_fwd")
+        ctx.save_for_backward(f, lse, npos, stats, *(() if groups is None else (groups,)))
+        ctx.views, ctx.temperature, ctx.dtype = views, temperature, feats.dtype
+        return row_loss, stats[0]
+
+    @staticmethod
+    def backward(ctx, drow, dloss):
+        f, lse, npos, stats, *rest = ctx.saved_tensors
+        groups = rest[0] if rest else None
+        n, p = f.shape
+        # w_i = d / d l_i: the rows' own upstream gradients plus the mean's gout / max(1, m) (rows without positives are dropped
+        # by the kernel); device arithmetic only, no synchronisation
+        w = drow.detach().float() + dloss.detach().float() / stats[1].clamp(min=1.0)
+        w = w.contiguous()
+        ws = _ntxent_workspace(n, p, f.device)
+        df = torch.empty((n, p), dtype=torch.float32, device=f.device)
+        with torch.cuda.device(f.device):
+            _lib.check(_lib.lib().bvc_op_ntxent_bwd(f.data_ptr(), f.stride(0), None if groups is None else groups.data_ptr(), ctx.views, n, p,
+                                                    ctx.temperature, NT_XENT_EPS, lse.data_ptr(), npos.data_ptr(), w.data_ptr(), 0, 0,
+                                                    df.data_ptr(), p, ws.data_ptr(), _lib.current_stream_ptr()), "bvc_op_ntxent_bwd")
+        return df.to(ctx.dtype), None, None, None
+
+
+def nt_xent_loss(feats, temperature=0.1, groups=None, views=2, reduction="mean"):
+    """NT-Xent / SupCon loss of feature rows (n, p) with one group id per row (include/bvc.h, bvc_op_ntxent_fwd):
+    l_i = log sum_{k != i} exp(s_ik) - mean_{j in P(i)} s_ij over the cosine scores s = zn zn^T / temperature, P(i) the other rows
+    of i's group; "mean" averages over the rows that have positives, "none" returns l [n].
+
+    groups=None: `views` view-major views (rows [0, n / views) are the first views: what ClipAugment(views=...) returns), which for
+    views=2 is SimCLR's NT-Xent.  groups = int tensor (n,) on the features' device: any grouping, e.g. class labels (SupCon's L_out)
+    or view_groups(n, views, "sample"); negative ids belong to no group.  Computed in f32 whatever the features' dtype; the gradient
+    comes back in that dtype.  Nothing here synchronises the stream."""
+    if not (isinstance(feats, torch.Tensor) and feats.dim() == 2 and feats.is_floating_point()):
+        raise ValueError("nt_xent_loss: feats must be a floating-point tensor (n, p)")
+    if not feats.is_cuda:
+        raise _lib.BvcError("nt_xent_loss runs on a GPU only (libbvc_hip.so has no CPU path)")
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"nt_xent_loss: reduction {reduction!r} is neither 'mean' nor 'none'")
+    n = feats.shape[0]
+    views = int(views)
+    if groups is None:
+        if views < 1 or n % views:
+            raise ValueError(f"nt_xent_loss: views {views} does not divide n {n}")
+    else:
+        if not (isinstance(groups, torch.Tensor) and groups.shape == (n,) and groups.dtype in (torch.int32, torch.int64)):
+            raise ValueError("nt_xent_loss: groups must be an int32 or int64 tensor (n,)")
+        if not groups.is_cuda:       # a host tensor can be checked without a synchronisation; a device tensor is taken as it is
+            if groups.numel() and (int(groups.max()) > 2 ** 31 - 1 or int(groups.min()) < -2 ** 31):
+                raise ValueError("nt_xent_loss: group ids must fit int32")
+            groups = groups.to(feats.device)
+        elif groups.device != feats.device:
+            raise ValueError("nt_xent_loss: groups must be on the features' device")
+        groups = groups.to(torch.int32).contiguous()
+    row_loss, loss = _NTXent.apply(feats, groups, views, float(temperature))
+    return loss if reduction == "mean" else row_loss
+
+
+def global_nt_xent_loss(feats_local, temperature=0.1, groups_local=None, views=2):
+    """nt_xent_loss over the rows of EVERY rank (AllGather: forward all_gather + cat, backward all_reduce then own slice); every rank
+    computes the whole loss, as global_info_nce_loss does.  groups_local=None: each rank holds `views` view-major views of its own
+    samples and the ids are global_groups(rank, world, n_local, views); else the ranks' ids are gathered as they are (labels: equal
+    ids on different ranks are the same class)."""
+    from .distributed import AllGather, world
+    n_local = feats_local.shape[0]
+    _, nranks = world()
+    if groups_local is None:
+        groups = torch.cat([global_groups(r, nranks, n_local, views, "view", feats_local.device) for r in range(nranks)])
+    elif nranks > 1:
+        import torch.distributed as dist
+        g = groups_local.to(feats_local.device).contiguous()
+        groups = g.new_empty(nranks * n_local)
+        dist.all_gather_into_tensor(groups, g)
+    else:
+        groups = groups_local
+    return nt_xent_loss(AllGather.apply(feats_local), temperature, groups=groups)
+
+
 def global_info_nce_loss(temperature, masks, feats_local):
     """info_nce_loss over the rows of EVERY rank: AllGather (pretraining/predictive/distributed.py:49-76: forward all_gather + cat,
     backward all_reduce then own slice) in front of the reference's loss.  `masks` are make_masks(global_batch)."""

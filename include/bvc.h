@@ -823,6 +823,39 @@ int bvc_op_attn_pool_fwd(const float* x, int64_t ldx, const float* u, int B, int
                          float* lse, void* workspace, void* stream);
 int bvc_op_attn_pool_bwd(const float* x, int64_t ldx, const float* u, const float* pooled, const float* lse, const float* dpooled, int B,
                          int N, int D, int R, float eps, int splits, float* du, float* dx, int64_t lddx, void* workspace, void* stream);
+/* NT-Xent / SupCon loss (csrc/ntxent.hip) over n feature rows f f32 [n] rows of p columns (row stride ldf elements) with one
+ * integer group id per row: groups int32 [n], or NULL for g_i = i mod (n / views), the view-major layout of `views` views.  A
+ * negative id belongs to no group.  With zn_i = f_i / max(|f_i|, eps), s_ij = zn_i . zn_j / temperature,
+ * P(i) = { j != i : g_j == g_i >= 0 } and c_i = |P(i)|:
+ *   lse f32 [n]       D_i = log sum_{k != i} exp(s_ik) over ALL other rows (natural log; -inf for n = 1)
+ *   npos int32 [n]    c_i
+ *   row_loss f32 [n]  l_i = D_i - (1 / c_i) sum_{j in P(i)} s_ij, 0 where c_i = 0
+ *   stats2 f32 [2]    { sum_i l_i / max(1, m), m = #{ i : c_i > 0 } }
+ * Two views per sample give SimCLR's NT-Xent, label ids the supervised contrastive loss L_out.  Rows are excluded by index, never
+ * by value.  Backward, for per-row upstream weights row_weight f32 [n] (ignored where c_i = 0; for the mean: gout / max(1, m)):
+ * df f32 [n] rows of p columns (row stride lddf) = sum_i row_weight_i d l_i / d f, through the normalisation (where |f_i| <= eps
+ * the clamp is active and zn_i = f_i / eps).  lse and npos as the forward wrote them; nothing else survives from the forward.
+ * All arithmetic is f32 (v_mfma_f32_32x32x2_f32 products); no [n][n] array is stored by the forward, the backward holds a block of
+ * block_rows x n f32 in the workspace.
+ *   key_splits  0 = chosen by the library (bvc_op_ntxent_splits), else the key tiles (128 rows) of every query tile are cut into that
+ *               many contiguous ranges (up to 256; empty ranges are legal), merged in ascending order.  Different split counts agree
+ *               to rounding, not bit for bit.
+ *   block_rows  0 = chosen by the library (bvc_op_ntxent_block_rows: the most whole 128-row tiles whose block stays under 256 MiB),
+ *               else rounded up to a multiple of 128.
+ *   workspace   bvc_op_ntxent_workspace(n, p, key_splits, block_rows) bytes, 16-byte aligned (-1 for a refused shape); serves the
+ *               forward and the backward; its contents on entry do not matter.
+ * Read: the p columns of the rows (never the ldf - p padding).  Written: the named outputs and the workspace, nothing else.  No
+ * atomics and no host synchronisation or allocation: the same bits on every run, and the calls may be captured in a graph.
+ * BVC_ERR_INVALID (bvc_last_error) and nothing launched unless 1 <= n <= 32768, 1 <= p <= 8192, temperature and eps positive and
+ * finite, ldf (lddf) >= p, 0 <= key_splits <= 256, block_rows >= 0, and, with groups NULL, views >= 1 dividing n. */
+int bvc_op_ntxent_splits(int n, int p);
+int bvc_op_ntxent_block_rows(int n, int p);
+int64_t bvc_op_ntxent_workspace(int n, int p, int key_splits, int block_rows);
+int bvc_op_ntxent_fwd(const float* f, int64_t ldf, const int32_t* groups, int views, int n, int p, float temperature, float eps,
+                      int key_splits, float* row_loss, float* lse, int32_t* npos, float* stats2, void* workspace, void* stream);
+int bvc_op_ntxent_bwd(const float* f, int64_t ldf, const int32_t* groups, int views, int n, int p, float temperature, float eps,
+                      const float* lse, const int32_t* npos, const float* row_weight, int key_splits, int block_rows, float* df,
+                      int64_t lddf, void* workspace, void* stream);
 /* nn.LayerNorm forward/backward (HF:336-337,484); rows may be strided by (rin, rout, roff), rin<=0 = dense */
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y_bf16,
                          float* mean, float* rstd, int M, int D, float eps, void* stream);

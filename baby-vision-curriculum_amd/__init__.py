@@ -26,7 +26,7 @@ from . import augment  # noqa: F401
 from .augment import ClipAugment, ClipTransform  # noqa: F401
 from .augment import (FRAME_RANDAUG, RANDAUG_OPS, RandAugment, empty_randaug_table, parse_randaug, rand_augment,  # noqa: F401
                       rand_augment_host, sample_randaug_params)
-from . import simclr, distributed, jepa, jepa_mask, checkpoint, launch, comm, probe, retrieval, separability, attentive  # noqa: F401
+from . import simclr, distributed, jepa, jepa_mask, checkpoint, launch, comm, probe, retrieval, separability, attentive, xcorr  # noqa: F401
 from .attentive import AttentiveClassifier, AttentivePooler, attentive_pool  # noqa: F401
 from . import input as input_pipeline  # noqa: F401
 from .input import ClipUploadRing  # noqa: F401

@@ -260,6 +260,13 @@ SYMBOLS = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_ntxent_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                   c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "bvc_op_xcorr_block_cols": (c_int, [c_int, c_int, c_int]),
+    "bvc_op_xcorr_workspace": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "bvc_op_xcorr_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_xcorr_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p,
+                                 c_int64, c_void_p, c_void_p]),
     "bvc_op_colstats": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "bvc_op_linear_pass_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
     "bvc_op_linear_pass_splits": (c_int, [c_int, c_int, c_int]),

@@ -6,6 +6,7 @@
 
 #include "attnpool.h"
 #include "ntxent.h"
+#include "xcorr.h"
 #include "context.h"
 #include "optim_layerwise.h"
 
@@ -408,6 +409,23 @@ int bvc_op_attn_pool_bwd(const float* x, int64_t ldx, const float* u, const floa
     return launch_attn_pool_bwd(x, ldx, u, pooled, lse, dpooled, B, N, D, R, eps, splits, du, dx, lddx, workspace, (hipStream_t)stream);
 }
 
+// ============================================================================ feature-correlation losses (xcorr.hip)
+int bvc_op_xcorr_block_cols(int n, int p, int q) { return xcorr_block_cols(n, p, q); }
+int64_t bvc_op_xcorr_workspace(int n, int p, int q, int alias, int block_cols, int backward) {
+    return xcorr_workspace(n, p, q, alias, block_cols, backward);
+}
+int bvc_op_xcorr_fwd(const float* x, int64_t ldx, const float* y, int64_t ldy, int n, int p, int q, int norm, int ddof, float eps, float scale,
+                     float diag_target, float* mean_x, float* var_x, float* mean_y, float* var_y, float* stats2, void* workspace, void* stream) {
+    return launch_xcorr_fwd(x, ldx, y, ldy, n, p, q, norm, ddof, eps, scale, diag_target, mean_x, var_x, mean_y, var_y, stats2, workspace,
+                            (hipStream_t)stream);
+}
+int bvc_op_xcorr_bwd(const float* x, int64_t ldx, const float* y, int64_t ldy, int n, int p, int q, int norm, int ddof, float eps, float scale,
+                     float diag_target, const float* mean_x, const float* var_x, const float* mean_y, const float* var_y, const float* w,
+                     const float* dvar_x, const float* dvar_y, int block_cols, float* dx, int64_t lddx, float* dy, int64_t lddy,
+                     void* workspace, void* stream) {
+    return launch_xcorr_bwd(x, ldx, y, ldy, n, p, q, norm, ddof, eps, scale, diag_target, mean_x, var_x, mean_y, var_y, w, dvar_x, dvar_y,
+                            block_cols, dx, lddx, dy, lddy, workspace, (hipStream_t)stream);
+}
 // ============================================================================ NT-Xent / SupCon loss (ntxent.hip)
 int bvc_op_ntxent_splits(int n, int p) { return ntxent_splits(n, p); }
 int bvc_op_ntxent_block_rows(int n, int p) { return ntxent_block_rows(n, p); }

@@ -317,6 +317,51 @@ def global_nt_xent_loss(feats_local, temperature=0.1, groups_local=None, views=2
     return nt_xent_loss(AllGather.apply(feats_local), temperature, groups=groups)
 
 
+# ---------------------------------------------------------------------------------------------- Barlow Twins / VICReg (csrc/xcorr.hip)
+def barlow_twins_loss(z1, z2, lambd=5e-3, eps=1e-5):
+    """Barlow Twins (Zbontar et al. 2021) of two views' features (n, p): with c = bn(z1)^T bn(z2) / n (BatchNorm1d without affine:
+    biased variance, eps), sum_i (c_ii - 1)^2 + lambd sum_{i != j} c_ij^2.  The p x p matrix is never stored
+    (bvc.xcorr.cross_correlation); computed in f32, gradients in the inputs' dtypes."""
+    from .xcorr import cross_correlation
+    if z1.shape != z2.shape:
+        raise ValueError("barlow_twins_loss: the two views must have the same shape")
+    on, off, _, _ = cross_correlation(z1, z2, norm=1, ddof=0, eps=eps, scale=1.0 / z1.shape[0], diag_target=1.0)
+    return on + lambd * off
+
+
+def vicreg_loss(x, y, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, eps=1e-4):
+    """VICReg (Bardes et al. 2022) of two views' features (n, p): sim_coeff mse(x, y) + std_coeff (v(x) + v(y)) + cov_coeff (c(x) + c(y)),
+    v = mean(relu(1 - sqrt(var + eps))) / 2 with the unbiased column variance, c = the sum of the squared off-diagonal entries of
+    the covariance matrix / p.  Variances and covariance sums come from two auto-covariance calls of bvc.xcorr.cross_correlation;
+    the variance term is torch arithmetic on the returned variances, so its gradient reaches the op as dvar."""
+    import torch.nn.functional as F
+    from .xcorr import cross_correlation
+    if x.shape != y.shape:
+        raise ValueError("vicreg_loss: the two views must have the same shape")
+    n, p = x.shape
+    if n < 2:
+        raise ValueError("vicreg_loss: the unbiased variance needs at least two rows")
+    _, off_x, var_x, _ = cross_correlation(x, None, norm=0, ddof=1, scale=1.0 / (n - 1), diag_target=0.0)
+    _, off_y, var_y, _ = cross_correlation(y, None, norm=0, ddof=1, scale=1.0 / (n - 1), diag_target=0.0)
+    sim = F.mse_loss(x.float(), y.float())
+    std = torch.relu(1.0 - torch.sqrt(var_x + eps)).mean() / 2 + torch.relu(1.0 - torch.sqrt(var_y + eps)).mean() / 2
+    cov = off_x / p + off_y / p
+    return sim_coeff * sim + std_coeff * std + cov_coeff * cov
+
+
+def global_barlow_twins_loss(z1_local, z2_local, lambd=5e-3, eps=1e-5):
+    """barlow_twins_loss over the rows of EVERY rank (AllGather in front of each view, as global_nt_xent_loss: every rank computes the
+    whole loss, the backward all-reduces and takes the rank's own slice)."""
+    from .distributed import AllGather
+    return barlow_twins_loss(AllGather.apply(z1_local), AllGather.apply(z2_local), lambd, eps)
+
+
+def global_vicreg_loss(x_local, y_local, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, eps=1e-4):
+    """vicreg_loss over the rows of EVERY rank (AllGather in front of each view)."""
+    from .distributed import AllGather
+    return vicreg_loss(AllGather.apply(x_local), AllGather.apply(y_local), sim_coeff, std_coeff, cov_coeff, eps)
+
+
 def global_info_nce_loss(temperature, masks, feats_local):
     """info_nce_loss over the rows of EVERY rank: AllGather (pretraining/predictive/distributed.py:49-76: forward all_gather + cat,
     backward all_reduce then own slice) in front of the reference's loss.  `masks` are make_masks(global_batch)."""

@@ -856,6 +856,50 @@ int bvc_op_ntxent_fwd(const float* f, int64_t ldf, const int32_t* groups, int vi
 int bvc_op_ntxent_bwd(const float* f, int64_t ldf, const int32_t* groups, int views, int n, int p, float temperature, float eps,
                       const float* lse, const int32_t* npos, const float* row_weight, int key_splits, int block_rows, float* df,
                       int64_t lddf, void* workspace, void* stream);
+/* Feature cross-correlation with a reduced epilogue (csrc/xcorr.hip): Barlow Twins, VICReg's covariance term and linear CKA.
+ * x f32 [n] rows of p columns (row stride ldx elements), y f32 [n] rows of q columns (row stride ldy); y may be the SAME POINTER as
+ * x with q == p and ldy == ldx, the auto-covariance ("alias") case.  Per column j of x (likewise of y):
+ *   mu_j = mean_i x_ij,  var_j = sum_i (x_ij - mu_j)^2 / (n - ddof),  r_j = 1 (norm 0: centre only) or 1 / sqrt(var_j + eps)
+ *   (norm 1: standardise),  xh_ij = (x_ij - mu_j) r_j.  A constant column is no special case: var 0, xh 0, r = 1 / sqrt(eps).
+ * With C = scale xh^T yh [p][q], which is never stored by the forward, and t = diag_target:
+ *   mean_x, var_x f32 [p]; mean_y, var_y f32 [q] (not written, and may be NULL, in the alias case)
+ *   stats2 f32 [2]   { on = sum_i (C_ii - t)^2 over i < min(p, q),  off = sum_{i != j} C_ij^2 }
+ * Barlow Twins: norm 1, ddof 0, eps 1e-5, scale 1 / n, t 1.  VICReg covariance: alias, norm 0, ddof 1, scale 1 / (n - 1), w_on 0.
+ * Linear CKA: norm 0, scale 1, t 0, so that on + off = |xc^T yc|_F^2.
+ * Backward, for w f32 [2] ON THE DEVICE = { d / d on, d / d off } and the optional upstream gradients dvar_x f32 [p], dvar_y f32 [q]
+ * of the returned variances (NULL = zero): G_ii = 2 w_on (C_ii - t), G_ij = 2 w_off C_ij, dxh = scale yh G^T, dyh = scale xh G
+ * (alias: dxh = scale xh (G + G^T)), a_j = dvar_j - (norm ? r_j^2 / 2 sum_i dxh_ij xh_ij : 0),
+ * dx_ij = r_j (dxh_ij - mean_i' dxh_i'j) + 2 (x_ij - mu_j) a_j / (n - ddof).  dx f32 [n] rows of p columns (row stride lddx), dy f32
+ * [n] rows of q columns (row stride lddy; NULL in the alias case, where dx is the whole gradient).  mean_* and var_* as the forward
+ * wrote them; nothing else survives from the forward.
+ * All arithmetic is f32 (v_mfma_f32_32x32x2_f32 products); every element of C is one accumulation chain over the rows in ascending
+ * order.  The column statistics, the sums of the squares and the backward's column sums are f64 sums in a fixed order with one
+ * rounding.  Diagonal membership and padding are decided by index, never by value.
+ *   block_cols  0 = chosen by the library (bvc_op_xcorr_block_cols: the most whole 128-column tiles whose G block
+ *               [block_cols][max(p, q) up to 32] f32 stays under 128 MiB), else rounded up to a multiple of 128.  The backward
+ *               holds one such block of G, and dxh [n][block_cols] f32, in the workspace.  Every blocking gives the same bits.
+ *               The cap covers G only: dxh is n x block_cols x 4 bytes (512 MiB at n = 32768 with 4096 columns); a smaller
+ *               block_cols shrinks both.
+ *   workspace   bvc_op_xcorr_workspace(n, p, q, alias, block_cols, backward) bytes, 16-byte aligned (-1 for a refused shape);
+ *               backward = 0 sizes the forward (the transposed operands and one f64 pair per tile: no [p][q] array), backward = 1
+ *               the backward of that blocking: the transposed and the row-major copies of both operands (4 x n x width x 4 bytes,
+ *               half of that in the alias case), the G block and dxh.  The largest shape (n = 32768, p = q = 8192, distinct
+ *               operands, automatic blocking) takes 4.6 GiB in the backward and 2.0 GiB in the forward.  Its contents on entry do
+ *               not matter.
+ * The explicit alias and y passed as a bit-equal copy give the same forward bits; their gradients (dx against dx + dy) agree to
+ * rounding.  Read: the p (q) columns of the rows, never the stride padding.  Written: the named outputs and the workspace, nothing
+ * else.  No atomics and no host synchronisation or allocation: the same bits on every run, and the calls may be captured in a graph.
+ * BVC_ERR_INVALID (bvc_last_error) and nothing launched unless 1 <= n <= 32768, 1 <= p, q <= 8192, norm and ddof in {0, 1},
+ * n - ddof >= 1, scale positive and finite, diag_target finite, eps positive and finite when norm == 1, every stride at least
+ * the width, no required pointer null, x and y 4-byte and the workspace 16-byte aligned, block_cols >= 0, x == y only with q == p and ldy == ldx, and dy NULL in the alias case. */
+int bvc_op_xcorr_block_cols(int n, int p, int q);
+int64_t bvc_op_xcorr_workspace(int n, int p, int q, int alias, int block_cols, int backward);
+int bvc_op_xcorr_fwd(const float* x, int64_t ldx, const float* y, int64_t ldy, int n, int p, int q, int norm, int ddof, float eps, float scale,
+                     float diag_target, float* mean_x, float* var_x, float* mean_y, float* var_y, float* stats2, void* workspace, void* stream);
+int bvc_op_xcorr_bwd(const float* x, int64_t ldx, const float* y, int64_t ldy, int n, int p, int q, int norm, int ddof, float eps, float scale,
+                     float diag_target, const float* mean_x, const float* var_x, const float* mean_y, const float* var_y, const float* w,
+                     const float* dvar_x, const float* dvar_y, int block_cols, float* dx, int64_t lddx, float* dy, int64_t lddy,
+                     void* workspace, void* stream);
 /* nn.LayerNorm forward/backward (HF:336-337,484); rows may be strided by (rin, rout, roff), rin<=0 = dense */
 int bvc_op_layernorm_fwd(const float* x, int rin, int rout, int roff, const float* gamma, const float* beta, void* y_bf16,
                          float* mean, float* rstd, int M, int D, float eps, void* stream);

@@ -152,6 +152,10 @@ __device__ __forceinline__ void glds4(__amdgpu_buffer_rsrc_t rs, uint32_t voff, 
 namespace bvc {
 void set_error(const char* fmt, ...);
 const char* last_error();
+// carving a caller's workspace: every array starts on a 256-byte boundary
+inline int64_t ws_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+template <class T>
+T* ws_at(void* ws, int64_t off) { return reinterpret_cast<T*>(static_cast<unsigned char*>(ws) + off); }
 }
 #include "../../include/bvc.h"
 #define BVC_CHECK_HIP(expr)                                                              \

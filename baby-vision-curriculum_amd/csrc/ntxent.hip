@@ -5,13 +5,11 @@
 //     G_ij = w_i (exp(s_ij - D_i) - [j in P(i)] / c_i),   E = G + G^T,   dzn = (1 / T) E zn,
 //     df_i = inv_i (dzn_i - zn_i (zn_i . dzn_i))   (dzn_i / eps where the clamp of the norm is active).
 //
-// Arithmetic: f32 throughout.  Every score is ONE accumulation chain over d on v_mfma_f32_32x32x2_f32 (retrieval.hip's chain): with
-// 1 / T = 10 ... 100 in front of the exponential, bf16 operands are three to four orders of magnitude worse ("NT-Xent").
+// Arithmetic: f32 throughout.  Every score is ONE accumulation chain over d on v_mfma_f32_32x32x2_f32: with 1 / T = 10 ... 100 in
+// front of the exponential, bf16 operands are three to four orders of magnitude worse ("NT-Xent").
 //
-// One tile loop serves the three products: nx_product is C [128][128] = A [128][K] . B [128][K]^T with both operands
-// contraction-contiguous, 256 threads = 4 waves as 2 (A halves) x 2 (B halves), a 32-float K stage through LDS (retrieval.hip's
-// stage: 36-float rows, even d then odd d, operands prefetched into registers under the MFMAs).  The B row is on the lane, the A rows
-// on the accumulator elements, so a store of one accumulator element by a wave is two runs of 32 consecutive floats.
+// The three products are f32t_product of f32_tile.h, C [128][128] = A [128][K] . B [128][K]^T over padded operands in the workspace;
+// the epilogues below take their rows (A side, on the accumulator elements) and columns (B side, on the lane) from its helpers.
 //   prologue  nx_rows_kernel (one wave per row): inv, the clamp flag, zn [nP][pP] with zero tails (nP = n up to 128, pP = p up to
 //             32), the group ids and, in the backward, the per-row vectors D, w, w / c; nx_transpose_kernel: znT [pP][nP].
 //   forward   nx_fwd_kernel, one workgroup per (128 query rows, key split): A = key tile of zn, B = the query rows of zn.  After the K
@@ -24,6 +22,7 @@
 //             nx_dfrow_kernel is the normalisation backward of each row.
 // Rows and keys are excluded by INDEX (j == i, j >= n), never by value.  No atomics: the same bits on every run.  Nothing in the
 // workspace survives a call: the backward recomputes zn from f.
+#include "f32_tile.h"
 #include "ntxent.h"
 
 #include <math.h>
@@ -31,76 +30,10 @@
 namespace bvc {
 namespace {
 
-constexpr int kNxTile = 128;
-constexpr int kNxKStep = 32;
-constexpr int kNxRow = 36;           // floats per LDS operand row
 constexpr int kNxCUs = 256;
 constexpr float kNxLog2e = 1.4426950408889634f;
 
 __device__ __forceinline__ float nx_exp(float x) { return exp2f(x * kNxLog2e); }
-
-// 16 floats of 4 rows (rows r0 + 32 m) of a 128-row x 32-float stage; the operands live in the workspace: 16-byte aligned rows,
-// K a multiple of 32, rows past the end repeat the last one (their products are never used).
-__device__ __forceinline__ void nx_load(const float* __restrict__ base, int64_t ld, int row0, int rows, int d0, int tid, f32x4 (&v)[4]) {
-    const int c = (tid & 7) * 4 + d0, r0 = tid >> 3;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int row = min(row0 + r0 + 32 * m, rows - 1);
-        v[m] = *reinterpret_cast<const f32x4*>(base + (int64_t)row * ld + c);
-    }
-}
-__device__ __forceinline__ void nx_stage(float* lds, int tid, const f32x4 (&v)[4]) {
-    const int c = tid & 7, r0 = tid >> 3;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        float* row = lds + (r0 + 32 * m) * kNxRow;
-        *reinterpret_cast<f32x2*>(row + 2 * c) = f32x2{v[m][0], v[m][2]};
-        *reinterpret_cast<f32x2*>(row + 16 + 2 * c) = f32x2{v[m][1], v[m][3]};
-    }
-}
-
-// acc[i][j][e] = sum_d A[a0 + arow][d] B[b0 + brow][d],  arow = wk 64 + 32 i + (e & 3) + 8 (e >> 2) + 4 h,  brow = wq 64 + 32 j + r
-// (wave = wk + 2 wq, lane = r + 32 h).  Ends with a barrier: the stages are free on return.
-__device__ __forceinline__ void nx_product(const float* __restrict__ A, int64_t lda, int a0, int arows, const float* __restrict__ B,
-                                           int64_t ldb, int b0, int brows, int K, float* ldsA, float* ldsB, int tid, f32x16 (&acc)[2][2]) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    const int ksteps = K / kNxKStep;
-    f32x4 va[4], vb[4];
-    nx_load(A, lda, a0, arows, 0, tid, va);
-    nx_load(B, ldb, b0, brows, 0, tid, vb);
-    for (int s = 0; s < ksteps; ++s) {
-        nx_stage(ldsA, tid, va);
-        nx_stage(ldsB, tid, vb);
-        __syncthreads();
-        if (s + 1 < ksteps) {
-            nx_load(A, lda, a0, arows, (s + 1) * kNxKStep, tid, va);
-            nx_load(B, ldb, b0, brows, (s + 1) * kNxKStep, tid, vb);
-        }
-        f32x4 fa[2][4], fb[2][4];      // element e of piece m: d = 2 (4 m + e) + h of the step
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                fa[b][m] = *reinterpret_cast<const f32x4*>(ldsA + (wk * 64 + 32 * b + r) * kNxRow + 16 * h + 4 * m);
-                fb[b][m] = *reinterpret_cast<const f32x4*>(ldsB + (wq * 64 + 32 * b + r) * kNxRow + 16 * h + 4 * m);
-            }
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk >> 2][kk & 3], fb[j][kk >> 2][kk & 3], acc[i][j], 0, 0, 0);
-        __syncthreads();
-    }
-}
 
 // ---------------------------------------------------------------- prologue
 struct NxRowArgs {
@@ -168,34 +101,34 @@ struct NxFwdArgs {
 };
 
 __global__ __launch_bounds__(256) void nx_fwd_kernel(NxFwdArgs a) {
-    __shared__ __attribute__((aligned(16))) float ldsA[kNxTile * kNxRow];
-    __shared__ __attribute__((aligned(16))) float ldsB[kNxTile * kNxRow];
-    __shared__ int32_t kg[2][kNxTile];
-    __shared__ float red[4][kNxTile][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-    const int tiles = a.nP / kNxTile;
+    __shared__ __attribute__((aligned(16))) float ldsA[kF32Tile * kF32Row];
+    __shared__ __attribute__((aligned(16))) float ldsB[kF32Tile * kF32Row];
+    __shared__ int32_t kg[2][kF32Tile];
+    __shared__ float red[4][kF32Tile][4];
+    const int tid = threadIdx.x;
+    const F32TileLane L = f32t_lane(tid);
+    const int tiles = a.nP / kF32Tile;
     const int qt = blockIdx.x % tiles, split = blockIdx.x / tiles;
-    const int q0 = qt * kNxTile;
+    const int q0 = qt * kF32Tile;
     const int t_begin = (int)((int64_t)tiles * split / a.splits), t_end = (int)((int64_t)tiles * (split + 1) / a.splits);
 
     int ql[2], qi[2]; int32_t gq[2];
     float m[2], l[2], ps[2], pc[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        ql[j] = wq * 64 + 32 * j + r;
+        ql[j] = F32T_BROW(L, 0, j);
         qi[j] = q0 + ql[j];
         gq[j] = a.gid[qi[j]];
         m[j] = -INFINITY; l[j] = 0.f; ps[j] = 0.f; pc[j] = 0.f;
     }
 
     for (int t = t_begin; t < t_end; ++t) {
-        const int key0 = t * kNxTile;
+        const int key0 = t * kF32Tile;
         // read after the K loop's barriers; two images by parity: the next tile's write cannot meet this tile's readers
         int32_t* const kgt = kg[(t - t_begin) & 1];
-        if (tid < kNxTile) kgt[tid] = a.gid[key0 + tid];
+        if (tid < kF32Tile) kgt[tid] = a.gid[key0 + tid];
         f32x16 acc[2][2];
-        nx_product(a.zn, a.pP, key0, a.nP, a.zn, a.pP, q0, a.nP, a.pP, ldsA, ldsB, tid, acc);
+        f32t_product(a.zn, a.pP, key0, a.nP, a.zn, a.pP, q0, a.nP, a.pP, ldsA, ldsB, tid, acc);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             float mt = -INFINITY;
@@ -203,7 +136,7 @@ __global__ __launch_bounds__(256) void nx_fwd_kernel(NxFwdArgs a) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int ki = key0 + wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    const int ki = F32T_AROW(L, key0, i, e);
                     const float s = acc[i][j][e] * a.invT;
                     acc[i][j][e] = s;
                     if (ki < a.n && ki != qi[j]) mt = fmaxf(mt, s);
@@ -215,7 +148,7 @@ __global__ __launch_bounds__(256) void nx_fwd_kernel(NxFwdArgs a) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int kl = wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    const int kl = F32T_AROW(L, 0, i, e);
                     const int ki = key0 + kl;
                     const bool ok = ki < a.n && ki != qi[j];
                     const float s = acc[i][j][e];
@@ -232,11 +165,11 @@ __global__ __launch_bounds__(256) void nx_fwd_kernel(NxFwdArgs a) {
     // the four lanes of a row (wk, h), merged in that order
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        float* o = red[wk * 2 + h][ql[j]];
+        float* o = red[L.wk * 2 + L.h][ql[j]];
         o[0] = m[j]; o[1] = l[j]; o[2] = ps[j]; o[3] = pc[j];
     }
     __syncthreads();
-    if (tid < kNxTile) {
+    if (tid < kF32Tile) {
         float M = -INFINITY;
 #pragma unroll
         for (int s = 0; s < 4; ++s) M = fmaxf(M, red[s][tid][0]);
@@ -313,31 +246,31 @@ struct NxBwdArgs {
 
 // E [i - r0][j] = w_i exp(s_ij - D_i) + w_j exp(s_ij - D_j) - [same group] (w_i / c_i + w_j / c_j);  0 for j == i and beyond n
 __global__ __launch_bounds__(256) void nx_e_kernel(NxBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) float ldsA[kNxTile * kNxRow];
-    __shared__ __attribute__((aligned(16))) float ldsB[kNxTile * kNxRow];
-    __shared__ float rD[kNxTile], rW[kNxTile], rC[kNxTile];
-    __shared__ int32_t rG[kNxTile];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-    const int rtiles = a.rb / kNxTile;
+    __shared__ __attribute__((aligned(16))) float ldsA[kF32Tile * kF32Row];
+    __shared__ __attribute__((aligned(16))) float ldsB[kF32Tile * kF32Row];
+    __shared__ float rD[kF32Tile], rW[kF32Tile], rC[kF32Tile];
+    __shared__ int32_t rG[kF32Tile];
+    const int tid = threadIdx.x;
+    const F32TileLane L = f32t_lane(tid);
+    const int rtiles = a.rb / kF32Tile;
     const int rt = blockIdx.x % rtiles, ct = blockIdx.x / rtiles;
-    const int i0 = a.r0 + rt * kNxTile, j0 = ct * kNxTile;
-    if (tid < kNxTile) {      // read after the K loop's barriers
+    const int i0 = a.r0 + rt * kF32Tile, j0 = ct * kF32Tile;
+    if (tid < kF32Tile) {      // read after the K loop's barriers
         rD[tid] = a.Dp[i0 + tid]; rW[tid] = a.wv[i0 + tid]; rC[tid] = a.wc[i0 + tid]; rG[tid] = a.gid[i0 + tid];
     }
     f32x16 acc[2][2];
-    nx_product(a.zn, a.pP, i0, a.nP, a.zn, a.pP, j0, a.nP, a.pP, ldsA, ldsB, tid, acc);
+    f32t_product(a.zn, a.pP, i0, a.nP, a.zn, a.pP, j0, a.nP, a.pP, ldsA, ldsB, tid, acc);
     int cj[2]; int32_t gj[2]; float Dj[2], wj[2], wcj[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        cj[j] = j0 + wq * 64 + 32 * j + r;
+        cj[j] = F32T_BROW(L, j0, j);
         gj[j] = a.gid[cj[j]]; Dj[j] = a.Dp[cj[j]]; wj[j] = a.wv[cj[j]]; wcj[j] = a.wc[cj[j]];
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int il = wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int il = F32T_AROW(L, 0, i, e);
             const int gi = i0 + il;
             const float Di = rD[il], wi = rW[il], wci = rC[il];
             const int32_t gri = rG[il];
@@ -355,22 +288,22 @@ __global__ __launch_bounds__(256) void nx_e_kernel(NxBwdArgs a) {
 
 // dzn [i - r0][c] = sum_k E [i - r0][k] znT [c][k]
 __global__ __launch_bounds__(256) void nx_dzn_kernel(NxBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) float ldsA[kNxTile * kNxRow];
-    __shared__ __attribute__((aligned(16))) float ldsB[kNxTile * kNxRow];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-    const int ctiles = (a.pP + kNxTile - 1) / kNxTile;
+    __shared__ __attribute__((aligned(16))) float ldsA[kF32Tile * kF32Row];
+    __shared__ __attribute__((aligned(16))) float ldsB[kF32Tile * kF32Row];
+    const int tid = threadIdx.x;
+    const F32TileLane L = f32t_lane(tid);
+    const int ctiles = (a.pP + kF32Tile - 1) / kF32Tile;
     const int ct = blockIdx.x % ctiles, rt = blockIdx.x / ctiles;
     f32x16 acc[2][2];
-    nx_product(a.E, a.nP, rt * kNxTile, a.rb, a.znT, a.nP, ct * kNxTile, a.pP, a.nP, ldsA, ldsB, tid, acc);
+    f32t_product(a.E, a.nP, rt * kF32Tile, a.rb, a.znT, a.nP, ct * kF32Tile, a.pP, a.nP, ldsA, ldsB, tid, acc);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int il = rt * kNxTile + wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int il = F32T_AROW(L, rt * kF32Tile, i, e);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int c = ct * kNxTile + wq * 64 + 32 * j + r;
+                const int c = F32T_BROW(L, ct * kF32Tile, j);
                 if (c < a.pP) a.dzn[(int64_t)il * a.pP + c] = acc[i][j][e];
             }
         }
@@ -397,9 +330,8 @@ __global__ __launch_bounds__(256) void nx_dfrow_kernel(NxBwdArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-int64_t nx_align(int64_t b) { return (b + 255) / 256 * 256; }
-int nx_np(int n) { return (n + kNxTile - 1) / kNxTile * kNxTile; }
-int nx_pp(int p) { return (p + kNxKStep - 1) / kNxKStep * kNxKStep; }
+int nx_np(int n) { return (n + kF32Tile - 1) / kF32Tile * kF32Tile; }
+int nx_pp(int p) { return (p + kF32KStep - 1) / kF32KStep * kF32KStep; }
 
 int nx_check_shape(const char* who, int n, int p, int key_splits, int block_rows) {
     BVC_REQUIRE(n >= 1 && n <= kNxMaxN, "%s: n %d outside 1 .. %d", who, n, kNxMaxN);
@@ -423,7 +355,7 @@ int nx_check_args(const char* who, const float* f, int64_t ldf, const int32_t* g
 
 // about two workgroups per CU, every split at least one key tile, at most 64
 int nx_auto_splits(int n) {
-    const int tiles = nx_np(n) / kNxTile;
+    const int tiles = nx_np(n) / kF32Tile;
     int s = (2 * kNxCUs + tiles - 1) / tiles;
     if (s > tiles) s = tiles;
     if (s > 64) s = 64;
@@ -433,15 +365,15 @@ int nx_auto_splits(int n) {
 // whole tiles of rows under the cap of the E block, at least one tile, at most all rows
 int nx_auto_block_rows(int n) {
     const int nP = nx_np(n);
-    int64_t r = kNxEBlockBytes / ((int64_t)nP * 4) / kNxTile * kNxTile;
-    if (r < kNxTile) r = kNxTile;
+    int64_t r = kNxEBlockBytes / ((int64_t)nP * 4) / kF32Tile * kF32Tile;
+    if (r < kF32Tile) r = kF32Tile;
     if (r > nP) r = nP;
     return (int)r;
 }
 int nx_resolve_block_rows(int n, int block_rows) {
     if (block_rows <= 0) return nx_auto_block_rows(n);
     const int nP = nx_np(n);
-    int64_t r = ((int64_t)block_rows + kNxTile - 1) / kNxTile * kNxTile;
+    int64_t r = ((int64_t)block_rows + kF32Tile - 1) / kF32Tile * kF32Tile;
     return (int)(r > nP ? nP : r);
 }
 
@@ -455,24 +387,21 @@ NxLayout nx_layout(int n, int p, int key_splits, int block_rows) {
     w.splits = key_splits > 0 ? key_splits : nx_auto_splits(n);
     w.R = nx_resolve_block_rows(n, block_rows);
     int64_t o = 0;
-    const int64_t vec = nx_align((int64_t)w.nP * 4);
+    const int64_t vec = ws_align((int64_t)w.nP * 4);
     w.inv = o; o += vec; w.live = o; o += vec; w.gid = o; o += vec; w.Dp = o; o += vec; w.wv = o; o += vec; w.wc = o; o += vec;
-    w.part = o; o += nx_align((int64_t)w.splits * w.nP * 16);
-    w.zn = o; o += nx_align((int64_t)w.nP * w.pP * 4);
-    w.znT = o; o += nx_align((int64_t)w.nP * w.pP * 4);
-    w.E = o; o += nx_align((int64_t)w.R * w.nP * 4);
-    w.dzn = o; o += nx_align((int64_t)w.R * w.pP * 4);
+    w.part = o; o += ws_align((int64_t)w.splits * w.nP * 16);
+    w.zn = o; o += ws_align((int64_t)w.nP * w.pP * 4);
+    w.znT = o; o += ws_align((int64_t)w.nP * w.pP * 4);
+    w.E = o; o += ws_align((int64_t)w.R * w.nP * 4);
+    w.dzn = o; o += ws_align((int64_t)w.R * w.pP * 4);
     w.total = o;
     return w;
 }
 
-template <class T>
-T* nx_at(void* ws, int64_t off) { return reinterpret_cast<T*>(static_cast<unsigned char*>(ws) + off); }
-
 int nx_prologue(const NxLayout& w, NxRowArgs& ra, void* ws, hipStream_t s) {
     ra.nP = w.nP; ra.pP = w.pP;
-    ra.inv = nx_at<float>(ws, w.inv); ra.live = nx_at<int32_t>(ws, w.live); ra.gid = nx_at<int32_t>(ws, w.gid); ra.zn = nx_at<float>(ws, w.zn);
-    ra.Dp = nx_at<float>(ws, w.Dp); ra.wv = nx_at<float>(ws, w.wv); ra.wc = nx_at<float>(ws, w.wc);
+    ra.inv = ws_at<float>(ws, w.inv); ra.live = ws_at<int32_t>(ws, w.live); ra.gid = ws_at<int32_t>(ws, w.gid); ra.zn = ws_at<float>(ws, w.zn);
+    ra.Dp = ws_at<float>(ws, w.Dp); ra.wv = ws_at<float>(ws, w.wv); ra.wc = ws_at<float>(ws, w.wc);
     nx_rows_kernel<<<dim3((unsigned)(w.nP / 4)), dim3(256), 0, s>>>(ra);
     BVC_CHECK_HIP(hipGetLastError());
     return BVC_OK;
@@ -504,8 +433,8 @@ int launch_ntxent_fwd(const float* f, int64_t ldf, const int32_t* groups, int vi
     NxRowArgs ra{};
     ra.f = f; ra.ldf = ldf; ra.groups = groups; ra.views = views; ra.n = n; ra.p = p; ra.eps = eps;
     if (int rc = nx_prologue(w, ra, workspace, s)) return rc;
-    NxFwdArgs a{ra.zn, ra.gid, nx_at<float>(workspace, w.part), n, w.nP, w.pP, w.splits, 1.0f / temperature};
-    nx_fwd_kernel<<<dim3((unsigned)(w.nP / kNxTile * w.splits)), dim3(256), 0, s>>>(a);
+    NxFwdArgs a{ra.zn, ra.gid, ws_at<float>(workspace, w.part), n, w.nP, w.pP, w.splits, 1.0f / temperature};
+    nx_fwd_kernel<<<dim3((unsigned)(w.nP / kF32Tile * w.splits)), dim3(256), 0, s>>>(a);
     BVC_CHECK_HIP(hipGetLastError());
     nx_combine_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(a.part, n, w.nP, w.splits, row_loss, lse, npos);
     nx_stats_kernel<<<dim3(1), dim3(256), 0, s>>>(row_loss, npos, n, stats2);
@@ -525,18 +454,18 @@ int launch_ntxent_bwd(const float* f, int64_t ldf, const int32_t* groups, int vi
     ra.f = f; ra.ldf = ldf; ra.groups = groups; ra.views = views; ra.n = n; ra.p = p; ra.eps = eps;
     ra.lse = lse; ra.npos = npos; ra.row_weight = row_weight;
     if (int rc = nx_prologue(w, ra, workspace, s)) return rc;
-    float* znT = nx_at<float>(workspace, w.znT);
+    float* znT = ws_at<float>(workspace, w.znT);
     nx_transpose_kernel<<<dim3((unsigned)(w.pP / 32), (unsigned)(w.nP / 32)), dim3(256), 0, s>>>(ra.zn, znT, w.nP, w.pP);
     BVC_CHECK_HIP(hipGetLastError());
     NxBwdArgs a{};
     a.zn = ra.zn; a.znT = znT; a.gid = ra.gid; a.Dp = ra.Dp; a.wv = ra.wv; a.wc = ra.wc; a.inv = ra.inv; a.live = ra.live;
-    a.E = nx_at<float>(workspace, w.E); a.dzn = nx_at<float>(workspace, w.dzn); a.df = df; a.lddf = lddf;
+    a.E = ws_at<float>(workspace, w.E); a.dzn = ws_at<float>(workspace, w.dzn); a.df = df; a.lddf = lddf;
     a.n = n; a.nP = w.nP; a.p = p; a.pP = w.pP; a.invT = 1.0f / temperature; a.eps = eps;
-    const int tiles = w.nP / kNxTile, ctiles = (w.pP + kNxTile - 1) / kNxTile;
+    const int tiles = w.nP / kF32Tile, ctiles = (w.pP + kF32Tile - 1) / kF32Tile;
     for (int r0 = 0; r0 < w.nP; r0 += w.R) {
         a.r0 = r0;
         a.rb = w.nP - r0 < w.R ? w.nP - r0 : w.R;
-        const int rtiles = a.rb / kNxTile;
+        const int rtiles = a.rb / kF32Tile;
         nx_e_kernel<<<dim3((unsigned)(rtiles * tiles)), dim3(256), 0, s>>>(a);
         nx_dzn_kernel<<<dim3((unsigned)(rtiles * ctiles)), dim3(256), 0, s>>>(a);
         nx_dfrow_kernel<<<dim3((unsigned)(a.rb / 4)), dim3(256), 0, s>>>(a);

@@ -17,12 +17,9 @@
 //   high = order-preserving image of the bits of -value, low = ~index      (real candidates are > 0; 0 = empty slot),
 // so sorting, merging and thresholding are one unsigned compare, and the result does not depend on arrival order anywhere.
 //
-// retr_topk_kernel: 256 threads = 4 waves as 2 (key halves) x 2 (query halves); one workgroup owns 128 queries and a range of key
-// tiles (128 keys each).  Per key tile a 32-deep K loop: operands global -> registers (next step) -> LDS (36-float rows, even d in
-// floats 0..15 and odd d in 16..31 of a row, so lane (r, h) of the MFMA reads its 16 operands of a step - d = 2 kk + h - as four
-// ds_read_b128, conflict-free at a 9-slot row stride); each wave holds 64 keys x 64 queries as 2 x 2 accumulators of 32 x 32 with the
-// KEYS as the A operand: the query is on the lane, so a lane keeps its two queries' thresholds in registers and the candidate
-// counters of one instruction's lanes are distinct.
+// retr_topk_kernel: one workgroup owns 128 queries and a range of key tiles (128 keys each).  Per key tile the K loop of f32_tile.h,
+// here over the caller's rows as they are (any stride, any D: f32t_load_raw), with the KEYS as the A operand: the query is on the
+// lane, so a lane keeps its two queries' thresholds in registers and the candidate counters of one instruction's lanes are distinct.
 // Selection: per query row a sorted list of k words in LDS and its k-th word as the threshold.  A lane turns its 64 scores into
 // words, appends those above the threshold to the row's queue (integer LDS counter), and a wave merges a row's queue into its list
 // by rank (every word counts the words above it: the ranks of distinct words are a permutation, so there is nothing to sort).  A
@@ -34,15 +31,12 @@
 // no dependence on timing: the same bits on every run, for every key_splits and every chunking.
 #include <math.h>
 
-#include "common.h"
+#include "f32_tile.h"
 
 namespace bvc {
 
 typedef unsigned long long u64;
 
-constexpr int kRetrTile = 128;       // queries per workgroup, keys per tile step
-constexpr int kRetrKStep = 32;       // floats of D per LDS stage
-constexpr int kRetrRow = 36;         // floats per LDS operand row (32 + 4: ds_read_b128 of 16 rows land on 16 different slots)
 constexpr int kRetrQueue = 32;       // candidate words per row and pass
 constexpr int kRetrMaxK = 64;
 constexpr int kRetrCUs = 256;
@@ -92,50 +86,12 @@ __global__ __launch_bounds__(256) void retr_rownorm_kernel(const float* __restri
     if (lane == 0) out[row] = inverse ? (s > 0.f ? 1.0f / sqrtf(s) : 0.f) : s;
 }
 
-// 16 floats of 4 rows (rows r0 + 32 m) of a 128-row x 32-float operand stage: thread t reads floats 4 (t & 7) .. + 3 of row t >> 3.
-// No load sits under a per-lane condition (hipcc would branch around each and wait for it before the next): a whole step of
-// 16-byte-aligned rows is four unconditional 16-byte loads, chosen by a workgroup-uniform test; everything else - the D tail,
-// unaligned rows - is sixteen unconditional 4-byte loads from the column clamped to D - 1 of the same row, zeroed by a select.
-template <bool VEC>
-__device__ __forceinline__ void retr_load(const float* __restrict__ base, int64_t ld, int row0, int rows, int d0, int D, int tid,
-                                          f32x4 (&v)[4]) {
-    const int c = (tid & 7) * 4 + d0, r0 = tid >> 3;
-    if (VEC && d0 + kRetrKStep <= D) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int row = min(row0 + r0 + 32 * m, rows - 1);      // rows past the end repeat the last one (never selected)
-            v[m] = *reinterpret_cast<const f32x4*>(base + (int64_t)row * ld + c);
-        }
-    } else {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int row = min(row0 + r0 + 32 * m, rows - 1);
-            const float* p = base + (int64_t)row * ld;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float x = p[min(c + e, D - 1)];
-                v[m][e] = c + e < D ? x : 0.f;
-            }
-        }
-    }
-}
-// floats d = 4 c .. 4 c + 3 of a row go to the even-d half at 2 c, 2 c + 1 (d = 4 c, 4 c + 2) and the odd-d half at 16 + 2 c ..
-__device__ __forceinline__ void retr_stage(float* lds, int tid, const f32x4 (&v)[4]) {
-    const int c = tid & 7, r0 = tid >> 3;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        float* row = lds + (r0 + 32 * m) * kRetrRow;
-        *reinterpret_cast<f32x2*>(row + 2 * c) = f32x2{v[m][0], v[m][2]};
-        *reinterpret_cast<f32x2*>(row + 16 + 2 * c) = f32x2{v[m][1], v[m][3]};
-    }
-}
-
 // The rows of this wave (wave + 4 l, l = 0 .. 31) whose queue holds at least `least` words: merge, raise the threshold, empty the
 // queue.  Lane l looks at one row's counter and the wave walks the set bits.  A queue is left to fill to half (least = 16) before
 // it is merged - a later merge costs one pass whatever it holds, and a stale threshold only lets more candidates in - and every
 // queue is flushed (least = 1) after the last tile.  A queue that overflowed is full, so the pass after an overflow finds room.
 __device__ __forceinline__ void retr_merge_rows(u64* list, u64* queue, u64* thr, int* cnt, int k, int least, int wave, int lane) {
-    const int mine = lane < kRetrTile / 4 ? cnt[wave + 4 * lane] : 0;
+    const int mine = lane < kF32Tile / 4 ? cnt[wave + 4 * lane] : 0;
     u64 work = __ballot(mine >= least);
     while (work) {
         const int l = __ffsll((unsigned long long)work) - 1;
@@ -157,19 +113,19 @@ struct RetrArgs {
 
 // dynamic LDS (bytes): operands 2 x 128 x 36 x 4 | lists 128 x 64 x 8 | queues 128 x 32 x 8 | thresholds 128 x 8 | key statistic
 // 128 x 4 | counters 128 x 4 | 2 pass flags
-constexpr int kRetrOffList = 2 * kRetrTile * kRetrRow * 4;
-constexpr int kRetrOffQueue = kRetrOffList + kRetrTile * kRetrMaxK * 8;
-constexpr int kRetrOffThr = kRetrOffQueue + kRetrTile * kRetrQueue * 8;
-constexpr int kRetrOffStat = kRetrOffThr + kRetrTile * 8;
-constexpr int kRetrOffCnt = kRetrOffStat + kRetrTile * 4;
-constexpr int kRetrOffFlag = kRetrOffCnt + kRetrTile * 4;
+constexpr int kRetrOffList = 2 * kF32Tile * kF32Row * 4;
+constexpr int kRetrOffQueue = kRetrOffList + kF32Tile * kRetrMaxK * 8;
+constexpr int kRetrOffThr = kRetrOffQueue + kF32Tile * kRetrQueue * 8;
+constexpr int kRetrOffStat = kRetrOffThr + kF32Tile * 8;
+constexpr int kRetrOffCnt = kRetrOffStat + kF32Tile * 4;
+constexpr int kRetrOffFlag = kRetrOffCnt + kF32Tile * 4;
 constexpr int kRetrLds = kRetrOffFlag + 16;
 
 template <int METRIC, bool VEC>
 __global__ __launch_bounds__(256) void retr_topk_kernel(RetrArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* const ldsK = reinterpret_cast<float*>(smem);
-    float* const ldsQ = ldsK + kRetrTile * kRetrRow;
+    float* const ldsQ = ldsK + kF32Tile * kF32Row;
     u64* const list = reinterpret_cast<u64*>(smem + kRetrOffList);
     u64* const queue = reinterpret_cast<u64*>(smem + kRetrOffQueue);
     u64* const thr = reinterpret_cast<u64*>(smem + kRetrOffThr);
@@ -178,71 +134,51 @@ __global__ __launch_bounds__(256) void retr_topk_kernel(RetrArgs a) {
     int* const flag = reinterpret_cast<int*>(smem + kRetrOffFlag);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wk = wave & 1, wq = wave >> 1;
-    const int qtiles = (a.Q + kRetrTile - 1) / kRetrTile;
+    const F32TileLane L = f32t_lane(tid);
+    const int qtiles = (a.Q + kF32Tile - 1) / kF32Tile;
     const int qt = blockIdx.x % qtiles, split = blockIdx.x / qtiles;      // query tiles of one split run side by side
-    const int q0 = qt * kRetrTile;
-    const int ktiles = (a.N + kRetrTile - 1) / kRetrTile;
+    const int q0 = qt * kF32Tile;
+    const int ktiles = (a.N + kF32Tile - 1) / kF32Tile;
     const int t_begin = (int)((int64_t)ktiles * split / a.splits), t_end = (int)((int64_t)ktiles * (split + 1) / a.splits);
     const int k = a.k;
 
-    for (int i = tid; i < kRetrTile * kRetrMaxK; i += 256) list[i] = 0ull;
-    if (tid < kRetrTile) { thr[tid] = 0ull; cnt[tid] = 0; }
+    for (int i = tid; i < kF32Tile * kRetrMaxK; i += 256) list[i] = 0ull;
+    if (tid < kF32Tile) { thr[tid] = 0ull; cnt[tid] = 0; }
     if (tid < 2) flag[tid] = 0;
 
     // this lane's two queries (j = 0, 1): local row, validity, statistic
     int ql[2]; bool qok[2]; float qs[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        ql[j] = wq * 64 + 32 * j + r;
+        ql[j] = F32T_BROW(L, 0, j);
         qok[j] = q0 + ql[j] < a.Q;
         qs[j] = a.qstat[min(q0 + ql[j], a.Q - 1)];
     }
-    const int ksteps = (a.D + kRetrKStep - 1) / kRetrKStep;
+    const int ksteps = (a.D + kF32KStep - 1) / kF32KStep;
     int pass = 0;
     __syncthreads();
 
     for (int t = t_begin; t < t_end; ++t) {
-        const int key0 = t * kRetrTile;
-        if (tid < kRetrTile) kstat[tid] = a.kstat[min(key0 + tid, a.N - 1)];      // read after the K loop's barriers
+        const int key0 = t * kF32Tile;
+        if (tid < kF32Tile) kstat[tid] = a.kstat[min(key0 + tid, a.N - 1)];      // read after the K loop's barriers
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        f32t_zero(acc);
         f32x4 vk[4], vq[4];
-        retr_load<VEC>(a.keys, a.ldk, key0, a.N, 0, a.D, tid, vk);
-        retr_load<VEC>(a.q, a.ldq, q0, a.Q, 0, a.D, tid, vq);
+        f32t_load_raw<VEC>(a.keys, a.ldk, key0, a.N, 0, a.D, tid, vk);
+        f32t_load_raw<VEC>(a.q, a.ldq, q0, a.Q, 0, a.D, tid, vq);
         for (int s = 0; s < ksteps; ++s) {
-            retr_stage(ldsK, tid, vk);
-            retr_stage(ldsQ, tid, vq);
+            f32t_stage(ldsK, tid, vk);
+            f32t_stage(ldsQ, tid, vq);
             __syncthreads();
             if (s + 1 < ksteps) {
-                retr_load<VEC>(a.keys, a.ldk, key0, a.N, (s + 1) * kRetrKStep, a.D, tid, vk);
-                retr_load<VEC>(a.q, a.ldq, q0, a.Q, (s + 1) * kRetrKStep, a.D, tid, vq);
+                f32t_load_raw<VEC>(a.keys, a.ldk, key0, a.N, (s + 1) * kF32KStep, a.D, tid, vk);
+                f32t_load_raw<VEC>(a.q, a.ldq, q0, a.Q, (s + 1) * kF32KStep, a.D, tid, vq);
             }
-            f32x4 fk[2][4], fq[2][4];      // element e of piece m: d = 2 (4 m + e) + h of the step
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    fk[b][m] = *reinterpret_cast<const f32x4*>(ldsK + (wk * 64 + 32 * b + r) * kRetrRow + 16 * h + 4 * m);
-                    fq[b][m] = *reinterpret_cast<const f32x4*>(ldsQ + (wq * 64 + 32 * b + r) * kRetrRow + 16 * h + 4 * m);
-                }
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fk[i][kk >> 2][kk & 3], fq[j][kk >> 2][kk & 3], acc[i][j], 0, 0, 0);
+            f32t_step(ldsK, ldsQ, tid, acc);
             __syncthreads();      // the stage is free for the next step's write
         }
 
-        // ---- values in place.  Element e of acc[i][j]: key row wk 64 + 32 i + (e & 3) + 8 (e >> 2) + 4 h, query ql[j]
+        // ---- values in place.  Element e of acc[i][j]: key row F32T_AROW(L, 0, i, e), query ql[j]
         uint32_t pend[2] = {0u, 0u};       // per j: bit 16 i + e = still to be offered
         float reach[2];                    // the value of the row's threshold (+inf while its list is not full): a value above it
 #pragma unroll                             // cannot pass, so the 64-bit word is built only for the few that are at or below it
@@ -254,7 +190,7 @@ __global__ __launch_bounds__(256) void retr_topk_kernel(RetrArgs a) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int kl = wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int kl = F32T_AROW(L, 0, i, e);
                 const float ks = kstat[kl];
                 const bool kok = key0 + kl < a.N;
 #pragma unroll
@@ -283,7 +219,7 @@ __global__ __launch_bounds__(256) void retr_topk_kernel(RetrArgs a) {
                     for (int e = 0; e < 16; ++e) {
                         const uint32_t bit = 1u << (16 * i + e);
                         if (pend[j] & bit) {
-                            const int kl = wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                            const int kl = F32T_AROW(L, 0, i, e);
                             const u64 w = retr_word(acc[i][j][e], a.key_base + key0 + kl);
                             if (w > th) {
                                 const int slot = atomicAdd(&cnt[ql[j]], 1);
@@ -307,7 +243,7 @@ __global__ __launch_bounds__(256) void retr_topk_kernel(RetrArgs a) {
     // ---- what is still queued, then this split's lists
     retr_merge_rows(list, queue, thr, cnt, k, 1, wave, lane);
     __syncthreads();
-    for (int i = tid; i < kRetrTile * k; i += 256) {
+    for (int i = tid; i < kF32Tile * k; i += 256) {
         const int row = i / k, j = i - row * k;
         if (q0 + row < a.Q) a.lists[((int64_t)split * a.Q + q0 + row) * k + j] = list[row * kRetrMaxK + j];
     }
@@ -340,14 +276,13 @@ __global__ __launch_bounds__(256) void retr_finish_kernel(const u64* __restrict_
 }
 
 // ---------------------------------------------------------------- host side
-static size_t retr_align(size_t b) { return (b + 255) / 256 * 256; }
 
 static int retr_auto_splits(int Q, int N) {
     // One workgroup per CU at a time (LDS), so the cost of s splits is rounds x work of a workgroup:
     //   ceil(query tiles x s / CUs) x (key tiles per split + 8),   8 tiles standing for a split's start-up passes and its merge.
     // Few query tiles: the key range is cut until the CUs are busy; many: s is chosen so that the last round is nearly full.
     // Each split covers at least 4 key tiles, at most 64 splits; ties go to the smaller s.
-    const int64_t qtiles = ((int64_t)Q + kRetrTile - 1) / kRetrTile, ktiles = ((int64_t)N + kRetrTile - 1) / kRetrTile;
+    const int64_t qtiles = ((int64_t)Q + kF32Tile - 1) / kF32Tile, ktiles = ((int64_t)N + kF32Tile - 1) / kF32Tile;
     int64_t most = ktiles / 4;
     if (most > 64) most = 64;
     int best = 1;
@@ -361,7 +296,7 @@ static int retr_auto_splits(int Q, int N) {
 }
 
 static int retr_resolve_splits(int Q, int N, int key_splits) {
-    const int64_t ktiles = ((int64_t)N + kRetrTile - 1) / kRetrTile;
+    const int64_t ktiles = ((int64_t)N + kF32Tile - 1) / kF32Tile;
     int s = key_splits > 0 ? key_splits : retr_auto_splits(Q, N);
     if (s > ktiles) s = (int)ktiles;      // no empty split
     return s;
@@ -377,7 +312,7 @@ static int retr_check_shape(int Q, int N, int D, int k, int key_splits) {
 int64_t retr_workspace(int Q, int N, int D, int k, int key_splits) {
     if (retr_check_shape(Q, N, D, k, key_splits) != BVC_OK) return -1;
     const int s = retr_resolve_splits(Q, N, key_splits);
-    return (int64_t)(retr_align((size_t)Q * 4) + retr_align((size_t)N * 4) + (size_t)s * Q * k * 8);
+    return ws_align((int64_t)Q * 4) + ws_align((int64_t)N * 4) + (int64_t)s * Q * k * 8;
 }
 
 int retr_splits(int Q, int N, int D, int k) {
@@ -396,13 +331,12 @@ int launch_topk(const float* queries, int64_t ldq, const float* keys, int64_t ld
     BVC_REQUIRE(accumulate == 0 || accumulate == 1, "op_topk: accumulate %d", accumulate);
     BVC_REQUIRE(((uintptr_t)queries & 3) == 0 && ((uintptr_t)keys & 3) == 0 && ((uintptr_t)workspace & 7) == 0, "op_topk: misaligned pointer");
     const int splits = retr_resolve_splits(Q, N, key_splits);
-    const int64_t qtiles = ((int64_t)Q + kRetrTile - 1) / kRetrTile;
+    const int64_t qtiles = ((int64_t)Q + kF32Tile - 1) / kF32Tile;
     BVC_REQUIRE(qtiles * splits < 0x7fffffffll, "op_topk: %lld workgroups exceed the grid", (long long)(qtiles * splits));
 
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    float* qstat = reinterpret_cast<float*>(ws);
-    float* kstat = reinterpret_cast<float*>(ws + retr_align((size_t)Q * 4));
-    u64* lists = reinterpret_cast<u64*>(ws + retr_align((size_t)Q * 4) + retr_align((size_t)N * 4));
+    float* qstat = ws_at<float>(workspace, 0);
+    float* kstat = ws_at<float>(workspace, ws_align((int64_t)Q * 4));
+    u64* lists = ws_at<u64>(workspace, ws_align((int64_t)Q * 4) + ws_align((int64_t)N * 4));
 
     retr_rownorm_kernel<<<dim3((unsigned)(((int64_t)Q + 3) / 4)), dim3(256), 0, stream>>>(queries, ldq, Q, D, metric == 0, qstat);
     retr_rownorm_kernel<<<dim3((unsigned)(((int64_t)N + 3) / 4)), dim3(256), 0, stream>>>(keys, ldk, N, D, metric == 0, kstat);

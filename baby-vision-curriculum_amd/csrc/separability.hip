@@ -297,7 +297,6 @@ __global__ __launch_bounds__(256) void sep_argmax_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------- host side
-static size_t sep_align(size_t b) { return (b + 255) / 256 * 256; }
 static int sep_tile_rows(int D) { return D + 1 <= 832 ? 32 : 16; }
 static int sep_stride(int D) {      // D + 1 padded to 16 columns, then to 18 mod 32 (conflict-free operand reads of product 1)
     int s = (D + 1 + 15) / 16 * 16;
@@ -323,9 +322,9 @@ static int sep_check_shape(int n, int D, int K, int mode) {
 
 int64_t sep_workspace(int n, int D, int K, int mode) {
     if (sep_check_shape(n, D, K, mode) != BVC_OK) return -1;
-    if (mode == kSepDecision) return (int64_t)sep_align((size_t)n * K * 4);
+    if (mode == kSepDecision) return ws_align((int64_t)n * K * 4);
     const int s = sep_resolve_splits(n, D, K);
-    return (int64_t)(sep_align((size_t)s * K * (D + 1) * 4) + sep_align((size_t)s * K * 4));
+    return ws_align((int64_t)s * K * (D + 1) * 4) + ws_align((int64_t)s * K * 4);
 }
 
 template <int MODE>
@@ -365,20 +364,19 @@ int launch_linear_pass(const float* x, int64_t ldx, const int* labels, const flo
 
     const int splits = sep_resolve_splits(n, D, K);
     const int chunks = (K + kSepKc - 1) / kSepKc;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
     SepArgs a{};
     a.x = x; a.ldx = ldx; a.labels = labels; a.mean = mean; a.inv_std = inv_std; a.W = W; a.V = V;
     a.n = n; a.D = D; a.K = K; a.class0 = class0; a.splits = splits; a.stride = sep_stride(D); a.C = C;
     if (mode == kSepDecision) {
-        a.dec = out_dec ? out_dec : reinterpret_cast<float*>(ws);
+        a.dec = out_dec ? out_dec : ws_at<float>(workspace, 0);
         if (int rc = sep_launch<kSepDecision>(a, splits * chunks, stream)) return rc;
         sep_argmax_kernel<<<dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, stream>>>(a.dec, n, K, out_pred);
         BVC_CHECK_HIP(hipGetLastError());
         return BVC_OK;
     }
     const int64_t ng = (int64_t)K * (D + 1);
-    a.part_G = reinterpret_cast<float*>(ws);
-    a.part_loss = reinterpret_cast<float*>(ws + sep_align((size_t)splits * ng * 4));
+    a.part_G = ws_at<float>(workspace, 0);
+    a.part_loss = ws_at<float>(workspace, ws_align(splits * ng * 4));
     if (int rc = mode == kSepGrad ? sep_launch<kSepGrad>(a, splits * chunks, stream) : sep_launch<kSepHessvec>(a, splits * chunks, stream)) return rc;
     sep_reduce_kernel<<<dim3((unsigned)((ng + K + 255) / 256)), dim3(256), 0, stream>>>(a.part_G, a.part_loss, splits, ng, K, out_G,
                                                                                        mode == kSepGrad ? out_loss : nullptr);

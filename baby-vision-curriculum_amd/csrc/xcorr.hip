@@ -8,8 +8,8 @@
 //     dx_ij = r_j (dxh_ij - mean_i' dxh_i'j) + 2 (x_ij - mu_j) a_j / (n - ddof).
 //
 // Arithmetic: f32 throughout, every element of C ONE accumulation chain over the rows in ascending order on v_mfma_f32_32x32x2_f32.
-// xc_product is ntxent.hip's tile loop (a private copy): C [128][128] = A [128][K] . B [128][K]^T, both operands contraction-contiguous,
-// 256 threads = 4 waves as 2 (A halves) x 2 (B halves), a 32-float K stage through LDS with 36-float rows.
+// The three products are f32t_product of f32_tile.h, C [128][128] = A [128][K] . B [128][K]^T over padded operands in the workspace;
+// the epilogues below take their rows (A side) and columns (B side) from its helpers.
 //   prologue  xc_stats_kernel: column mean and variance, summed in f64 in a fixed order, one rounding to f32.  xc_centre_kernel: from
 //             the ROUNDED mean and variance (what the backward is handed), the transposed operand xhT [p][nK] (nK = n up to 32, the
 //             contraction index contiguous) and, in the backward, the row-major xh [n][pK] (pK = p up to 32).  Elements beyond n or p
@@ -22,79 +22,13 @@
 //             order and writes dx.  Then the same for blocks of columns of y with the operands' roles swapped (G^T is recomputed, not
 //             transposed: every element of dyh stays one chain over all p).  The alias case runs the first pass only, with 2 G.
 // No atomics: the same bits on every run and for every blocking.  Nothing in the workspace survives a call.
+#include "f32_tile.h"
 #include "xcorr.h"
 
 #include <math.h>
 
 namespace bvc {
 namespace {
-
-constexpr int kXcTile = 128;
-constexpr int kXcKStep = 32;
-constexpr int kXcRow = 36;           // floats per LDS operand row
-
-// 16 floats of 4 rows (rows r0 + 32 m) of a 128-row x 32-float stage; the operands live in the workspace: 16-byte aligned rows,
-// K a multiple of 32, rows past the end repeat the last one (their products are never used).
-__device__ __forceinline__ void xc_load(const float* __restrict__ base, int64_t ld, int row0, int rows, int d0, int tid, f32x4 (&v)[4]) {
-    const int c = (tid & 7) * 4 + d0, r0 = tid >> 3;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int row = min(row0 + r0 + 32 * m, rows - 1);
-        v[m] = *reinterpret_cast<const f32x4*>(base + (int64_t)row * ld + c);
-    }
-}
-__device__ __forceinline__ void xc_stage(float* lds, int tid, const f32x4 (&v)[4]) {
-    const int c = tid & 7, r0 = tid >> 3;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        float* row = lds + (r0 + 32 * m) * kXcRow;
-        *reinterpret_cast<f32x2*>(row + 2 * c) = f32x2{v[m][0], v[m][2]};
-        *reinterpret_cast<f32x2*>(row + 16 + 2 * c) = f32x2{v[m][1], v[m][3]};
-    }
-}
-
-// acc[i][j][e] = sum_d A[a0 + arow][d] B[b0 + brow][d],  arow = wk 64 + 32 i + (e & 3) + 8 (e >> 2) + 4 h,  brow = wq 64 + 32 j + r
-// (wave = wk + 2 wq, lane = r + 32 h).  Ends with a barrier: the stages are free on return.
-__device__ __forceinline__ void xc_product(const float* __restrict__ A, int64_t lda, int a0, int arows, const float* __restrict__ B,
-                                           int64_t ldb, int b0, int brows, int K, float* ldsA, float* ldsB, int tid, f32x16 (&acc)[2][2]) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    const int ksteps = K / kXcKStep;
-    f32x4 va[4], vb[4];
-    xc_load(A, lda, a0, arows, 0, tid, va);
-    xc_load(B, ldb, b0, brows, 0, tid, vb);
-    for (int s = 0; s < ksteps; ++s) {
-        xc_stage(ldsA, tid, va);
-        xc_stage(ldsB, tid, vb);
-        __syncthreads();
-        if (s + 1 < ksteps) {
-            xc_load(A, lda, a0, arows, (s + 1) * kXcKStep, tid, va);
-            xc_load(B, ldb, b0, brows, (s + 1) * kXcKStep, tid, vb);
-        }
-        f32x4 fa[2][4], fb[2][4];      // element e of piece m: d = 2 (4 m + e) + h of the step
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                fa[b][m] = *reinterpret_cast<const f32x4*>(ldsA + (wk * 64 + 32 * b + r) * kXcRow + 16 * h + 4 * m);
-                fb[b][m] = *reinterpret_cast<const f32x4*>(ldsB + (wq * 64 + 32 * b + r) * kXcRow + 16 * h + 4 * m);
-            }
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk >> 2][kk & 3], fb[j][kk >> 2][kk & 3], acc[i][j], 0, 0, 0);
-        __syncthreads();
-    }
-}
 
 // ---------------------------------------------------------------- prologue
 // 32 columns per workgroup, 8 row lanes: lane ry sums rows ry, ry + 8, .. in f64, the 8 partials are added in ascending order
@@ -167,24 +101,24 @@ struct XcFwdArgs {
 };
 
 __global__ __launch_bounds__(256) void xc_fwd_kernel(XcFwdArgs a) {
-    __shared__ __attribute__((aligned(16))) float ldsA[kXcTile * kXcRow];
-    __shared__ __attribute__((aligned(16))) float ldsB[kXcTile * kXcRow];
+    __shared__ __attribute__((aligned(16))) float ldsA[kF32Tile * kF32Row];
+    __shared__ __attribute__((aligned(16))) float ldsB[kF32Tile * kF32Row];
     __shared__ double red[2][256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-    const int ptiles = (a.p + kXcTile - 1) / kXcTile;
+    const int tid = threadIdx.x;
+    const F32TileLane L = f32t_lane(tid);
+    const int ptiles = (a.p + kF32Tile - 1) / kF32Tile;
     const int rt = blockIdx.x % ptiles, ct = blockIdx.x / ptiles;
     f32x16 acc[2][2];
-    xc_product(a.xhT, a.nK, rt * kXcTile, a.p, a.yhT, a.nK, ct * kXcTile, a.q, a.nK, ldsA, ldsB, tid, acc);
+    f32t_product(a.xhT, a.nK, rt * kF32Tile, a.p, a.yhT, a.nK, ct * kF32Tile, a.q, a.nK, ldsA, ldsB, tid, acc);
     double on = 0.0, off = 0.0;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int cb = ct * kXcTile + wq * 64 + 32 * j + r;
+            const int cb = F32T_BROW(L, ct * kF32Tile, j);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int ca = rt * kXcTile + wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int ca = F32T_AROW(L, rt * kF32Tile, i, e);
                 if (ca < a.p && cb < a.q) {
                     const float c = acc[i][j][e] * a.scale;
                     if (ca == cb) {
@@ -241,27 +175,27 @@ struct XcBwdArgs {
 
 // G [a - c0][b] = factor scale 2 (a == b ? w_on (C_ab - t) : w_off C_ab);  0 for b beyond qo (the K tail of the next product)
 __global__ __launch_bounds__(256) void xc_g_kernel(XcBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) float ldsA[kXcTile * kXcRow];
-    __shared__ __attribute__((aligned(16))) float ldsB[kXcTile * kXcRow];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-    const int rtiles = (a.rb + kXcTile - 1) / kXcTile;
+    __shared__ __attribute__((aligned(16))) float ldsA[kF32Tile * kF32Row];
+    __shared__ __attribute__((aligned(16))) float ldsB[kF32Tile * kF32Row];
+    const int tid = threadIdx.x;
+    const F32TileLane L = f32t_lane(tid);
+    const int rtiles = (a.rb + kF32Tile - 1) / kF32Tile;
     const int rt = blockIdx.x % rtiles, ct = blockIdx.x / rtiles;
-    const int a0 = a.c0 + rt * kXcTile, b0 = ct * kXcTile;
+    const int a0 = a.c0 + rt * kF32Tile, b0 = ct * kF32Tile;
     const float f = 2.0f * a.scale * a.factor;
     const float won = a.w[0] * f, woff = a.w[1] * f;
     f32x16 acc[2][2];
-    xc_product(a.ownT, a.nK, a0, a.po, a.otherT, a.nK, b0, a.qo, a.nK, ldsA, ldsB, tid, acc);
+    f32t_product(a.ownT, a.nK, a0, a.po, a.otherT, a.nK, b0, a.qo, a.nK, ldsA, ldsB, tid, acc);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int ca = a0 + wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int ca = F32T_AROW(L, a0, i, e);
             if (ca >= a.c0 + a.rb) continue;
             float* grow = a.G + (int64_t)(ca - a.c0) * a.qoK;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int cb = b0 + wq * 64 + 32 * j + r;
+                const int cb = F32T_BROW(L, b0, j);
                 if (cb >= a.qoK) continue;
                 const float c = acc[i][j][e] * a.scale;
                 const float v = ca == cb ? won * (c - a.target) : woff * c;
@@ -272,23 +206,23 @@ __global__ __launch_bounds__(256) void xc_g_kernel(XcBwdArgs a) {
 
 // dxh [i][a - c0] = sum_b other [i][b] G [a - c0][b]
 __global__ __launch_bounds__(256) void xc_dxh_kernel(XcBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) float ldsA[kXcTile * kXcRow];
-    __shared__ __attribute__((aligned(16))) float ldsB[kXcTile * kXcRow];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wk = wave & 1, wq = wave >> 1;
-    const int ctiles = (a.rb + kXcTile - 1) / kXcTile;
+    __shared__ __attribute__((aligned(16))) float ldsA[kF32Tile * kF32Row];
+    __shared__ __attribute__((aligned(16))) float ldsB[kF32Tile * kF32Row];
+    const int tid = threadIdx.x;
+    const F32TileLane L = f32t_lane(tid);
+    const int ctiles = (a.rb + kF32Tile - 1) / kF32Tile;
     const int ct = blockIdx.x % ctiles, rt = blockIdx.x / ctiles;
     f32x16 acc[2][2];
-    xc_product(a.other, a.qoK, rt * kXcTile, a.n, a.G, a.qoK, ct * kXcTile, a.rb, a.qoK, ldsA, ldsB, tid, acc);
+    f32t_product(a.other, a.qoK, rt * kF32Tile, a.n, a.G, a.qoK, ct * kF32Tile, a.rb, a.qoK, ldsA, ldsB, tid, acc);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int row = rt * kXcTile + wk * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int row = F32T_AROW(L, rt * kF32Tile, i, e);
             if (row >= a.n) continue;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int c = ct * kXcTile + wq * 64 + 32 * j + r;
+                const int c = F32T_BROW(L, ct * kF32Tile, j);
                 if (c < a.rb) a.dxh[(int64_t)row * a.R + c] = acc[i][j][e];
             }
         }
@@ -327,9 +261,8 @@ __global__ __launch_bounds__(256) void xc_dx_kernel(XcBwdArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-int64_t xc_align(int64_t b) { return (b + 255) / 256 * 256; }
-int xc_k(int v) { return (v + kXcKStep - 1) / kXcKStep * kXcKStep; }
-int xc_tiles(int v) { return (v + kXcTile - 1) / kXcTile; }
+int xc_k(int v) { return (v + kF32KStep - 1) / kF32KStep * kF32KStep; }
+int xc_tiles(int v) { return (v + kF32Tile - 1) / kF32Tile; }
 
 int xc_check_shape(const char* who, int n, int p, int q, int block_cols) {
     BVC_REQUIRE(n >= 1 && n <= kXcMaxN, "%s: n %d outside 1 .. %d", who, n, kXcMaxN);
@@ -359,16 +292,16 @@ int xc_check_args(const char* who, const float* x, int64_t ldx, const float* y, 
 
 // whole tiles of columns under the cap of the G block, at least one tile, at most all columns
 int xc_auto_block_cols(int p, int q) {
-    const int wide = xc_k(p > q ? p : q), most = xc_tiles(p > q ? p : q) * kXcTile;
-    int64_t r = kXcGBlockBytes / ((int64_t)wide * 4) / kXcTile * kXcTile;
-    if (r < kXcTile) r = kXcTile;
+    const int wide = xc_k(p > q ? p : q), most = xc_tiles(p > q ? p : q) * kF32Tile;
+    int64_t r = kXcGBlockBytes / ((int64_t)wide * 4) / kF32Tile * kF32Tile;
+    if (r < kF32Tile) r = kF32Tile;
     if (r > most) r = most;
     return (int)r;
 }
 int xc_resolve_block_cols(int p, int q, int block_cols) {
     if (block_cols <= 0) return xc_auto_block_cols(p, q);
-    const int most = xc_tiles(p > q ? p : q) * kXcTile;
-    const int64_t r = ((int64_t)block_cols + kXcTile - 1) / kXcTile * kXcTile;
+    const int most = xc_tiles(p > q ? p : q) * kF32Tile;
+    const int64_t r = ((int64_t)block_cols + kF32Tile - 1) / kF32Tile * kF32Tile;
     return (int)(r > most ? most : r);
 }
 
@@ -381,22 +314,19 @@ XcLayout xc_layout(int n, int p, int q, bool alias, int block_cols, bool backwar
     w.nK = xc_k(n); w.pK = xc_k(p); w.qK = xc_k(q);
     w.R = xc_resolve_block_cols(p, q, block_cols);
     int64_t o = 0;
-    w.xhT = o; o += xc_align((int64_t)p * w.nK * 4);
-    w.yhT = alias ? w.xhT : o; if (!alias) o += xc_align((int64_t)q * w.nK * 4);
+    w.xhT = o; o += ws_align((int64_t)p * w.nK * 4);
+    w.yhT = alias ? w.xhT : o; if (!alias) o += ws_align((int64_t)q * w.nK * 4);
     if (backward) {
-        w.xh = o; o += xc_align((int64_t)n * w.pK * 4);
-        w.yh = alias ? w.xh : o; if (!alias) o += xc_align((int64_t)n * w.qK * 4);
-        w.G = o; o += xc_align((int64_t)w.R * (w.pK > w.qK ? w.pK : w.qK) * 4);
-        w.dxh = o; o += xc_align((int64_t)n * w.R * 4);
+        w.xh = o; o += ws_align((int64_t)n * w.pK * 4);
+        w.yh = alias ? w.xh : o; if (!alias) o += ws_align((int64_t)n * w.qK * 4);
+        w.G = o; o += ws_align((int64_t)w.R * (w.pK > w.qK ? w.pK : w.qK) * 4);
+        w.dxh = o; o += ws_align((int64_t)n * w.R * 4);
     } else {
-        w.part = o; o += xc_align((int64_t)xc_tiles(p) * xc_tiles(q) * 16);
+        w.part = o; o += ws_align((int64_t)xc_tiles(p) * xc_tiles(q) * 16);
     }
     w.total = o;
     return w;
 }
-
-template <class T>
-T* xc_at(void* ws, int64_t off) { return reinterpret_cast<T*>(static_cast<unsigned char*>(ws) + off); }
 
 int xc_centre(const float* x, int64_t ld, int n, int p, int nK, int pK, const float* mean, const float* var, int norm, float eps, float* xh,
               float* xhT, hipStream_t s) {
@@ -440,8 +370,8 @@ int launch_xcorr_fwd(const float* x, int64_t ldx, const float* y, int64_t ldy, i
     const bool alias = x == y;
     BVC_REQUIRE(mean_x && var_x && stats2 && (alias || (mean_y && var_y)), "%s: null argument", who);
     const XcLayout w = xc_layout(n, p, q, alias, 0, false);
-    float* xhT = xc_at<float>(workspace, w.xhT);
-    float* yhT = xc_at<float>(workspace, w.yhT);
+    float* xhT = ws_at<float>(workspace, w.xhT);
+    float* yhT = ws_at<float>(workspace, w.yhT);
     xc_stats_kernel<<<dim3((unsigned)((p + 31) / 32)), dim3(256), 0, s>>>(x, ldx, n, p, ddof, mean_x, var_x);
     if (int rc = xc_centre(x, ldx, n, p, w.nK, w.pK, mean_x, var_x, norm, eps, nullptr, xhT, s)) return rc;
     if (!alias) {
@@ -449,7 +379,7 @@ int launch_xcorr_fwd(const float* x, int64_t ldx, const float* y, int64_t ldy, i
         if (int rc = xc_centre(y, ldy, n, q, w.nK, w.qK, mean_y, var_y, norm, eps, nullptr, yhT, s)) return rc;
     }
     const int tiles = xc_tiles(p) * xc_tiles(q);
-    XcFwdArgs a{xhT, yhT, xc_at<double>(workspace, w.part), p, q, w.nK, scale, diag_target};
+    XcFwdArgs a{xhT, yhT, ws_at<double>(workspace, w.part), p, q, w.nK, scale, diag_target};
     xc_fwd_kernel<<<dim3((unsigned)tiles), dim3(256), 0, s>>>(a);
     xc_final_kernel<<<dim3(1), dim3(256), 0, s>>>(a.part, tiles, stats2);
     BVC_CHECK_HIP(hipGetLastError());
@@ -469,15 +399,15 @@ int launch_xcorr_bwd(const float* x, int64_t ldx, const float* y, int64_t ldy, i
     BVC_REQUIRE(lddx >= p, "%s: row stride of dx %lld below p %d", who, (long long)lddx, p);
     BVC_REQUIRE(alias || lddy >= q, "%s: row stride of dy %lld below q %d", who, (long long)lddy, q);
     const XcLayout l = xc_layout(n, p, q, alias, block_cols, true);
-    float* xhT = xc_at<float>(workspace, l.xhT);
-    float* yhT = xc_at<float>(workspace, l.yhT);
-    float* xh = xc_at<float>(workspace, l.xh);
-    float* yh = xc_at<float>(workspace, l.yh);
+    float* xhT = ws_at<float>(workspace, l.xhT);
+    float* yhT = ws_at<float>(workspace, l.yhT);
+    float* xh = ws_at<float>(workspace, l.xh);
+    float* yh = ws_at<float>(workspace, l.yh);
     if (int rc = xc_centre(x, ldx, n, p, l.nK, l.pK, mean_x, var_x, norm, eps, xh, xhT, s)) return rc;
     if (!alias)
         if (int rc = xc_centre(y, ldy, n, q, l.nK, l.qK, mean_y, var_y, norm, eps, yh, yhT, s)) return rc;
     XcBwdArgs a{};
-    a.w = w; a.G = xc_at<float>(workspace, l.G); a.dxh = xc_at<float>(workspace, l.dxh);
+    a.w = w; a.G = ws_at<float>(workspace, l.G); a.dxh = ws_at<float>(workspace, l.dxh);
     a.n = n; a.nK = l.nK; a.R = l.R; a.norm = norm; a.ddof = ddof; a.eps = eps; a.scale = scale; a.target = diag_target;
     a.factor = alias ? 2.0f : 1.0f;
     a.ownT = xhT; a.otherT = yhT; a.own = xh; a.other = yh; a.src = x; a.ldsrc = ldx; a.mean = mean_x; a.var = var_x; a.dvar = dvar_x;

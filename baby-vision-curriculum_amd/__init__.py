@@ -28,6 +28,8 @@ from .augment import (FRAME_RANDAUG, RANDAUG_OPS, RandAugment, empty_randaug_tab
                       rand_augment_host, sample_randaug_params)
 from . import simclr, distributed, jepa, jepa_mask, checkpoint, launch, comm, probe, retrieval, separability, attentive, xcorr  # noqa: F401
 from .attentive import AttentiveClassifier, AttentivePooler, attentive_pool  # noqa: F401
+from . import dino  # noqa: F401
+from .dino import DINOHead, DINOLoss, dino_loss, prototype_ce, update_teacher  # noqa: F401
 from . import input as input_pipeline  # noqa: F401
 from .input import ClipUploadRing  # noqa: F401
 from . import jpeg  # noqa: F401

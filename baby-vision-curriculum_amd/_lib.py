@@ -260,6 +260,14 @@ SYMBOLS = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "bvc_op_ntxent_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                   c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "bvc_op_proto_ce_splits": (c_int, [c_int, c_int, c_int]),
+    "bvc_op_proto_ce_block": (c_int, [c_int, c_int, c_int]),
+    "bvc_op_proto_ce_workspace": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "bvc_op_proto_ce_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
+                                    c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bvc_op_proto_ce_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
+                                    c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_void_p, c_void_p]),
     "bvc_op_xcorr_block_cols": (c_int, [c_int, c_int, c_int]),
     "bvc_op_xcorr_workspace": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "bvc_op_xcorr_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float,

@@ -6,6 +6,7 @@
 
 #include "attnpool.h"
 #include "ntxent.h"
+#include "proto_ce.h"
 #include "xcorr.h"
 #include "context.h"
 #include "optim_layerwise.h"
@@ -440,6 +441,23 @@ int bvc_op_ntxent_bwd(const float* f, int64_t ldf, const int32_t* groups, int vi
                       int64_t lddf, void* workspace, void* stream) {
     return launch_ntxent_bwd(f, ldf, groups, views, n, p, temperature, eps, lse, npos, row_weight, key_splits, block_rows, df, lddf,
                              workspace, (hipStream_t)stream);
+}
+// ============================================================================ prototype cross-entropy, DINO (proto_ce.hip)
+int bvc_op_proto_ce_splits(int m, int K, int p) { return proto_ce_splits(m, K, p); }
+int bvc_op_proto_ce_block(int m, int K, int p) { return proto_ce_block(m, K, p); }
+int64_t bvc_op_proto_ce_workspace(int m, int K, int p, int splits, int block) { return proto_ce_workspace(m, K, p, splits, block); }
+int bvc_op_proto_ce_fwd(const float* xs, int64_t ldxs, const float* vs, int64_t ldvs, const float* xt, int64_t ldxt, const float* vt,
+                        int64_t ldvt, const float* center, int m, int K, int p, float tau_s, float tau_t, float eps, int splits,
+                        float* row_loss, float* lse_s, float* lse_t, float* stats2, float* batch_center, void* workspace, void* stream) {
+    return launch_proto_ce_fwd(xs, ldxs, vs, ldvs, xt, ldxt, vt, ldvt, center, m, K, p, tau_s, tau_t, eps, splits, row_loss, lse_s, lse_t,
+                               stats2, batch_center, workspace, (hipStream_t)stream);
+}
+int bvc_op_proto_ce_bwd(const float* xs, int64_t ldxs, const float* vs, int64_t ldvs, const float* xt, int64_t ldxt, const float* vt,
+                        int64_t ldvt, const float* center, int m, int K, int p, float tau_s, float tau_t, float eps, const float* lse_s,
+                        const float* lse_t, const float* row_weight, int splits, int block, float* dxs, int64_t lddxs, float* dvs,
+                        int64_t lddvs, void* workspace, void* stream) {
+    return launch_proto_ce_bwd(xs, ldxs, vs, ldvs, xt, ldxt, vt, ldvt, center, m, K, p, tau_s, tau_t, eps, lse_s, lse_t, row_weight, splits,
+                               block, dxs, lddxs, dvs, lddvs, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -856,6 +856,53 @@ int bvc_op_ntxent_fwd(const float* f, int64_t ldf, const int32_t* groups, int vi
 int bvc_op_ntxent_bwd(const float* f, int64_t ldf, const int32_t* groups, int views, int n, int p, float temperature, float eps,
                       const float* lse, const int32_t* npos, const float* row_weight, int key_splits, int block_rows, float* df,
                       int64_t lddf, void* workspace, void* stream);
+/* Prototype cross-entropy (csrc/proto_ce.hip): the loss of DINO and of the [CLS] half of iBOT / DINOv2 for ONE (teacher view,
+ * student view) pair.  xs, xt f32 [m] rows of p columns (row strides ldxs, ldxt): row i of xt is the teacher row paired with row i
+ * of xs.  vs, vt f32 [K] rows of p columns (row strides ldvs, ldvt): the student's and the teacher's prototype weights, the
+ * weight-normalised last layer of a DINO head with gain 1.  center f32 [K] or NULL (= 0): any per-prototype shift.  With
+ * xsn_i = xs_i / max(|xs_i|, eps), wsn_k = vs_k / |vs_k| (xtn, wtn likewise), s_ik = xsn_i . wsn_k / tau_s and
+ * t_ik = (xtn_i . wtn_k - center_k) / tau_t:
+ *   lse_s f32 [m]         Ls_i = log sum_k exp(s_ik)
+ *   lse_t f32 [m]         Lt_i = log sum_k exp(t_ik)
+ *   row_loss f32 [m]      l_i = Ls_i - sum_k q_ik s_ik,  q_ik = exp(t_ik - Lt_i)   (= sum_k -q_ik log_softmax(s_i)_k)
+ *   stats2 f32 [2]        { sum_i l_i / m,  the number of zero rows of vs plus the number of zero rows of vt }
+ *   batch_center f32 [K]  (1 / m) sum_i xtn_i . wtn_k, the raw teacher scores before centre and temperature; may be NULL
+ * A prototype row of norm 0 has no direction: it is given wsn_k = 0 (wtn_k = 0), so it scores 0, takes part in the softmax with
+ * that score and receives dvs_k = 0; stats2[1] counts such rows on the device, so that a caller can look at it when it next
+ * synchronises anyway.  Only an exact 0 counts: a row holding NaN gives NaN scores, and the loss shows it.
+ * Backward, for per-row weights row_weight f32 [m] (the mean: gout / m); the teacher side and center get no gradient: dS_ik = w_i (exp(s_ik - Ls_i) - q_ik) / tau_s, dxsn = dS wsn, dwsn = dS^T xsn,
+ * dxs_i = (dxsn_i - xsn_i (xsn_i . dxsn_i)) / max(|xs_i|, eps) (dxsn_i / eps where the clamp is active),
+ * dvs_k = (dwsn_k - wsn_k (wsn_k . dwsn_k)) / |vs_k|.  dxs f32 [m] rows (stride lddxs), dvs f32 [K] rows (stride lddvs).  lse_s and
+ * lse_t as the forward wrote them; nothing else survives from the forward.
+ * All arithmetic is f32 (v_mfma_f32_32x32x2_f32 products, every score one accumulation chain over the p columns); the forward stores
+ * no array of m x K elements, the backward holds two blocks of m x block f32 in the workspace.
+ *   splits     0 = chosen by the library (bvc_op_proto_ce_splits: about two workgroups per CU, at most one per 128-prototype tile, at
+ *              most 512), else the prototype tiles of every 128-row tile are cut into that many contiguous ranges (up to 2048; empty
+ *              ranges are legal), merged in ascending order.  Different split counts agree to rounding, not bit for bit.
+ *   block      0 = chosen by the library (bvc_op_proto_ce_block: the most whole 128-prototype tiles whose dS block [m up to 128][block]
+ *              f32 stays under 64 MiB), else rounded up to a multiple of 128.  dvs has the same bits for every block (the
+ *              contraction over the rows is complete within a block); dxs is summed block after block and agrees to rounding.
+ *   workspace  bvc_op_proto_ce_workspace(m, K, p, splits, block) bytes, 16-byte aligned (-1 for a refused shape); serves the forward
+ *              and the backward; its contents on entry do not matter.  The forward touches only the leading part (the vectors, the
+ *              split partials and the four normalised operands), whose size does not depend on block: a caller of the forward alone
+ *              may pass bvc_op_proto_ce_workspace(m, K, p, splits, 128) bytes, the smallest block (137 MiB instead of 327 MiB at
+ *              m = 1024, K = 65536, p = 256).  It holds the normalised operands (2 m p + 2 K p floats, m
+ *              and K rounded up to 128, p to 32), in the backward also the transposes and gradients of a block, 2 m block floats
+ *              of dS and the partial products of dxsn (up to 32 MiB).  m = 1024, K = 65536, p = 256: 327 MiB.  The largest shape (m = 32768, K = 262144, p = 8192): 21.2 GiB.
+ * Read: the p columns of the rows (never the stride padding).  Written: the named outputs and the workspace, nothing else.  No
+ * atomics and no host synchronisation or allocation: the same bits on every run, and the calls may be captured in a graph.
+ * BVC_ERR_INVALID (bvc_last_error) and nothing launched unless 1 <= m <= 32768, 1 <= K <= 262144, 1 <= p <= 8192, tau_s, tau_t and
+ * eps positive and finite, every stride at least p, 0 <= splits <= 2048, block >= 0 and no required pointer null. */
+int bvc_op_proto_ce_splits(int m, int K, int p);
+int bvc_op_proto_ce_block(int m, int K, int p);
+int64_t bvc_op_proto_ce_workspace(int m, int K, int p, int splits, int block);
+int bvc_op_proto_ce_fwd(const float* xs, int64_t ldxs, const float* vs, int64_t ldvs, const float* xt, int64_t ldxt, const float* vt,
+                        int64_t ldvt, const float* center, int m, int K, int p, float tau_s, float tau_t, float eps, int splits,
+                        float* row_loss, float* lse_s, float* lse_t, float* stats2, float* batch_center, void* workspace, void* stream);
+int bvc_op_proto_ce_bwd(const float* xs, int64_t ldxs, const float* vs, int64_t ldvs, const float* xt, int64_t ldxt, const float* vt,
+                        int64_t ldvt, const float* center, int m, int K, int p, float tau_s, float tau_t, float eps, const float* lse_s,
+                        const float* lse_t, const float* row_weight, int splits, int block, float* dxs, int64_t lddxs, float* dvs,
+                        int64_t lddvs, void* workspace, void* stream);
 /* Feature cross-correlation with a reduced epilogue (csrc/xcorr.hip): Barlow Twins, VICReg's covariance term and linear CKA.
  * x f32 [n] rows of p columns (row stride ldx elements), y f32 [n] rows of q columns (row stride ldy); y may be the SAME POINTER as
  * x with q == p and ldy == ldx, the auto-covariance ("alias") case.  Per column j of x (likewise of y):

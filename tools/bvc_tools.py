@@ -4,7 +4,7 @@
     python tools/bvc_tools.py list                       # what exists, one line each
     python tools/bvc_tools.py ab <name> [args ...]       # a same-process A/B or experiment (tools/ab/<name>.py or <name>_ab.py)
     python tools/bvc_tools.py pmc <name> [args ...]      # a counter reduction / single-kernel driver (tools/pmc/<name>.py or pmc_<name>.py)
-    python tools/bvc_tools.py bench <jepa|simclr|encode|retrieval|separability|attentive|ntxent|xcorr|jpeg> [args ...]
+    python tools/bvc_tools.py bench <jepa|simclr|encode|retrieval|separability|attentive|ntxent|proto_ce|xcorr|jpeg> [args ...]
     python tools/bvc_tools.py fixtures jpeg [--extract DIR]   # rewrite (needs PIL) or unpack tests/golden/jpeg_*.json
     python tools/bvc_tools.py screen [gemm8|persist]     # race screens
     python tools/bvc_tools.py probe [step|gemm]          # per-product tables of one training step
@@ -20,7 +20,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GROUPS = {"ab": ("ab", ("{}.py", "{}_ab.py")), "pmc": ("pmc", ("{}.py", "pmc_{}.py"))}
-TOP = {"bench": {"jepa": "bench_jepa.py", "simclr": "bench_simclr.py", "encode": "bench_encode.py", "retrieval": "bench_retrieval.py", "separability": "bench_separability.py", "attentive": "bench_attentive.py", "ntxent": "bench_ntxent.py", "xcorr": "bench_xcorr.py", "jpeg": "bench_jpeg.py"},
+TOP = {"bench": {"jepa": "bench_jepa.py", "simclr": "bench_simclr.py", "encode": "bench_encode.py", "retrieval": "bench_retrieval.py", "separability": "bench_separability.py", "attentive": "bench_attentive.py", "ntxent": "bench_ntxent.py", "proto_ce": "bench_proto_ce.py", "xcorr": "bench_xcorr.py", "jpeg": "bench_jpeg.py"},
        "fixtures": {"jpeg": "make_jpeg_golden.py"},
        "screen": {"gemm8": "g8_race_screen.py", "persist": "persist_race_screen.py"},
        "probe": {"step": "step_probe.py", "gemm": "gemm_probe.py"}}
